@@ -13,6 +13,12 @@ reference's own `Perf/total_fps` formula (mh_ppo.py:649-652).
 
 Prints ONE JSON line on rank 0.  `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset) re-starts itself under
 `torch.distributed.run` BEFORE anything touches the GPU, so the 1 -> 8 curve needs no wrapper.
+
+A plain run sets up, warms up, times the `--steps` iterations and prints the line.  `--full` adds what takes runs of its own: the
+k_env_step roofline meter (`eager`, `roofline`), the stand-alone gradient all-reduce (`collectives.grad_allreduce_ms`), and at N = 1 the
+configs[2] `secondary` run, the one-rank RCCL `dp1_rehearsal` and the CPU `cpu_baseline`.  `--dump-outputs DIR` writes what the last
+timed iteration computed (observations, rollout buffers, losses, updated weights) as DIR/*.npy; the inputs are seeded, so two builds
+compare output for output.
 """
 import argparse
 import ctypes as C
@@ -227,6 +233,49 @@ def allreduce_probe(numel, device, reps=20):
     return float(t)
 
 
+def algo_parameters(algo):
+    """(name, parameter) of the agent's networks: ppo_mimic's one ActorCritic, or MHPPO's actor and critic"""
+    if hasattr(algo, "alg"):
+        return list(algo.alg.named_parameters())
+    return [("actor." + n, p) for n, p in algo.actor.named_parameters()] + [("critic." + n, p) for n, p in algo.critic.named_parameters()]
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(algo, obs, losses, out_dir, max_envs=1024):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per array (float32, or float64 for wider types) —
+    `obs.*` the observations `_rollout_step` returned, `rollout.*` the buffers it filled (its observation slabs excepted), `loss.*` what
+    `_training_step` returned and `param.*` the networks after its update.  Arrays over envs keep a fixed, seeded sample of `max_envs`
+    envs, halved until the whole dump fits in DUMP_MAX_BYTES."""
+    import numpy as np
+
+    st = algo.storage
+    rollout = [k for k in st.stored_keys if k not in obs and not k.startswith("next_")]
+    params = [(n, p.detach()) for n, p in algo_parameters(algo)]
+    wide = (torch.float64, torch.int64, torch.int32)
+    size = lambda t: t.numel() * (8 if t.dtype in wide else 4)           # bytes as written
+    N = st.num_envs
+    fixed = sum(size(p) for _, p in params) + sum(size(v) for v in losses.values())
+    per_env = sum(size(obs[k][0]) for k in obs) + sum(size(getattr(st, k)[:, 0]) for k in rollout)
+    n = min(N, max_envs)
+    while n > 1 and fixed + n * per_env > DUMP_MAX_BYTES:
+        n //= 2
+    if fixed + n * per_env > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_MAX_BYTES >> 20} MB")
+    idx = torch.arange(N) if n == N else torch.from_numpy(np.sort(np.random.default_rng(0).choice(N, n, replace=False)))
+    idx = idx.to(st.actions.device)
+    arrays = {f"obs.{k}": obs[k].index_select(0, idx) for k in obs}
+    arrays.update({f"rollout.{k}": getattr(st, k).index_select(1, idx) for k in rollout})
+    arrays.update({f"loss.{k}": v for k, v in losses.items()})
+    arrays.update({f"param.{k}": p for k, p in params})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.double() if a.dtype in wide else a.float()
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 # BASELINE.json's metric string, verbatim; the GPU count a line was measured on is `n_gpus` / `measured_on`
 METRIC = "env-steps/s (obs+reward+PPO update), 4096 G1 envs @1/2/4/8 MI355X"
 
@@ -258,14 +307,17 @@ def dry_run(a, world, rank):
         dist.destroy_process_group()
 
 
-def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=True):
-    """One timed run: W warm-up iterations, then exactly K iterations between barrier + synchronize; returns the JSON object on rank 0."""
+def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=True, full=True, dump_dir=None):
+    """One timed run: W warm-up iterations, then exactly K iterations between barrier + synchronize; returns the JSON object on rank 0.
+    `dump_dir`: rank 0 writes what the last timed iteration computed there (dump_outputs).  `full`: the measurements beyond the timed
+    iterations follow — the k_env_step roofline meter (E eager iterations) and, data-parallel, the stand-alone gradient all-reduce."""
     cfg, env, MHPPO = build(N, device, seed=1234 + rank, workload=workload, num_clips=clips)
     algo = MHPPO(env=env, config=cfg.algo.config, log_dir=None, device=device)
     algo.setup()
     T = algo.num_steps_per_env
     obs = env.reset_all()
     E = 2                                                    # eager, per-launch-timed iterations after the timed region (the roofline meter)
+    # (the replay window holds frames for them with or without `full`: the same window, the same frames for the timed iterations)
     frames = (K + max(W, 2) + E) * T + 2
     env.simulator.set_replay(*make_replay_on_device(env, frames, seed=99 + rank))
     algo._train_mode()
@@ -296,7 +348,7 @@ def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=
         ev[3 * i].record()
         obs = algo._rollout_step(obs)
         ev[3 * i + 1].record()
-        algo._training_step()
+        losses = algo._training_step()
         ev[3 * i + 2].record()
     sync()
     dt = time.perf_counter() - t0
@@ -308,34 +360,37 @@ def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=
     dt = float(tmax)
     rollout_ms = sum(ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(K)) / K
     update_ms = sum(ev[3 * i + 1].elapsed_time(ev[3 * i + 2]) for i in range(K)) / K
-    # --- roofline of the fused obs/reward step kernel: a HIP event pair attached to each k_env_step dispatch.  A graph replay cannot carry
-    # per-launch events, so the meter runs right AFTER the timed region: E more iterations of the same workload with the rollout loop eager
-    # (env.set_profiling switches the step to the hipExt launch form, which `rollout_graph_safe` excludes from a capture) — the kernel, its
-    # inputs and its neighbours on the stream are the ones of the timed iterations; `eager` reports what those iterations took.
-    env.set_profiling(True)
-    te0 = time.perf_counter()
-    for i in range(K, K + E):
-        ev[3 * i].record()
-        obs = algo._rollout_step(obs)
-        ev[3 * i + 1].record()
-        algo._training_step()
-        ev[3 * i + 2].record()
-    sync()
-    eager_ms = (time.perf_counter() - te0) / E * 1e3
-    eager_rollout_ms = sum(ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(K, K + E)) / E
-    buf = (C.c_float * 512)()
-    cnt = C.c_int(0)
-    _lib.check(lib.pbhc_env_profile_read(env._env, buf, min(512, E * T), C.byref(cnt)))
-    kern_ms = sum(buf[i] for i in range(cnt.value)) / max(cnt.value, 1)      # the RAW event-pair reading: what roofline.achieved / frac use
-    # what the dispatch-attached pair reads beyond a kernel's execution, from a kernel of known duration (a 20 us spin): published next to
-    # the raw value, not subtracted from it (round 2 subtracted it and read 5-7 % below rocprofv3 of the same launches)
-    ov = C.c_float(0.0)
-    _lib.check(lib.pbhc_env_profile_overhead(env._env, _lib.current_stream(), C.byref(ov)))
-    ev_overhead_ms = max(0.0, float(ov.value))
-    words, motion_words, _, _ = algorithmic_bytes_per_env_step(env)
-    alg_bytes = 4.0 * (words + motion_words) * N
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    nets = list(algo.alg.named_parameters()) if hasattr(algo, "alg") else list(algo.actor.named_parameters()) + list(algo.critic.named_parameters())
+    if dump_dir and rank == 0:
+        dump_outputs(algo, obs, losses, dump_dir)
+    if full:
+        # --- roofline of the fused obs/reward step kernel: a HIP event pair attached to each k_env_step dispatch.  A graph replay cannot carry
+        # per-launch events, so the meter runs right AFTER the timed region: E more iterations of the same workload with the rollout loop eager
+        # (env.set_profiling switches the step to the hipExt launch form, which `rollout_graph_safe` excludes from a capture) — the kernel, its
+        # inputs and its neighbours on the stream are the ones of the timed iterations; `eager` reports what those iterations took.
+        env.set_profiling(True)
+        te0 = time.perf_counter()
+        for i in range(K, K + E):
+            ev[3 * i].record()
+            obs = algo._rollout_step(obs)
+            ev[3 * i + 1].record()
+            algo._training_step()
+            ev[3 * i + 2].record()
+        sync()
+        eager_ms = (time.perf_counter() - te0) / E * 1e3
+        eager_rollout_ms = sum(ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(K, K + E)) / E
+        buf = (C.c_float * 512)()
+        cnt = C.c_int(0)
+        _lib.check(lib.pbhc_env_profile_read(env._env, buf, min(512, E * T), C.byref(cnt)))
+        kern_ms = sum(buf[i] for i in range(cnt.value)) / max(cnt.value, 1)      # the RAW event-pair reading: what roofline.achieved / frac use
+        # what the dispatch-attached pair reads beyond a kernel's execution, from a kernel of known duration (a 20 us spin): published next to
+        # the raw value, not subtracted from it (round 2 subtracted it and read 5-7 % below rocprofv3 of the same launches)
+        ov = C.c_float(0.0)
+        _lib.check(lib.pbhc_env_profile_overhead(env._env, _lib.current_stream(), C.byref(ov)))
+        ev_overhead_ms = max(0.0, float(ov.value))
+        words, motion_words, _, _ = algorithmic_bytes_per_env_step(env)
+        alg_bytes = 4.0 * (words + motion_words) * N
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+    nets = algo_parameters(algo)
     flops_per_sample = 2.0 * sum(p.numel() for n, p in nets if n.endswith("weight") and p.dim() == 2)     # Linear layers only (conv windows not counted)
     upd_flops_3x = 3.0 * flops_per_sample * T * N * algo.num_learning_epochs          # SURVEY 8d's convention: backward = 2 x forward for every layer
     if hasattr(algo, "alg"):
@@ -348,7 +403,7 @@ def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=
             per += sum(2.0 * l.in_features * l.out_features * (3.0 if i else 2.0) for i, l in enumerate(lins))
         upd_flops, flops_note = per * T * N * algo.num_learning_epochs, "executed GEMM work (no input gradient for the first layers)"
     n_grad = sum(p.numel() for _, p in nets)
-    ar_ms = allreduce_probe(n_grad, device) if dp else None
+    ar_ms = allreduce_probe(n_grad, device) if dp and full else None
     out = None
     if rank == 0:
         out = {
@@ -359,21 +414,24 @@ def measure(workload, clips, N, K, W, rank, world, dp, device, backend, primary=
                                    f", {T} steps/iter, 5 epochs x 4 minibatches; replay sim-stub tensors resident in HBM",
                        "envs_per_gpu": N, "global_envs": N * world, "num_steps_per_env": T, "parallelism": f"dp{world}"},
             "rollout_ms": rollout_ms, "update_ms": update_ms, "rollout_mode": rollout_mode,
-            "eager": {"ms_per_step": eager_ms, "rollout_ms": eager_rollout_ms, "steps": E,
-                      "note": "the same workload with the rollout loop launched step by step (PBHC_ROLLOUT_GRAPH=0 / while per-launch event pairs are on): "
-                              "the iterations the roofline meter below ran in, right after the timed region"},
-            "roofline": {"kernel": "k_env_step", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "frac_by_survey_bytes": (SURVEY_BYTES_PER_ENV_STEP[workload] * N / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if workload in SURVEY_BYTES_PER_ENV_STEP else None,
-                         "traffic": pmc_traffic_bytes(workload) if (N == 4096 and clips == (1 if workload == "v1_walk" else 256)) else None, "kernel_ms": kern_ms, "kernel_ms_minus_event_overhead": max(kern_ms - ev_overhead_ms, 1e-6), "event_pair_overhead_ms": ev_overhead_ms, "launches_timed": cnt.value,
-                         "measured_in": f"{E} eager iterations right after the timed region (see `eager`)",
-                         "kernel_specialised_to_config": bool(env.is_specialised),
-                         "algorithmic_bytes_per_launch": alg_bytes, "bytes_per_env_step": 4.0 * (words + motion_words),
-                         "bytes_per_env_step_excl_cached_motion_rows": 4.0 * words},
             "roofline_update": {"bound": "mfma", "achieved": upd_flops / (update_ms * 1e-3) / 1e12, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                 "frac": upd_flops / (update_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, "flops": upd_flops, "flops_counted": flops_note,
                                 "frac_by_3x_forward_convention": upd_flops_3x / (update_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
                                 "note": "whole update phase, fp32: fused MFMA forward / input-gradient Linear kernels + library weight-gradient GEMMs + loss + gather + Adam"},
         }
+        if full:
+            out.update({
+                "eager": {"ms_per_step": eager_ms, "rollout_ms": eager_rollout_ms, "steps": E,
+                          "note": "the same workload with the rollout loop launched step by step (PBHC_ROLLOUT_GRAPH=0 / while per-launch event pairs are on): "
+                                  "the iterations the roofline meter below ran in, right after the timed region"},
+                "roofline": {"kernel": "k_env_step", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "frac_by_survey_bytes": (SURVEY_BYTES_PER_ENV_STEP[workload] * N / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if workload in SURVEY_BYTES_PER_ENV_STEP else None,
+                             "traffic": pmc_traffic_bytes(workload) if (N == 4096 and clips == (1 if workload == "v1_walk" else 256)) else None, "kernel_ms": kern_ms, "kernel_ms_minus_event_overhead": max(kern_ms - ev_overhead_ms, 1e-6), "event_pair_overhead_ms": ev_overhead_ms, "launches_timed": cnt.value,
+                             "measured_in": f"{E} eager iterations right after the timed region (see `eager`)",
+                             "kernel_specialised_to_config": bool(env.is_specialised),
+                             "algorithmic_bytes_per_launch": alg_bytes, "bytes_per_env_step": 4.0 * (words + motion_words),
+                             "bytes_per_env_step_excl_cached_motion_rows": 4.0 * words},
+            })
         if dp:
             out["collectives"] = {"backend": backend, "all_reduces_per_iter": coll["all_reduce"] / K, "all_reduce_bytes_per_iter": coll["all_reduce_bytes"] / K,
                                   "grad_allreduce_ms": ar_ms, "grad_bucket_bytes": 4 * n_grad,
@@ -418,10 +476,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] (general tracking, 256 clips) measurement appended to the default run")
-    ap.add_argument("--no-dp-rehearsal", action="store_true", help="skip the one-rank RCCL rehearsal of the data-parallel path appended to the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] (general tracking, 256 clips) measurement appended to a --full run")
+    ap.add_argument("--no-dp-rehearsal", action="store_true", help="skip the one-rank RCCL rehearsal of the data-parallel path appended to a --full run")
     ap.add_argument("--workload", default="v1_walk", choices=sorted(WORKLOADS.keys()))
     ap.add_argument("--clips", type=int, default=1, help="synthetic motion library of this many clips (general-tracking workloads)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline figure: the k_env_step roofline meter, "
+                    "the stand-alone gradient all-reduce, the configs[2] secondary run, the one-rank RCCL rehearsal and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed iteration computed to DIR/<name>.npy (at most 64 MB)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus, sys.argv[1:]))          # no GPU call has happened in this process
@@ -453,8 +514,8 @@ def main():
             os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
         dist.init_process_group(backend=backend, **({"device_id": torch.device(device)} if backend == "nccl" else {}))
     dp = world > 1 or force
-    out = measure(a.workload, a.clips, a.envs, a.steps, a.warmup, rank, world, dp, device, backend, primary=True)
-    if rank == 0:
+    out = measure(a.workload, a.clips, a.envs, a.steps, a.warmup, rank, world, dp, device, backend, primary=True, full=a.full, dump_dir=a.dump_outputs)
+    if rank == 0 and a.full:
         # BASELINE.json configs[2] in the same driver-visible record: 4096 envs, G1 29-DoF general tracking, 256-clip synthetic library
         if world == 1 and a.workload == "v1_walk" and not a.no_secondary:
             sec = measure("v2_teacher29", 256, a.envs, 3, 2, rank, world, False, device, backend, primary=False)
@@ -468,6 +529,7 @@ def main():
             out["dp1_rehearsal"] = dp1_rehearsal(a, device, out["ms_per_step"])
         if world == 1 and not a.no_cpu_baseline and a.workload == "v1_walk":
             out["cpu_baseline"] = cpu_baseline(num_envs_sample=a.envs)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dp:
         dist.destroy_process_group()

@@ -1,6 +1,6 @@
 """`Skeleton.from_mjcf` RUN, not its stored output (torch_humanoid_batch.py:104-165 is what it restates): a small
-hand-written MJCF with hand-derived tables runs everywhere; the two G1 files of the reference are parsed where /root/reference exists
-(this container) and compared with the tables the reference's own `Humanoid_Batch` produced (tests/golden/skeleton_fk_g1_*.npz, written by
+hand-written MJCF with hand-derived tables runs everywhere; the reference's two G1 files (stored as fixtures under tests/golden/mjcf/)
+are parsed and compared with the tables the reference's own `Humanoid_Batch` produced (tests/golden/skeleton_fk_g1_*.npz, written by
 oracle/ref_harness/gen_golden.py from the unmodified reference) and with the JSON the fixtures ship."""
 import os
 
@@ -11,7 +11,7 @@ from pbhc_amd import _lib
 from pbhc_amd.skeleton import Skeleton
 from tests.helpers import GOLDEN, fixture_config
 
-REF_G1 = "/root/reference/description/robots/g1"
+REF_G1 = os.path.join(GOLDEN, "mjcf")          # the reference's description/robots/g1/*.xml, verbatim
 
 
 def test_from_mjcf_on_a_hand_written_file():
@@ -62,7 +62,6 @@ def test_skeleton_larger_than_the_kernel_maxima_is_refused():
         sk.to_c()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_G1), reason="the reference's MJCF files exist in the build container only")
 @pytest.mark.parametrize("xml,cfgname,robot,json_name", [
     ("g1_23dof_lock_wrist_fitmotionONLY.xml", "v1_g1_23dof_walk.yaml", "g1_23dof", "skeleton_g1_23dof_lock_wrist_fitmotionONLY.json"),
     ("g1_29dof_rev_1_0.xml", "v2_g1_29dof_teacher.yaml", "g1_29dof", "skeleton_g1_29dof_rev_1_0.json")])

@@ -8,10 +8,10 @@ mkdir -p $O
 # the specialised kernels of the probed configs are built first, outside any profiler (cached in pbhc_amd/_spec for the rest of the call)
 python3 tools/kernel_probe.py 4096 > $O/probe_specialised.txt 2>&1
 PBHC_SPECIALISE=off python3 tools/kernel_probe.py 4096 > $O/probe_generic.txt 2>&1
-python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-dp-rehearsal > $O/bench_prebuild.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/v1 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-dp-rehearsal > $O/v1_bench.log 2>&1
+python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --full > $O/bench_prebuild.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/v1 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-dp-rehearsal --full > $O/v1_bench.log 2>&1
 echo "v1 stats done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/v2 -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --workload v2_teacher29 --clips 256 > $O/v2_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/v2 -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --workload v2_teacher29 --clips 256 --full > $O/v2_bench.log 2>&1
 echo "v2 stats done"
 bash tools/env_step_pmc.sh prof3/sq_specialised
 PBHC_SPECIALISE=off bash tools/env_step_pmc.sh prof3/sq_generic

@@ -8,10 +8,10 @@ step prebuild
 python3 tools/kernel_probe.py 4096 > $O/probe_specialised.txt 2>&1
 python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --no-secondary > $O/bench_prebuild.log 2>&1
 step "v1 kernel stats"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v1 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-dp-rehearsal > $O/v1_bench.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v1 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-dp-rehearsal --full > $O/v1_bench.log 2>&1
 cp $(find $O/v1 -name "*kernel_stats.csv" | head -1) $O/round4_bench_kernel_stats.csv
 step "v2 kernel stats"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v2 -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --workload v2_teacher29 --clips 256 > $O/v2_bench.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v2 -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dp-rehearsal --workload v2_teacher29 --clips 256 --full > $O/v2_bench.log 2>&1
 cp $(find $O/v2 -name "*kernel_stats.csv" | head -1) $O/round4_bench_kernel_stats_v2_teacher29.csv
 rm -rf $O/v1 $O/v2
 step "phase stamps"
