@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define PBHC_ABI_VERSION 11
+#define PBHC_ABI_VERSION 12
 
 #define PBHC_OK 0
 #define PBHC_EINVAL (-22)   /* bad argument / size over a compile-time maximum */
@@ -146,6 +146,9 @@ enum PbhcGlobal {
   PBHC_G_SOFT_TAU_VAL = 45,
   PBHC_G_STEP_COUNTER = 46,
   PBHC_G_NOISE_CURRICULUM = 47,
+  PBHC_G_DOF_FAR_THR = 48,                /* terminate_when_dof_far threshold (motion_tracking.py:128-130,283-292) */
+  PBHC_G_DOF_FAR_HIT = 49,                /* 1.0 when k_dof_far_any found an env past the threshold in this step, else 0.0; set by the pre-pass,
+                                           * read by k_env_step, cleared by k_env_finalize */
   PBHC_G_LOG = 64                         /* [PBHC_NUM_LOG] per-step log means, see PbhcLog */
 };
 
@@ -157,6 +160,7 @@ enum PbhcLog {
   PBHC_L_LOCAL_KEY_BODY_DIFF_NORM, PBHC_L_TERM_REF_POS_Z, PBHC_L_TERM_REF_ORI, PBHC_L_TERM_BODY_Z,
   PBHC_L_TERM_CONTACT, PBHC_L_TERM_LOW_HEIGHT,
   PBHC_L_TERM_DOF_POS_LIMIT, PBHC_L_TERM_DOF_VEL_LIMIT, PBHC_L_TERM_TORQUE_LIMIT,
+  PBHC_L_TERM_DOF_FAR, PBHC_L_DOF_FAR_THR,  /* terminate_by_dof_far; the threshold this step's termination test used */
   PBHC_L_NUM
 };
 
@@ -306,6 +310,17 @@ typedef struct PbhcEnvConfig {
   float term_close_prob[3];
   float dof_pos_limits_termination[PBHC_MAX_DOF][2];
   float term_close_vel_scale, term_close_tau_scale;
+  /* termination.terminate_when_dof_far (motion_tracking.py:343-349, v1 only): EVERY env resets in a step where any env's
+   * |ref dof_pos - dof_pos| exceeds PBHC_G_DOF_FAR_THR (a batch-global decision: the pre-pass k_dof_far_any, launched before k_env_step).
+   * termination_curriculum.terminate_when_dof_far_curriculum (:283-292): the threshold moves by (1 +/- degree) against the average episode
+   * length at every step that resets an env, clipped to [min, max] */
+  int32_t terminate_when_dof_far, dof_far_curriculum;
+  float dof_far_degree, dof_far_down, dof_far_up, dof_far_min, dof_far_max;
+  /* noise on the reset state (motion_tracking.py:470-545, general_tracking.py:405-485), init_noise_scale.* x noise_to_initial_level folded in:
+   * root position / linear / angular velocity + N(0,1) x scale, root rotation <- small_random_quaternion(max angle rn_root_rot) (x) rotation,
+   * dof position / velocity + N(0,1) x scale (tracking_mode 1: + U[0,1) x scale, as the reference's rand_like).  reset_noise = 0: no draws */
+  int32_t reset_noise;
+  float rn_root_pos, rn_root_rot, rn_root_vel, rn_root_ang_vel, rn_dof_pos, rn_dof_vel;
   int32_t pad2_;
   uint64_t seed;
 } PbhcEnvConfig;
@@ -347,6 +362,9 @@ typedef struct PbhcStepIO {
   const float* ovr_dof_pos_bias;                                                          /* [N,D] the U(dof_pos_range) draw of randomize_default_dof_pos */
   const int64_t* ovr_delay;       /* [N]                                                       */
   const float* ovr_gate_u;        /* [3]   the per-step uniforms of the terminate_when_close_to_* gates (pos, vel, torque) */
+  /* reset-state noise draws (PbhcEnvConfig.reset_noise), in the reference's call order: ovr_reset_root [N,13] = randn pos (3), randn axis (3),
+   * rand angle (1), randn lin vel (3), randn ang vel (3); ovr_reset_dof_pos / ovr_reset_dof_vel [N,D] = randn (tracking_mode 1: rand) */
+  const float* ovr_reset_root; const float* ovr_reset_dof_pos; const float* ovr_reset_dof_vel;
   /* simulator-surface state (reference names; simulator/isaacgym/isaacgym.py:574-618) */
   float* root_states;             /* [N,13] */
   float* dof_state;               /* [N,D,2] (pos, vel) */

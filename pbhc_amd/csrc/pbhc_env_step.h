@@ -546,6 +546,31 @@ __device__ __forceinline__ void motion_lookup_meta(const PbhcMotionTable& tbl, i
   }
 }
 
+// ---- noise on the reset state (motion_tracking.py:470-545, general_tracking.py:405-485): Philox streams of their own, 12 (root) and 13
+// (dofs), so that every other draw of the step is the same with the noise on or off.  N(0,1) by Box-Muller from one uniform pair.
+__device__ __forceinline__ void box_muller(float u0, float u1, float* z0, float* z1) {
+  const float r = sqrtf(-2.0f * logf(1.0f - u0));            // 1 - u0 in (0, 1]
+  const float a = 6.2831855f * u1;
+  *z0 = r * cosf(a); *z1 = r * sinf(a);
+}
+// the 13 root draws of one reset, in the reference's call order: randn pos (3), randn axis (3), rand angle (1), randn vel (3), randn ang vel (3)
+__device__ __forceinline__ void reset_root_draws(uint64_t seed, uint32_t env, uint32_t step, float z[13]) {
+  float n[12];
+#pragma unroll
+  for (int p = 0; p < 6; ++p) {
+    float u[4];
+    pbhc::rng_uniform4(seed, env, step, 12, (uint32_t)p, u);
+    box_muller(u[0], u[1], &n[2 * p], &n[2 * p + 1]);
+  }
+  float ua[4];
+  pbhc::rng_uniform4(seed, env, step, 12, 6u, ua);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) z[k] = n[k];
+  z[6] = ua[0];
+#pragma unroll
+  for (int k = 7; k < 13; ++k) z[k] = n[k - 1];
+}
+
 // =================================================================================================
 //  k_env_step: LeggedRobotBase.step (legged_robot_base.py:239-338) for LeggedRobotMotionTracking
 // =================================================================================================
@@ -1023,6 +1048,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   uint32_t psrc0 = 0, psrc1 = 0;                              // sources of this lane's two partial-sum columns (kPartTab)
   float sumrow = 0.0f, pf_tscale = 0.0f, pf_sigma = 1.0f, pf_pen_scale = 1.0f, pf_far_thr = 0.0f, kpA = 1.0f, kdA = 1.0f, dpA = 0.0f, etr_old = 0.0f;
   int pf_tid = 0, pf_tpen = 0, pf_tsrc = -1, pf_colterm = -1;
+  bool pf_dof_far = false;                                    // terminate_when_dof_far: the pre-pass (k_dof_far_any) found an env past the threshold
   long long adelay = 0;
   // role-B registers that live across phases (loads issued in its prologue, consumed after bar1)
   float pf_last_act = 0.0f, pf_last_qd = 0.0f;
@@ -1071,6 +1097,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       sumrow = NTLD(at(io.episode_sums, (u32)envc * (u32)c.num_sum_cols + (u32)min(lane, c.num_sum_cols - 1)));
       pf_sigma = (float)glob[PBHC_G_SIGMA + min(lane, PBHC_NUM_SIGMA - 1)];
       pf_pen_scale = (float)glob[PBHC_G_PENALTY_SCALE]; pf_far_thr = (float)glob[PBHC_G_MOTION_FAR_THR];
+      if (c.terminate_when_dof_far) pf_dof_far = glob[PBHC_G_DOF_FAR_HIT] != 0.0;
       kpA = NTLD(at(io.kp_scale, eDc + dc)); kdA = NTLD(at(io.kd_scale, eDc + dc));                // phase H (a reset replaces them in registers)
       dpA = io.default_dof_pos ? at(io.default_dof_pos, eDc + dc) : c.default_dof_pos[dc];
       adelay = io.action_delay_idx[envc];
@@ -1522,7 +1549,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       }
       misc[M_GRAV] = grav; misc[M_FAR] = far; misc[M_END] = tend; misc[M_TOUT_LEN] = tlen;
       misc[M_TIMEOUT] = tout;
-      misc[M_RESET] = (grav != 0.0f || far != 0.0f || tout != 0.0f || refz != 0.0f || refori != 0.0f || bodyz != 0.0f || tcontact != 0.0f || tlowh != 0.0f) ? 1.0f : 0.0f;
+      // terminate_when_dof_far (motion_tracking.py:343-349): torch.any over the ENV axis — decided for the whole batch by k_dof_far_any
+      const bool dof_far = c.terminate_when_dof_far && pf_dof_far;
+      misc[M_RESET] = (grav != 0.0f || far != 0.0f || tout != 0.0f || refz != 0.0f || refori != 0.0f || bodyz != 0.0f || tcontact != 0.0f || tlowh != 0.0f
+                       || dof_far) ? 1.0f : 0.0f;
 #ifdef PBHC_ABL_NORESET
       misc[M_RESET] = 0.0f;
 #endif
@@ -2077,12 +2107,43 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         const f4 q1r = mk4(__shfl(lr1, 3, PBHC_G), __shfl(lr1, 4, PBHC_G), __shfl(lr1, 5, PBHC_G), __shfl(lr1, 6, PBHC_G));
         if (lane == 0) st4(rq, slerp(q0r, q1r, lk_b));
       }
+      if (c.reset_noise && do_reset) {
+        // _reset_dofs: dof_pos / dof_vel + randn x scale (general tracking: rand_like, a one-sided U[0,1) offset, as the reference draws it)
+        for (int dd = lane; dd < D; dd += PBHC_G) {
+          float u[4];
+          pbhc::rng_uniform4(rt.seed, env, step_ctr, 13, dd, u);
+          float zp = u[0], zv = u[1];
+          if (!MODE) box_muller(u[0], u[1], &zp, &zv);
+          if (io.ovr_reset_dof_pos) zp = at(io.ovr_reset_dof_pos, eD + dd);
+          if (io.ovr_reset_dof_vel) zv = at(io.ovr_reset_dof_vel, eD + dd);
+          q[dd] = q[dd] + zp * c.rn_dof_pos;
+          qd[dd] = qd[dd] + zv * c.rn_dof_vel;
+        }
+      }
       WAVE_LDS_FENCE();
       if (do_reset && lane == 0) {
-        st3(root, ld3(rp));
-        st4(root + 3, quat_mul(mk4(0.f, 0.f, 0.f, 1.f), ld4(rq)));       // quat_mul(small_random_quaternions(max_angle=0), root_rot)
-        st3(root + 7, ld3(rv));
-        st3(root + 10, ld3(rw));
+        if (c.reset_noise) {
+          // _reset_root_states: pos / vel / ang vel + randn x scale, rot <- quat_mul(small_random_quaternions(max angle), rot)
+          float z[13];
+          if (io.ovr_reset_root) {
+            for (int k = 0; k < 13; ++k) z[k] = at(io.ovr_reset_root, (u32)env * 13u + (u32)k);
+          } else {
+            reset_root_draws(rt.seed, env, step_ctr, z);
+          }
+          const f3 p0 = ld3(rp), v0 = ld3(rv), w0 = ld3(rw);
+          st3(root, mk3(p0.x + z[0] * c.rn_root_pos, p0.y + z[1] * c.rn_root_pos, p0.z + z[2] * c.rn_root_pos));
+          const float an = sqrtf(z[3] * z[3] + z[4] * z[4] + z[5] * z[5]);
+          const float ha = (c.rn_root_rot * z[6]) / 2.0f;
+          const float sh = sinf(ha);
+          st4(root + 3, quat_mul(mk4(sh * (z[3] / an), sh * (z[4] / an), sh * (z[5] / an), cosf(ha)), ld4(rq)));
+          st3(root + 7, mk3(v0.x + z[7] * c.rn_root_vel, v0.y + z[8] * c.rn_root_vel, v0.z + z[9] * c.rn_root_vel));
+          st3(root + 10, mk3(w0.x + z[10] * c.rn_root_ang_vel, w0.y + z[11] * c.rn_root_ang_vel, w0.z + z[12] * c.rn_root_ang_vel));
+        } else {
+          st3(root, ld3(rp));
+          st4(root + 3, quat_mul(mk4(0.f, 0.f, 0.f, 1.f), ld4(rq)));       // quat_mul(small_random_quaternions(max_angle=0), root_rot)
+          st3(root + 7, ld3(rv));
+          st3(root + 10, ld3(rw));
+        }
       }
     } else if (valid && lane == 0) {
       etr_val = etr_old;

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(64 * PBHC_FIN_CHUNKS) void k_env_finalize(const Pbh
   const int tid = threadIdx.x;
   if (tot_out) {                                     // reduce-only half: the per-launch counters still advance here
     if (tid == 64) {
+      if (c.terminate_when_dof_far) glob[PBHC_G_DOF_FAR_HIT] = 0.0;
       glob[PBHC_G_STEP_COUNTER] += 1.0;
       frame_cursor[0] = (frame_cursor[0] + 1) % num_frames;
     }
@@ -126,6 +127,10 @@ __global__ __launch_bounds__(64 * PBHC_FIN_CHUNKS) void k_env_finalize(const Pbh
     L[PBHC_L_TERM_CONTACT] = (tot[P_TERM_CONTACT] / N) / (rfrac + 1e-15); L[PBHC_L_TERM_LOW_HEIGHT] = (tot[P_TERM_LOWH] / N) / (rfrac + 1e-15);
     L[PBHC_L_TERM_DOF_POS_LIMIT] = (tot[P_TERM_POSLIM] / N) / (rfrac + 1e-15); L[PBHC_L_TERM_DOF_VEL_LIMIT] = (tot[P_TERM_VELLIM] / N) / (rfrac + 1e-15);
     L[PBHC_L_TERM_TORQUE_LIMIT] = (tot[P_TERM_TAULIM] / N) / (rfrac + 1e-15);
+    if (c.terminate_when_dof_far) {     // motion_tracking.py:346: a scalar flag, its env-mean is the flag itself; cleared for the next pre-pass
+      L[PBHC_L_TERM_DOF_FAR] = glob[PBHC_G_DOF_FAR_HIT] / (rfrac + 1e-15);
+      glob[PBHC_G_DOF_FAR_HIT] = 0.0;
+    }
     if (c.tracking_mode) {
       L[PBHC_L_TERM_REF_POS_Z] = (tot[P_TERM_REFZ] / N) / (rfrac + 1e-15); L[PBHC_L_TERM_REF_ORI] = (tot[P_TERM_REFORI] / N) / (rfrac + 1e-15);
       L[PBHC_L_TERM_BODY_Z] = (tot[P_TERM_BODYZ] / N) / (rfrac + 1e-15);
@@ -136,7 +141,10 @@ __global__ __launch_bounds__(64 * PBHC_FIN_CHUNKS) void k_env_finalize(const Pbh
       L[PBHC_L_LOCAL_LOWER_BODY_DIFF_NORM] = tot[P_LLO_NORM] / N; L[PBHC_L_LOCAL_VR_3POINT_DIFF_NORM] = tot[P_LVR_NORM] / N;
       L[PBHC_L_LOCAL_KEY_BODY_DIFF_NORM] = tot[P_LKEY_NORM] / N;
     }
-  } else if (tid == 256 && nreset > 0.0) {
+  } else if (tid == 256) {
+    // the threshold this step's termination test used (logged by _update_reset_buf before the curriculum below moves it)
+    if (c.terminate_when_dof_far) L[PBHC_L_DOF_FAR_THR] = glob[PBHC_G_DOF_FAR_THR];
+    if (nreset > 0.0) {
     // _update_average_episode_length (legged_robot_base.py:875-879), fp32 like the reference's 0-dim tensor
     float cur = (float)(tot[P_RESET_EPLEN] / nreset);
     double frac = nreset / (double)c.num_compute_average_epl;
@@ -172,12 +180,61 @@ __global__ __launch_bounds__(64 * PBHC_FIN_CHUNKS) void k_env_finalize(const Pbh
       else if (avg > c.motion_far_up) t *= (1.0 - (double)c.motion_far_degree);
       glob[PBHC_G_MOTION_FAR_THR] = fmin(fmax(t, (double)c.motion_far_min), (double)c.motion_far_max);
     }
+    if (c.terminate_when_dof_far && c.dof_far_curriculum) {         // motion_tracking.py:283-292, the same call site
+      double t = glob[PBHC_G_DOF_FAR_THR];
+      if (avg < c.dof_far_down) t *= (1.0 + (double)c.dof_far_degree);
+      else if (avg > c.dof_far_up) t *= (1.0 - (double)c.dof_far_degree);
+      glob[PBHC_G_DOF_FAR_THR] = fmin(fmax(t, (double)c.dof_far_min), (double)c.dof_far_max);
+    }
+    }
   } else if (tid == 320 && nreset > 0.0) {
     double mean = tot[P_ETR_SUM] / N;
     L[PBHC_L_END_TIME_RATIO] = mean;
     double var = (tot[P_ETR_SQ] - N * mean * mean) / (N - 1.0);
     L[PBHC_L_END_TIME_RATIO_STD] = var > 0.0 ? sqrt(var) : 0.0;
   }
+}
+
+// =================================================================================================
+//  k_dof_far_any: the batch-global decision of termination.terminate_when_dof_far (motion_tracking.py:343-349,
+//  torch.any(norm(dif_joint_angles, dim=-1) > threshold) over the ENV axis: one env past the threshold resets every env of the step).
+//  A pre-pass on the step's stream right before k_env_step, launched only when the switch is on: k_env_step's workgroups are not
+//  co-resident at large env counts, so the decision cannot be exchanged inside it (a grid barrier there would deadlock).  Per env it
+//  evaluates |ref dof_pos - dof_pos| exactly as k_env_step's role B does — the replay frame the step will read, the reference at the
+//  step's pre-reset time (ep_len + 2) dt + start with frame_blend and the same lerp, the same 32-lane reduction — so that the decision
+//  agrees bit for bit with the norm the step logs.  One device-scope atomic per workgroup sets PBHC_G_DOF_FAR_HIT; k_env_step reads it
+//  once, k_env_finalize clears it (stream order: finalize of step t precedes the pre-pass of step t + 1, in a captured graph too).
+// =================================================================================================
+#define DOF_FAR_EPB 8                                             // envs per 256-thread workgroup: 32 lanes per env
+__global__ __launch_bounds__(PBHC_G * DOF_FAR_EPB) void k_dof_far_any(const long long* __restrict__ ep_len, const float* __restrict__ start,
+                                                                       const float* __restrict__ frame_q, const int32_t* __restrict__ cursor,
+                                                                       int frame_index, int num_frames, int N, int D, float dt, PbhcMotionTable tbl,
+                                                                       const int64_t* __restrict__ motion_ids, double* __restrict__ glob) {
+  const int lane = threadIdx.x & (PBHC_G - 1);
+  const int env = blockIdx.x * DOF_FAR_EPB + (int)(threadIdx.x / PBHC_G);
+  const bool valid = env < N;
+  const int envc = valid ? env : N - 1;
+  const int dc = min(lane, D - 1);
+  const size_t fk = (size_t)(frame_index >= 0 ? frame_index : cursor[0] % num_frames) * (size_t)N;
+  const int mid = (int)motion_ids[envc];
+  float m_len = tbl.single_len, m_dt = tbl.single_dt;
+  int m_nf = tbl.single_num_frames, m_row0 = 0;
+  if (tbl.num_motions != 1) { m_len = tbl.motion_len[mid]; m_nf = tbl.num_frames[mid]; m_dt = tbl.motion_dt[mid]; m_row0 = tbl.length_starts[mid]; }
+  const long long ep1 = ep_len[envc] + 1;
+  const float tref = (float)(ep1 + 1) * dt + start[envc];
+  int f0, f1;
+  float blend;
+  frame_blend(tref, m_len, m_nf, m_dt, &f0, &f1, &blend);
+  const float rd0 = tbl.frames[(size_t)(m_row0 + f0) * tbl.row + dc], rd1 = tbl.frames[(size_t)(m_row0 + f1) * tbl.row + dc];
+  const float q = frame_q[fk * D + (size_t)envc * D + dc];
+  const float a = 1.0f - blend;
+  const float dj = (a * rd0 + blend * rd1) - q;
+  float s = 0.0f;
+  if (lane < D) s += dj * dj;
+  s = group_sum(s);
+  const bool far = valid && sqrtf(s) > (float)glob[PBHC_G_DOF_FAR_THR];
+  if (__syncthreads_or(far) && threadIdx.x == 0)
+    __hip_atomic_store(glob + PBHC_G_DOF_FAR_HIT, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // =================================================================================================
@@ -907,6 +964,9 @@ int pbhc_env_step_launch(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
   int a_fi = io->frame_index, a_n = e->cfg.num_envs;
   void* args[] = {(void*)&a_ep, (void*)&a_st, (void*)&a_fr, (void*)&a_fq, (void*)&a_fqd, (void*)&a_cur, (void*)&a_fi, (void*)&a_n, (void*)&a_cfg, (void*)&e->tbl, (void*)&a_io, (void*)&a_glob, (void*)&e->d_partials, (void*)&a_stride, (void*)&a_skc, (void*)&a_map, (void*)&a_skj};
   const void* fn = e->spec_fn ? e->spec_fn : (e->cfg.tracking_mode ? (const void*)k_env_step<1> : (const void*)k_env_step<0>);
+  if (e->cfg.terminate_when_dof_far)          // the batch-global dof-far decision, ahead of the step's reset path (k_dof_far_any)
+    hipLaunchKernelGGL(k_dof_far_any, dim3((a_n + DOF_FAR_EPB - 1) / DOF_FAR_EPB), dim3(PBHC_G * DOF_FAR_EPB), 0, st, a_ep, a_st, a_fq, a_cur, a_fi,
+                       io->num_frames, a_n, e->cfg.skel.num_dof, e->cfg.dt, e->tbl, (const int64_t*)io->motion_ids, e->d_glob);
   if (e->profile) HIP_CHECK(hipExtLaunchKernel(fn, dim3(e->nblocks), dim3(PBHC_TPB), args, a_lds, st, pe0, pe1, 0));
   else HIP_CHECK(hipLaunchKernel(fn, dim3(e->nblocks), dim3(PBHC_TPB), args, a_lds, st));
   if (e->profile) e->prof_count++;

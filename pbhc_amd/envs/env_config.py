@@ -207,14 +207,27 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     L.feet, L.penalised, L.upper, L.lower, L.track, L.key = feet, pen, upper, lower, track, key_ids
     # ---- termination
     T = ec.termination
-    if T.get("terminate_when_dof_far", False):
-        # motion_tracking.py:345 reduces torch.any(norm(dif_joint_angles) > threshold) over the ENV axis: one env past the threshold resets all
-        # of them — a batch-global decision inside a step (a grid-wide exchange before the reset path; a collective per step under data parallelism)
-        raise NotImplementedError("termination.terminate_when_dof_far")
-    if float(ec.get("noise_to_initial_level", 0) or 0) != 0.0:
-        # motion_tracking.py:481-484,538-539 / general_tracking.py:413-416,478-479: normal noise on the state an env is reset to (and on the
-        # observations of that step); 0 in every shipped yaml.  The in-kernel reset path writes the reference state as it is.
-        raise NotImplementedError("noise_to_initial_level != 0 (noise on the reset state)")
+    tc = ec.termination_curriculum
+    dof_far_thr = 0.0
+    if mode == 0 and T.get("terminate_when_dof_far", False):
+        # motion_tracking.py:343-349 reduces torch.any(norm(dif_joint_angles) > threshold) over the ENV axis: one env past the threshold resets
+        # all of them.  The decision is the pre-pass k_dof_far_any; general tracking never reads the switch (accepted and ignored, as there).
+        dcur = tc.terminate_when_dof_far_curriculum
+        c.terminate_when_dof_far = 1
+        dof_far_thr = float(dcur.init)                                # :128-130, whether or not the curriculum is enabled
+        c.dof_far_curriculum = int(bool(dcur.get("enable", False)))
+        if c.dof_far_curriculum:                                      # :283-292
+            c.dof_far_degree, c.dof_far_down, c.dof_far_up = float(dcur.degree), float(dcur.level_down_threshold), float(dcur.level_up_threshold)
+            c.dof_far_min, c.dof_far_max = float(dcur.min), float(dcur.max)
+    level = float(ec.get("noise_to_initial_level", 0) or 0)
+    if level != 0.0:
+        # motion_tracking.py:470-545 / general_tracking.py:405-485 (custom_origins False: the plane-terrain branch every fixture runs): noise on
+        # the state an env is reset to, scale x level as the reference multiplies its python floats (the rotation's max angle with its 3.14 / 180)
+        ns = ec.init_noise_scale
+        c.reset_noise = 1
+        c.rn_root_pos, c.rn_root_vel, c.rn_root_ang_vel = (float(ns.root_pos * level), float(ns.root_vel * level), float(ns.root_ang_vel * level))
+        c.rn_root_rot = float(ns.root_rot * 3.14 / 180 * level)
+        c.rn_dof_pos, c.rn_dof_vel = float(ns.dof_pos * level), float(ns.dof_vel * level)
     if ec.get("use_teleop_control", False):
         raise NotImplementedError("use_teleop_control (a ROS subscriber feeding marker coordinates, motion_tracking.py:112-118)")
     sdc = ec.get("soft_dynamic_correction", None)
@@ -271,7 +284,6 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
             pass                                                              # read by nobody in the reference either
     elif any(T.get(k, False) for k in ("terminate_by_ref_pos_z", "terminate_by_ref_ori", "terminate_by_body_z")):
         raise NotImplementedError("general-tracking terminations need env._target_ ...general_tracking.LeggedRobotGeneralTracking")
-    tc = ec.termination_curriculum
     c.motion_far_curriculum = int(bool(tc.terminate_when_motion_far_curriculum))
     c.motion_far_degree = float(tc.terminate_when_motion_far_curriculum_degree)
     c.motion_far_down = float(tc.terminate_when_motion_far_curriculum_level_down_threshold)
@@ -656,6 +668,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     g[K["PBHC_G_AVG_EP_LEN"]] = 0.0
     g[K["PBHC_G_MOTION_FAR_THR"]] = float(tc.terminate_when_motion_far_initial_threshold if (T.terminate_when_motion_far and tc.terminate_when_motion_far_curriculum)
                                            else ec.termination_scales.termination_motion_far_threshold)
+    g[K["PBHC_G_DOF_FAR_THR"]] = dof_far_thr
     g[K["PBHC_G_SOFT_POS_VAL"]] = float(lc.soft_dof_pos_initial_limit)
     g[K["PBHC_G_SOFT_VEL_VAL"]] = float(lc.soft_dof_vel_initial_limit)
     g[K["PBHC_G_SOFT_TAU_VAL"]] = float(lc.soft_torque_initial_limit)

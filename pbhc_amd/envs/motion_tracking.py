@@ -428,10 +428,13 @@ class LeggedRobotMotionTracking:
             self._io.obs_pitch[i] = t.stride(0)
 
     # ---- test / replay hooks: inject the random draws instead of the in-kernel Philox ---------
-    def set_injected_draws(self, u_rfi=None, start_time=None, kp=None, kd=None, rfi_lim=None, rao=None, delay=None, dof_pos_bias=None, gate_u=None):
-        """Keeps the tensors alive and points the kernel at them (None -> in-kernel RNG)."""
+    def set_injected_draws(self, u_rfi=None, start_time=None, kp=None, kd=None, rfi_lim=None, rao=None, delay=None, dof_pos_bias=None, gate_u=None,
+                           reset_root=None, reset_dof_pos=None, reset_dof_vel=None):
+        """Keeps the tensors alive and points the kernel at them (None -> in-kernel RNG).  reset_root [N,13] / reset_dof_pos, reset_dof_vel [N,D]:
+        the raw draws of the reset-state noise (PbhcStepIO.ovr_reset_*), consumed by the envs that reset."""
         self._overrides = dict(u_rfi=u_rfi, ovr_start_time=start_time, ovr_kp=kp, ovr_kd=kd, ovr_rfi_lim=rfi_lim, ovr_rao=rao, ovr_delay=delay,
-                               ovr_dof_pos_bias=dof_pos_bias, ovr_gate_u=gate_u)
+                               ovr_dof_pos_bias=dof_pos_bias, ovr_gate_u=gate_u, ovr_reset_root=reset_root, ovr_reset_dof_pos=reset_dof_pos,
+                               ovr_reset_dof_vel=reset_dof_vel)
         self._io_epoch += 1
         for k, v in self._overrides.items():
             setattr(self._io, k, None if v is None else v.data_ptr())
@@ -449,6 +452,11 @@ class LeggedRobotMotionTracking:
                  latency-critical collectives per iteration."""
         if not pdist.active(group):
             return False
+        if self._c.terminate_when_dof_far:
+            # one env past the threshold resets every env (motion_tracking.py:343-349): across ranks that is a collective before every step's
+            # reset path — on the step -> policy -> step chain — and each rank deciding alone would not be the reference's batch
+            raise NotImplementedError("termination.terminate_when_dof_far under data parallelism: the batch-global decision would need a "
+                                      "cross-rank collective every step")
         assert mode in ("rollout", "step"), mode
         self._flush_statistics()
         self._stat_group, self._stat_mode = group, mode
@@ -589,6 +597,10 @@ class LeggedRobotMotionTracking:
             t = float(g[K["PBHC_G_MOTION_FAR_THR"]])
             t *= (1 + c.motion_far_degree) if avg_f < c.motion_far_down else ((1 - c.motion_far_degree) if avg_f > c.motion_far_up else 1.0)
             g[K["PBHC_G_MOTION_FAR_THR"]] = float(np.clip(t, c.motion_far_min, c.motion_far_max))
+        if c.terminate_when_dof_far and c.dof_far_curriculum:                    # motion_tracking.py:283-292, the same call site
+            t = float(g[K["PBHC_G_DOF_FAR_THR"]])
+            t *= (1 + c.dof_far_degree) if avg_f < c.dof_far_down else ((1 - c.dof_far_degree) if avg_f > c.dof_far_up else 1.0)
+            g[K["PBHC_G_DOF_FAR_THR"]] = float(np.clip(t, c.dof_far_min, c.dof_far_max))
         # _reset_dofs / _reset_root_states from the reference frame at (0+1)*dt + start
         ref = self._motion_lib.get_motion_state(self.motion_ids, (self._episode_length_buf + 1) * self.dt + self.motion_start_times, offset=self.env_origins)
         s = self.simulator
@@ -597,10 +609,30 @@ class LeggedRobotMotionTracking:
         s.dof_pos.copy_(ref_dof["dof_pos"]); s.dof_vel.copy_(ref_dof["dof_vel"])
         s.robot_root_states[:, 0:3] = ref["root_pos"]; s.robot_root_states[:, 3:7] = ref["root_rot"]
         s.robot_root_states[:, 7:10] = ref["root_vel"]; s.robot_root_states[:, 10:13] = ref["root_ang_vel"]
+        if c.reset_noise:
+            self._reset_state_noise()
         self.extras["episode"] = {"rew_" + k: (v / self.max_episode_length_s).clone() for k, v in self.episode_sums.items()}
         self.extras["episode"]["end_epis_length"] = self.last_episode_length_buf.clone()
         self._episode_sums.zero_()
         self.extras["time_outs"] = self.time_out_buf
+
+    def _reset_state_noise(self):
+        """noise_to_initial_level != 0: _reset_dofs / _reset_root_states of every env (motion_tracking.py:470-545, general_tracking.py:405-485)
+        on the state just written, with the env's generator (the kernel's per-env resets draw from Philox streams of their own)."""
+        N, D, dev, c, s = self.num_envs, self.num_dof, self.device, self._c, self.simulator
+        gen = self._gen
+        draw = torch.randn if self.TRACKING_MODE == 0 else torch.rand            # general tracking: rand_like on the dofs, sic
+        s.dof_pos.add_(draw(N, D, device=dev, generator=gen) * c.rn_dof_pos)
+        s.dof_vel.add_(draw(N, D, device=dev, generator=gen) * c.rn_dof_vel)
+        rs = s.robot_root_states
+        rs[:, 0:3] += torch.randn(N, 3, device=dev, generator=gen) * c.rn_root_pos
+        axis = torch.randn(N, 3, device=dev, generator=gen)
+        axis = axis / torch.norm(axis, dim=1, keepdim=True)
+        half = c.rn_root_rot * torch.rand(N, 1, device=dev, generator=gen) / 2
+        small = torch.cat([torch.sin(half) * axis, torch.cos(half)], dim=1)        # small_random_quaternions (xyzw)
+        rs[:, 3:7] = _quat_mul_xyzw(small, rs[:, 3:7].clone())
+        rs[:, 7:10] += torch.randn(N, 3, device=dev, generator=gen) * c.rn_root_vel
+        rs[:, 10:13] += torch.randn(N, 3, device=dev, generator=gen) * c.rn_root_ang_vel
 
     def _episodic_domain_randomization_all(self):
         """_episodic_domain_randomization(arange(N)) (legged_robot_base.py:599-635): kp / kd / rfi-limit / rao scales, control delay."""
@@ -714,11 +746,28 @@ class LeggedRobotMotionTracking:
                                 (self._c.terminate_close_tau, "PBHC_L_TERM_TORQUE_LIMIT", "torque_limit")):
             if flag:
                 out["terminate_by_" + name] = g[L0 + K[key]]
+        if self._c.terminate_when_dof_far:                # motion_tracking.py:346-349 (the threshold: when its curriculum is enabled)
+            out["terminate_by_dof_far"] = g[L0 + K["PBHC_L_TERM_DOF_FAR"]]
+            if self._c.dof_far_curriculum:
+                out["terminate_when_dof_far_threshold"] = g[L0 + K["PBHC_L_DOF_FAR_THR"]]
         for i, k in enumerate(env_config.SIGMA_KEYS):
             out["adp_sigma_" + k] = g[K["PBHC_G_SIGMA"] + i]
             out["error_ema_" + k] = g[K["PBHC_G_EMA"] + i]
         self.log_dict.update({k: torch.tensor(float(v)) for k, v in out.items()})
         return out
+
+
+def _quat_mul_xyzw(a, b):
+    """Hamilton product of [N,4] xyzw quaternions: the 9-multiplication form of csrc/pbhc_math.h quat_mul (the kernel's reset path)"""
+    ax, ay, az, aw = a.unbind(-1)
+    bx, by, bz, bw = b.unbind(-1)
+    ww = (az + ax) * (bx + by)
+    yy = (aw - ay) * (bw + bz)
+    zz = (aw + ay) * (bw - bz)
+    xx = ww + yy + zz
+    qq = 0.5 * (xx + (az - ax) * (bx - by))
+    return torch.stack([qq - xx + (ax + aw) * (bx + bw), qq - yy + (aw - ax) * (by + bz), qq - zz + (az + ay) * (bw - bx),
+                        qq - ww + (az - ay) * (by - bz)], dim=-1)
 
 
 def _padded_rows(n, dim, device, dtype=torch.float32):

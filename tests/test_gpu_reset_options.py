@@ -1,0 +1,223 @@
+"""termination.terminate_when_dof_far (batch-global: the pre-pass k_dof_far_any ahead of k_env_step) and noise_to_initial_level (noise on
+the reset state, in the kernel's reset path) on the GPU: the reference's own traces with injected draws, full-size decisions, the in-kernel
+distributions, and the rollout graph."""
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import GOLDEN, build_hip_env, load_state_into_hip_env, state_dict_from_golden
+from tests.test_gpu_parity import angvel_tol, close, trace_slerp_bounds
+
+pytestmark = pytest.mark.gpu
+
+TC = "env.config.termination_curriculum.terminate_when_dof_far_curriculum."
+DOF_FAR = {"env.config.termination.terminate_when_dof_far": True, TC + "enable": True, TC + "init": 2.0, TC + "degree": 0.05, TC + "min": 1.0,
+           TC + "max": 2.5, TC + "level_down_threshold": 40, TC + "level_up_threshold": 42}
+NOISE = {"env.config.noise_to_initial_level": 1.0}
+WALK, STUDENT = "v1_g1_23dof_walk.yaml", "v2_g1_23dof_student.yaml"
+
+
+def _K():
+    from pbhc_amd import _lib
+
+    return _lib.K
+
+
+def _trace(tag, cfgname, overrides, general):
+    g = dict(np.load(f"{GOLDEN}/{tag}.npz"))
+    T, N, D = g["actions_in"].shape
+    cfg, env = build_hip_env(cfgname, N, general=general, overrides=dict({"domain_rand.push_robots": False}, **overrides))
+    assert env.reward_names == list(g["reward_names"])
+    load_state_into_hip_env(env, state_dict_from_golden(g), g)
+    if "step__log__terminate_when_dof_far_threshold" in g:              # the threshold the trace starts from (reset_all moved it once)
+        env.globals[_K()["PBHC_G_DOF_FAR_THR"]] = float(g["step__log__terminate_when_dof_far_threshold"][0])
+    tg = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(env.device)
+    env.simulator.set_replay(tg(g["replay_root"]), tg(g["replay_dof_pos"]), tg(g["replay_dof_vel"]), tg(g["replay_contact"]))
+    from oracle.motion_lib import MotionLib as OML
+    from tests.helpers import clip_from_env_golden, skel_from_golden
+
+    oml = OML(skel_from_golden(), [clip_from_env_golden(g)]) if not general else None
+    noisy_resets = 0
+    for k in range(T):
+        st = lambda name, dt=torch.float32: tg(g["step__state__" + name][k]).to(dt)
+        env.set_injected_draws(u_rfi=tg(g["step__u_rfi"][k]), start_time=st("motion_start_times"), kp=st("kp_scale"), kd=st("kd_scale"),
+                               rfi_lim=st("rfi_lim_scale"), rao=st("rao_scale"), delay=st("action_delay_idx", torch.long),
+                               reset_root=tg(g["step__reset_root"][k]), reset_dof_pos=tg(g["step__reset_dof_pos"][k]), reset_dof_vel=tg(g["step__reset_dof_vel"][k]))
+        obs, rew, reset, extras = env.step({"actions": tg(g["actions_in"][k])})
+        torch.cuda.synchronize()
+        w = f"{tag} step {k}: "
+        rs = torch.from_numpy(g["step__reset_buf_out"][k]).bool()
+        noisy_resets += int((rs & (torch.from_numpy(g["step__reset_root"][k]).abs().sum(1) > 0)).sum())
+        assert torch.equal(reset.cpu(), torch.from_numpy(g["step__reset_buf_out"][k])), w + "reset_buf"
+        assert torch.equal(extras["time_outs"].cpu(), torch.from_numpy(g["step__time_outs"][k])), w + "time_outs"
+        close(rew, g["step__rew_buf"][k], 3e-5, w + "rew_buf", rtol=2e-4)
+        for ok in obs:
+            if general:         # (slerp-conditioned elements of the v2 rows: the bound tests/test_gpu_parity_v2.py derives per element)
+                close(obs[ok], g["step__obs__" + ok][k], 3e-5, w + ok, hard=2e-3, frac=0.02)
+            else:
+                close(obs[ok], g["step__obs__" + ok][k], 3e-5, w + ok)
+        close(env.simulator.dof_pos, g["step__state__dof_pos"][k], 3e-5, w + "dof_pos")
+        close(env.simulator.dof_vel, g["step__state__dof_vel"][k], 3e-5, w + "dof_vel", rtol=1e-4)
+        for name in ["actions", "last_actions", "motion_start_times", "motion_len", "last_dof_vel"]:
+            close(getattr(env, name), g["step__state__" + name][k], 3e-5, w + "state " + name)
+        gs = lambda name, j: torch.from_numpy(g["state0__" + name] if j < 0 else g["step__state__" + name][j])
+        rs_tol = torch.full((N, 10), 3e-5)
+        if oml is not None:
+            _, root_tol = trace_slerp_bounds(oml, gs("episode_length_buf", k - 1), gs("motion_start_times", k - 1), gs("episode_length_buf", k),
+                                             gs("motion_start_times", k), rs, float(env.dt), 2e-5)
+            rs_tol[:, 3:7] = (root_tol + 1e-5).expand(-1, 4)
+        else:
+            rs_tol[:, 3:7] = 2e-4
+        close(env.simulator.robot_root_states[:, :10], g["step__state__root_states"][k][:, :10], rs_tol, w + "root_states", rtol=3e-5)
+        ref_w = torch.from_numpy(g["step__state__root_states"][k][:, 10:])
+        close(env.simulator.robot_root_states[:, 10:], ref_w, angvel_tol(ref_w, float(env._motion_lib._motion_dt[0]), k=32.0, base=3e-5), w + "root ang vel", rtol=3e-5)
+        assert torch.equal(env.episode_length_buf.cpu(), torch.from_numpy(g["step__state__episode_length_buf"][k]))
+        log = env.read_log()
+        for lk in ("terminate_by_dof_far", "terminate_when_dof_far_threshold", "terminate_by_time_out"):
+            if "step__log__" + lk in g:
+                close(torch.tensor(log[lk]), g["step__log__" + lk][k], 1e-4, w + "log " + lk, rtol=1e-6)
+    assert noisy_resets > 0, f"{tag}: the trace holds no reset with noise"
+    return g
+
+
+def test_v1_trace_dof_far_and_reset_noise():
+    """the walk trace with dof-far (+ curriculum) and reset noise on: fired on exactly one step, every env reset there, noisy resets"""
+    g = _trace("env_v1_walk_doffar", WALK, dict(DOF_FAR, **NOISE), general=False)
+    fired = g["step__log__terminate_by_dof_far"] > 0
+    assert fired.any() and not fired.all()
+    assert g["step__reset_buf_out"][fired].all()
+
+
+def test_v2_trace_reset_noise():
+    """student23 with reset noise (general tracking: the dof offsets are rand_like, U[0,1) x scale)"""
+    g = _trace("env_v2_student23_resetnoise", STUDENT, NOISE, general=True)
+    assert (g["step__reset_dof_pos"] >= 0).all() and g["step__reset_dof_pos"].max() > 0
+
+
+def _full(cfgname, overrides, general=False, seed=3):
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    cfg, env = build_hip_env(cfgname, 4096, general=general, overrides=overrides)
+    env.reset_all()
+    return env
+
+
+def _replay(env, seed=5, T=3):
+    import bench
+
+    return [t.contiguous() for t in bench.make_replay_on_device(env, T, seed=seed)]
+
+
+def _outputs(env, obs, rew, reset):
+    out = {"obs__" + k: v.clone() for k, v in obs.items()}
+    out.update(rew=rew.clone(), reset=reset.clone(), time_outs=env.time_out_buf.clone(), root=env.simulator.robot_root_states.clone(),
+               dof_pos=env.simulator.dof_pos.clone(), dof_vel=env.simulator.dof_vel.clone(), kp=env._kp_scale.clone(),
+               start=env.motion_start_times.clone(), hist=env._hist.clone(), ep=env.episode_length_buf.clone(), sums=env._episode_sums.clone())
+    return out
+
+
+@pytest.mark.parametrize("which", ["first", "last", "middle"])
+def test_one_env_past_the_threshold_resets_every_env_4096(which):
+    env = _full(WALK, DOF_FAR)
+    N = env.num_envs
+    i = {"first": 0, "last": N - 1, "middle": 1733}[which]
+    root, qp, qv, cf = _replay(env)
+    qp[0, i, 3] += 5.0                                     # one knee far off its reference in the frame the next step reads
+    env.simulator.set_replay(root, qp, qv, cf)
+    obs, rew, reset, extras = env.step({"actions": torch.zeros(N, env.num_dof, device=env.device)})
+    torch.cuda.synchronize()
+    assert bool(reset.bool().all()), int(reset.sum())
+    log = env.read_log()
+    assert abs(log["terminate_by_dof_far"] - 1.0) < 1e-12
+    assert float(env.globals[_K()["PBHC_G_DOF_FAR_HIT"]]) == 0.0          # cleared by the finalize for the next step
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_switch_on_without_a_far_env_is_bit_identical_to_switch_off(general):
+    cfgname = STUDENT if general else WALK
+    outs = []
+    rep = None
+    for ov in ({}, {"env.config.termination.terminate_when_dof_far": True} if general else DOF_FAR):
+        env = _full(cfgname, ov, general=general)
+        if rep is None:
+            rep = _replay(env)
+        env.simulator.set_replay(*[t.clone() for t in rep])
+        o = [_outputs(env, *env.step({"actions": torch.zeros(env.num_envs, env.num_dof, device=env.device)})[:3])]
+        torch.cuda.synchronize()
+        if ov and not general:
+            assert env.read_log()["terminate_by_dof_far"] == 0.0
+        outs.append(o)
+    for a, b in zip(*outs):
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
+
+
+def _reset_everything(general, noise):
+    """one step in which every env times out (the kernel's reset path for all 4096), noise on or off, same seeds"""
+    env = _full(STUDENT if general else WALK, NOISE if noise else {}, general=general)
+    env.simulator.set_replay(*_replay(env))
+    env._episode_length_buf.fill_(int(env.max_episode_length) + 1)
+    env.step({"actions": torch.zeros(env.num_envs, env.num_dof, device=env.device)})
+    torch.cuda.synchronize()
+    assert bool(env.reset_buf.bool().all())
+    return env
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_in_kernel_reset_noise_distributions_4096(general):
+    on, off = _reset_everything(general, True), _reset_everything(general, False)
+    c, N, D = on._c, on.num_envs, on.num_dof
+    # every other draw of the reset is the same with the noise on or off (Philox streams of their own)
+    for name in ("motion_start_times", "_kp_scale", "_kd_scale", "_rfi_lim_scale", "_rao_scale", "action_delay_idx"):
+        assert torch.equal(getattr(on, name), getattr(off, name)), name
+    dq = (on.simulator.dof_pos - off.simulator.dof_pos).double().cpu()
+    dv = (on.simulator.dof_vel - off.simulator.dof_vel).double().cpu()
+    for d, s in ((dq, c.rn_dof_pos), (dv, c.rn_dof_vel)):
+        z = d / s
+        n = z.numel()
+        if general:                                          # U[0, 1): mean 1/2, variance 1/12, one-sided
+            assert float(z.min()) >= -1e-4 and float(z.max()) < 1.0 + 1e-4
+            assert abs(float(z.mean()) - 0.5) < 5 * (1 / 12) ** 0.5 / n ** 0.5
+            assert abs(float(z.var()) - 1 / 12) < 0.01
+        else:                                                # N(0, 1) per component
+            assert abs(float(z.mean())) < 5 / n ** 0.5
+            assert abs(float(z.std()) - 1.0) < 0.02
+            for j in (0, 7, D - 1):
+                assert abs(float(z[:, j].std()) - 1.0) < 0.1 and abs(float(z[:, j].mean())) < 0.1
+    ra, rb = on.simulator.robot_root_states.double().cpu(), off.simulator.robot_root_states.double().cpu()
+    for sl, s in ((slice(0, 3), c.rn_root_pos), (slice(7, 10), c.rn_root_vel), (slice(10, 13), c.rn_root_ang_vel)):
+        z = (ra[:, sl] - rb[:, sl]) / s
+        assert abs(float(z.mean())) < 5 / z.numel() ** 0.5 and abs(float(z.std()) - 1.0) < 0.05, sl
+    # the small rotation: small = q_on (x) conj(q_off); its angle <= max, its axis isotropic
+    from oracle import rotations as R
+
+    qa, qb = ra[:, 3:7], rb[:, 3:7]
+    qa, qb = qa / qa.norm(dim=1, keepdim=True), qb / qb.norm(dim=1, keepdim=True)     # (a slerped reference rotation is unit only to ~1e-4)
+    qb_conj = torch.cat([-qb[:, :3], qb[:, 3:]], 1)
+    small = R.quat_mul(qa, qb_conj)
+    small = small * torch.sign(small[:, 3:4])
+    ang = 2 * torch.acos(small[:, 3].clamp(max=1.0))
+    assert float(ang.max()) <= c.rn_root_rot + 1e-4 and float(ang.mean()) > 0.4 * c.rn_root_rot
+    axis = small[:, :3] / small[:, :3].norm(dim=1, keepdim=True)
+    assert float(axis.mean(0).abs().max()) < 0.05
+    assert float(((axis ** 2).mean(0) - 1 / 3).abs().max()) < 0.03
+
+
+@pytest.mark.parametrize("agent", ["v1", "v2"])
+def test_graph_rollout_with_both_switches_equals_the_eager_loop(agent, monkeypatch):
+    """the rollout hipGraph (pre-pass, step, reduction on the branch stream) against the step-by-step loop, both switches on"""
+    import tests.test_gpu_parity as P
+
+    ov = dict(DOF_FAR, **{TC + "init": 1.0}, **NOISE) if agent == "v1" else dict({"env.config.termination.terminate_when_dof_far": True}, **NOISE)
+    orig = P.build_hip_env
+    monkeypatch.setattr(P, "build_hip_env", lambda *a, **k: orig(*a, **dict(k, overrides=dict(k.get("overrides") or {}, **ov))))
+    import tests.test_gpu_parity_v2 as P2
+
+    monkeypatch.setattr(P2, "build_hip_env", lambda *a, **k: orig(*a, **dict(k, overrides=dict(k.get("overrides") or {}, **ov))))
+    a = P._rollouts_with_split(True, agent, batched=True, fused_sample=True, rollout_graph=True, rollouts=4)
+    b = P._rollouts_with_split(True, agent, batched=True, fused_sample=True, rollout_graph=False, rollouts=4)
+    a.pop("_time_outs_seen"); b.pop("_time_outs_seen")
+    assert bool(a.pop("_used_graph")) and not bool(b.pop("_used_graph"))
+    a.pop("_used_graph_each"); b.pop("_used_graph_each")
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
