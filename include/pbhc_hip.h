@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define PBHC_ABI_VERSION 12
+#define PBHC_ABI_VERSION 13
 
 #define PBHC_OK 0
 #define PBHC_EINVAL (-22)   /* bad argument / size over a compile-time maximum */
@@ -128,6 +128,10 @@ enum PbhcFeature {
   PBHC_F_ROLL_PITCH, PBHC_F_CONTACT_MASK, PBHC_F_DR_BASE_MASS, PBHC_F_LOCAL_BODY_POS, PBHC_F_LOCAL_BODY_ROT, PBHC_F_ANCHOR_REF_POS,
   PBHC_F_ANCHOR_REF_ROT, PBHC_F_DIF_ROOT_VELOCITY, PBHC_F_DIF_ROOT_ROT, PBHC_F_DIF_ROOT_HEIGHT, PBHC_F_REF_CONTACT_MASK,
   PBHC_F_FUT_ROOT_HEIGHT, PBHC_F_FUT_ROLL_PITCH, PBHC_F_FUT_BASE_LIN_VEL, PBHC_F_FUT_BASE_ANG_VEL, PBHC_F_FUT_DOF_POS, PBHC_F_FUT_LOCAL_KEY_POS,
+  /* obs.noise_process (legged_robot_base.py:356-372): base_ang_vel_noise / projected_gravity_noise, the two root-frame quantities of
+   * PBHC_F_BASE_ANG_VEL / PBHC_F_PROJECTED_GRAVITY rotated by the Ornstein-Uhlenbeck-perturbed base orientation.  (Appended, so that every
+   * other id keeps its value; with the process off the two names read the clean slots instead.) */
+  PBHC_F_BASE_ANG_VEL_NOISE, PBHC_F_PROJECTED_GRAVITY_NOISE,
   PBHC_F_NUM
 };
 
@@ -321,6 +325,23 @@ typedef struct PbhcEnvConfig {
    * dof position / velocity + N(0,1) x scale (tracking_mode 1: + U[0,1) x scale, as the reference's rand_like).  reset_noise = 0: no draws */
   int32_t reset_noise;
   float rn_root_pos, rn_root_rot, rn_root_vel, rn_root_ang_vel, rn_dof_pos, rn_dof_vel;
+  /* obs.noise_process, type ou (utils/noise_tool.py OUProcess; legged_robot_base.py:122-129,356-372,593-597): a per-env state x [6]
+   * (PbhcStepIO.ou_state) stepped once per control step before termination, x += theta (mu - x) dt + sigma sqrt(dt) N(0,1), and re-drawn
+   * from its stationary law mu + sigma / sqrt(2 theta) N(0,1) for the envs that reset (after the step's features: the redraw first shows in
+   * the next step).  x[0:3] x ou_scale_rpy x pi / 180 perturb the base's euler angles, x[3:6] x ou_scale_ang_vel the
+   * world-frame angular velocity, of the two PBHC_F_*_NOISE features.  dt is the control dt; ou_sqrt_dt = sqrt(dt), ou_sqrt_2theta =
+   * sqrt(2 theta) as the reference's numpy scalars (float32).  noise_process = 0: no state, no draws */
+  int32_t noise_process;
+  float ou_mu, ou_theta, ou_sigma, ou_sqrt_dt, ou_sqrt_2theta, ou_scale_rpy, ou_scale_ang_vel;
+  /* domain_rand.parallel_serial_pd (legged_robot_base.py:607-613): at every episodic DR of an env, after the randomize_pd_gain draws, the
+   * gain scales of the listed joints are MULTIPLIED by U(ps_pd_ratio) (kp, then kd; they compound across episodes when randomize_pd_gain is
+   * off).  domain_rand.parallel_serial_tau (:621-623, 822-829): at every episodic DR rao_scale of the listed joints += ps_tau_rao_lim N(0,1)
+   * (accumulating; it reaches the torque only through use_rao), and every control step torque += ps_tau_rfi_lim x torque_limit x N(0,1) on
+   * them, after the RFI term, before rao and clipping.  ps_*_slot[d]: column of dof d in the joint_idx list (the [N,J] draws), -1 if absent */
+  int32_t ps_pd, ps_pd_num, ps_pd_slot[PBHC_MAX_DOF];
+  float ps_pd_ratio[2];
+  int32_t ps_tau, ps_tau_num, ps_tau_slot[PBHC_MAX_DOF];
+  float ps_tau_rao_lim, ps_tau_rfi_lim;
   int32_t pad2_;
   uint64_t seed;
 } PbhcEnvConfig;
@@ -365,6 +386,10 @@ typedef struct PbhcStepIO {
   /* reset-state noise draws (PbhcEnvConfig.reset_noise), in the reference's call order: ovr_reset_root [N,13] = randn pos (3), randn axis (3),
    * rand angle (1), randn lin vel (3), randn ang vel (3); ovr_reset_dof_pos / ovr_reset_dof_vel [N,D] = randn (tracking_mode 1: rand) */
   const float* ovr_reset_root; const float* ovr_reset_dof_pos; const float* ovr_reset_dof_vel;
+  /* obs.noise_process / parallel_serial_* draws, raw N(0,1) / ratios: ovr_ou_step [N,6] the OU step's normals (every env), ovr_ou_reset [N,6]
+   * the stationary redraw's normals (envs that reset), ovr_ps_kp / ovr_ps_kd [N,J_pd] the U(ratio) factors, ovr_ps_rao [N,J_tau] the episodic
+   * normals (envs with an episodic DR), ovr_ps_tau [N,J_tau] the per-step torque normals (every env) */
+  const float* ovr_ou_step; const float* ovr_ou_reset; const float* ovr_ps_kp; const float* ovr_ps_kd; const float* ovr_ps_rao; const float* ovr_ps_tau;
   /* simulator-surface state (reference names; simulator/isaacgym/isaacgym.py:574-618) */
   float* root_states;             /* [N,13] */
   float* dof_state;               /* [N,D,2] (pos, vel) */
@@ -380,6 +405,7 @@ typedef struct PbhcStepIO {
   float* motion_start_times; float* motion_len; float* end_time_ratio_buf;               /* [N] */
   float* episode_sums;            /* [N,num_sum_cols] */
   float* hist;                    /* [N,hist_dim] */
+  float* ou_state;                /* [N,6] Ornstein-Uhlenbeck state of obs.noise_process (read and written by the step); NULL when it is off */
   int64_t* episode_length_buf; int64_t* last_episode_length_buf; int64_t* reset_buf; int64_t* action_delay_idx; /* [N] */
   const int64_t* motion_ids;      /* [N] slot -> clip */
   uint8_t* time_out_buf;          /* [N] bool */

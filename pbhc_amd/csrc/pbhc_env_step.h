@@ -571,6 +571,33 @@ __device__ __forceinline__ void reset_root_draws(uint64_t seed, uint32_t env, ui
   for (int k = 7; k < 13; ++k) z[k] = n[k - 1];
 }
 
+// one N(0,1) per (stream, idx): the first Box-Muller value of the quad's first pair (obs.noise_process, parallel_serial_*: streams 14, 15,
+// 17-19, listed in pbhc_math.h)
+__device__ __forceinline__ float rng_normal(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, uint32_t idx) {
+  float u[4], z0, z1;
+  pbhc::rng_uniform4(seed, env, step, stream, idx, u);
+  box_muller(u[0], u[1], &z0, &z1);
+  return z0;
+}
+// parallel_serial_pd's two U(ratio) factors of dof dd (kp, kd; stream 17) or the injected ones (column `slot` of [N, J])
+__device__ __forceinline__ float2 ps_pd_ratios(uint64_t seed, uint32_t env, uint32_t step, int dd, int slot, int J, float lo, float hi,
+                                               const float* ovr_kp, const float* ovr_kd) {
+  float u[4];
+  pbhc::rng_uniform4(seed, env, step, 17, (uint32_t)dd, u);
+  const uint32_t o = env * (uint32_t)J + (uint32_t)slot;
+  return make_float2(ovr_kp ? ovr_kp[o] : (hi - lo) * u[0] + lo, ovr_kd ? ovr_kd[o] : (hi - lo) * u[1] + lo);
+}
+// parallel_serial_tau's episodic N(0,1) of dof dd (stream 18) or the injected one
+__device__ __forceinline__ float ps_tau_rao_normal(uint64_t seed, uint32_t env, uint32_t step, int dd, int slot, int J, const float* ovr) {
+  return ovr ? ovr[env * (uint32_t)J + (uint32_t)slot] : rng_normal(seed, env, step, 18, (uint32_t)dd);
+}
+// quat_from_euler_xyz_better (utils/torch_utils.py:188-203), xyzw
+__device__ __forceinline__ f4 quat_from_euler_xyz(f3 rpy) {
+  const float cy = cosf(rpy.z * 0.5f), sy = sinf(rpy.z * 0.5f), cr = cosf(rpy.x * 0.5f), sr = sinf(rpy.x * 0.5f);
+  const float cp = cosf(rpy.y * 0.5f), sp = sinf(rpy.y * 0.5f);
+  return mk4(cy * sr * cp - sy * cr * sp, cy * cr * sp + sy * sr * cp, sy * cr * cp - cy * sr * sp, cy * cr * cp + sy * sr * sp);
+}
+
 // =================================================================================================
 //  k_env_step: LeggedRobotBase.step (legged_robot_base.py:239-338) for LeggedRobotMotionTracking
 // =================================================================================================
@@ -1049,6 +1076,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   float sumrow = 0.0f, pf_tscale = 0.0f, pf_sigma = 1.0f, pf_pen_scale = 1.0f, pf_far_thr = 0.0f, kpA = 1.0f, kdA = 1.0f, dpA = 0.0f, etr_old = 0.0f;
   int pf_tid = 0, pf_tpen = 0, pf_tsrc = -1, pf_colterm = -1;
   bool pf_dof_far = false;                                    // terminate_when_dof_far: the pre-pass (k_dof_far_any) found an env past the threshold
+  float ou_x = 0.0f;                                          // obs.noise_process: component min(lane, 5) of this env's OU state (stepped in phase C)
   long long adelay = 0;
   // role-B registers that live across phases (loads issued in its prologue, consumed after bar1)
   float pf_last_act = 0.0f, pf_last_qd = 0.0f;
@@ -1098,6 +1126,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       pf_sigma = (float)glob[PBHC_G_SIGMA + min(lane, PBHC_NUM_SIGMA - 1)];
       pf_pen_scale = (float)glob[PBHC_G_PENALTY_SCALE]; pf_far_thr = (float)glob[PBHC_G_MOTION_FAR_THR];
       if (c.terminate_when_dof_far) pf_dof_far = glob[PBHC_G_DOF_FAR_HIT] != 0.0;
+      if (c.noise_process) ou_x = at(io.ou_state, (u32)envc * 6u + (u32)min(lane, 5));
       kpA = NTLD(at(io.kp_scale, eDc + dc)); kdA = NTLD(at(io.kd_scale, eDc + dc));                // phase H (a reset replaces them in registers)
       dpA = io.default_dof_pos ? at(io.default_dof_pos, eDc + dc) : c.default_dof_pos[dc];
       adelay = io.action_delay_idx[envc];
@@ -1120,6 +1149,16 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
 #else       // (timing ablations, -DPBHC_ABL_*: what a phase costs is read off the launch time without it; results are meaningless)
     if (valid && lane < Bx) { st3(bp + 3 * lane, ld3(root)); st4(bq + 4 * lane, ld4(root + 3)); st3(bv + 3 * lane, ld3(root + 7)); st3(bw + 3 * lane, ld3(root + 10)); }
 #endif
+    // ---- obs.noise_process (legged_robot_base.py:357-358, noise_tool.py OUProcess.step): x += theta (mu - x) dt + sigma randn sqrt(dt), every
+    // env, before termination; lane k < 6 holds component k, every lane gets the stepped state for the noisy features below
+    float oux[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c.noise_process) {
+      const u32 k6 = (u32)min(lane, 5);
+      const float n = io.ovr_ou_step ? at(io.ovr_ou_step, (u32)envc * 6u + k6) : rng_normal(rt.seed, env, step_ctr, 14, k6);
+      ou_x = (ou_x + ((c.ou_mu - ou_x) * c.ou_theta) * dt) + (c.ou_sigma * n) * c.ou_sqrt_dt;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) oux[k] = __shfl(ou_x, k, PBHC_G);
+    }
     // ---- phase C: per-env scalars of the root state (legged_robot_base.py:346-380).  One lane per quantity and ONE code path per function:
     // lanes 0-2 evaluate the three atan2 (yaw, heading, roll), lane 3 the asin of the pitch, lanes 4-6 the three base-frame rotations (lane 0
     // doing all of it in turn was ~450 instructions; roll and pitch only exist where an observation reads them: general tracking).
@@ -1146,6 +1185,16 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         const int off = lane == 4 ? c.feat_off[PBHC_F_BASE_LIN_VEL] : (lane == 5 ? c.feat_off[PBHC_F_BASE_ANG_VEL] : c.feat_off[PBHC_F_PROJECTED_GRAVITY]);
         st3(feat + off, vo);
         if (lane == 6) { misc[M_GX] = vo.x; misc[M_GY] = vo.y; misc[M_GZ] = vo.z; }
+      } else if (c.noise_process && lane <= 8) {
+        // legged_robot_base.py:359-371: the base orientation with OU-perturbed euler angles (no wrap), then lane 7 base_ang_vel_noise (the
+        // noise added to the WORLD-frame angular velocity), lane 8 projected_gravity_noise — pre-reset values, as the clean pair
+        const f3 e = euler_xyz(rq4);
+        const float sr = c.ou_scale_rpy, d2r = (float)(3.14159265358979323846 / 180.0);
+        const f4 qn = quat_from_euler_xyz(mk3(e.x + (oux[0] * sr) * d2r, e.y + (oux[1] * sr) * d2r, e.z + (oux[2] * sr) * d2r));
+        const f3 w = ld3(root + 10);
+        const float sw = c.ou_scale_ang_vel;
+        const f3 vin = lane == 7 ? mk3(w.x + oux[3] * sw, w.y + oux[4] * sw, w.z + oux[5] * sw) : mk3(0.0f, 0.0f, -1.0f);
+        st3(feat + (lane == 7 ? c.feat_off[PBHC_F_BASE_ANG_VEL_NOISE] : c.feat_off[PBHC_F_PROJECTED_GRAVITY_NOISE]), quat_rotate_inverse(qn, vin));
       }
     }
     // the observation-noise base of this env and step (obs_noise_u): ONE Philox call per env, here — these waves wait at bar1 —, handed
@@ -1382,6 +1431,11 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         else if (c.control_type == 1) tq = kp * k_pg * (a_sc - qv) - kd * k_dg * (qv - pf_last_qd) / c.sim_dt;      // "V" (legged_robot_base.py:812-813)
         else tq = a_sc;                                                                                                 // "T" (:814-815)
         if (c.randomize_torque_rfi) tq = tq + (u_rfi * 2.0f - 1.0f) * c.rfi_lim * rfs * tl;
+        if (c.ps_tau && c.ps_tau_slot[d] >= 0) {         // parallel_serial_tau, per step (legged_robot_base.py:822-829): one draw per control step
+          const int sl = c.ps_tau_slot[d];
+          const float n = io.ovr_ps_tau ? at(io.ovr_ps_tau, (u32)env * (u32)c.ps_tau_num + (u32)sl) : rng_normal(rt.seed, env, step_ctr, 19, (u32)d);
+          tq = tq + (c.ps_tau_rfi_lim * tl) * n;
+        }
         if (c.use_rao) tq = tq + ras * tl;
         if (c.clip_torques) tq = clampf(tq, -tl, tl);
         tau[d] = tq;
@@ -1738,9 +1792,18 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     for (int dd = lane; dd < D; dd += PBHC_G) {
       float ur[4];
       pbhc::rng_uniform4(rt.seed, env, step_ctr, 2, dd, ur);
-      if (c.randomize_pd_gain) {
-        const float kpn = io.ovr_kp ? at(io.ovr_kp, eD + dd) : (c.kp_range[1] - c.kp_range[0]) * ur[0] + c.kp_range[0];
-        const float kdn = io.ovr_kd ? at(io.ovr_kd, eD + dd) : (c.kd_range[1] - c.kd_range[0]) * ur[1] + c.kd_range[0];
+      const bool ps_pd_d = c.ps_pd && c.ps_pd_slot[dd] >= 0;
+      if (c.randomize_pd_gain || ps_pd_d) {
+        float kpn = kp, kdn = kd;                           // the old scales (dd == lane, D <= 32): what parallel_serial_pd compounds alone
+        if (c.randomize_pd_gain) {
+          kpn = io.ovr_kp ? at(io.ovr_kp, eD + dd) : (c.kp_range[1] - c.kp_range[0]) * ur[0] + c.kp_range[0];
+          kdn = io.ovr_kd ? at(io.ovr_kd, eD + dd) : (c.kd_range[1] - c.kd_range[0]) * ur[1] + c.kd_range[0];
+        }
+        if (ps_pd_d) {                                      // parallel_serial_pd: the dynamics waves' form (phase G)
+          const float2 r = ps_pd_ratios(rt.seed, env, step_ctr, dd, c.ps_pd_slot[dd], c.ps_pd_num, c.ps_pd_ratio[0], c.ps_pd_ratio[1], io.ovr_ps_kp, io.ovr_ps_kd);
+          kpn = kpn * r.x;
+          kdn = kdn * r.y;
+        }
         at(io.kp_scale, eD + dd) = kpn;
         at(io.kd_scale, eD + dd) = kdn;
         feat[o_kp + dd] = kpn;
@@ -1748,8 +1811,11 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       }
       if (c.randomize_rfi_lim)
         at(io.rfi_lim_scale, eD + dd) = io.ovr_rfi_lim ? at(io.ovr_rfi_lim, eD + dd) : (c.rfi_lim_range[1] - c.rfi_lim_range[0]) * ur[2] + c.rfi_lim_range[0];
-      if (c.use_rao)
-        at(io.rao_scale, eD + dd) = io.ovr_rao ? at(io.ovr_rao, eD + dd) : (c.rao_lim - (-c.rao_lim)) * ur[3] + (-c.rao_lim);
+      if (c.use_rao) {
+        float ra = io.ovr_rao ? at(io.ovr_rao, eD + dd) : (c.rao_lim - (-c.rao_lim)) * ur[3] + (-c.rao_lim);
+        if (c.ps_tau && c.ps_tau_slot[dd] >= 0) ra = ra + c.ps_tau_rao_lim * ps_tau_rao_normal(rt.seed, env, step_ctr, dd, c.ps_tau_slot[dd], c.ps_tau_num, io.ovr_ps_rao);
+        at(io.rao_scale, eD + dd) = ra;
+      }
       if (c.randomize_ctrl_delay)
         for (int k = 0; k < Q; ++k) at(io.action_queue, ((u32)env * (u32)Q + (u32)k) * (u32)D + (u32)dd) = 0.0f;     // queue *= 0 (finite values)
     }
@@ -2010,6 +2076,15 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // a surviving env keeping everything else — after this step's torques, before its observations, as `_update_tasks_callback` sits
     const bool do_dr = do_reset || (valid && io.redraw_all != 0);
     if (valid && lane == 0) { misc[M_LASTEP] = misc[M_EPLEN]; misc[M_DELAY] = (float)adelay; }
+    if (c.noise_process && valid && lane < 6) {
+      // the stepped OU state, or for a reset env noise_process.reset_part (legged_robot_base.py:593-597): mu + sigma / sqrt(2 theta) randn
+      float xs = ou_x;
+      if (do_reset) {
+        const float n = io.ovr_ou_reset ? at(io.ovr_ou_reset, (u32)env * 6u + (u32)lane) : rng_normal(rt.seed, env, step_ctr, 15, (u32)lane);
+        xs = (n * c.ou_sigma) / c.ou_sqrt_2theta + c.ou_mu;
+      }
+      at(io.ou_state, (u32)env * 6u + (u32)lane) = xs;
+    }
     if (do_dr) {
       // env origin + clip meta: role B's prologue loads, handed over in LDS before bar1
       const f3 origin = mk3(misc[M_ORIGIN0], misc[M_ORIGIN1], misc[M_ORIGIN2]);
@@ -2050,10 +2125,21 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
           at(io.kp_scale, eD + dd) = kpA;
           at(io.kd_scale, eD + dd) = kdA;
         }
+        if (c.ps_pd && c.ps_pd_slot[dd] >= 0) {                // parallel_serial_pd: kpA / kdA hold the old scale when randomize_pd_gain is off
+          const float2 r = ps_pd_ratios(rt.seed, env, step_ctr, dd, c.ps_pd_slot[dd], c.ps_pd_num, c.ps_pd_ratio[0], c.ps_pd_ratio[1], io.ovr_ps_kp, io.ovr_ps_kd);
+          kpA = kpA * r.x;
+          kdA = kdA * r.y;
+          at(io.kp_scale, eD + dd) = kpA;
+          at(io.kd_scale, eD + dd) = kdA;
+        }
         if (c.randomize_rfi_lim)
           at(io.rfi_lim_scale, eD + dd) = io.ovr_rfi_lim ? at(io.ovr_rfi_lim, eD + dd) : (c.rfi_lim_range[1] - c.rfi_lim_range[0]) * ur[2] + c.rfi_lim_range[0];
-        if (c.use_rao)
-          at(io.rao_scale, eD + dd) = io.ovr_rao ? at(io.ovr_rao, eD + dd) : (c.rao_lim - (-c.rao_lim)) * ur[3] + (-c.rao_lim);
+        if (c.use_rao) {
+          float ra = io.ovr_rao ? at(io.ovr_rao, eD + dd) : (c.rao_lim - (-c.rao_lim)) * ur[3] + (-c.rao_lim);
+          // parallel_serial_tau, episodic part: accumulates on the fresh draw; without use_rao the scale never reaches the torque (skipped)
+          if (c.ps_tau && c.ps_tau_slot[dd] >= 0) ra = ra + c.ps_tau_rao_lim * ps_tau_rao_normal(rt.seed, env, step_ctr, dd, c.ps_tau_slot[dd], c.ps_tau_num, io.ovr_ps_rao);
+          at(io.rao_scale, eD + dd) = ra;
+        }
         if (c.randomize_ctrl_delay)
           for (int k = 0; k < Q; ++k) at(io.action_queue, ((u32)env * (u32)Q + (u32)k) * (u32)D + (u32)dd) = 0.0f;     // queue *= 0 (finite values)
         }

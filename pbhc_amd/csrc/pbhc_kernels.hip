@@ -688,6 +688,12 @@ static int finalize_config(const PbhcEnvConfig* cfg, PbhcEnvConfig* fin, int* ld
   ARG_CHECK(cfg->num_term_contact >= 0 && cfg->num_term_contact <= PBHC_MAX_IDX);
   for (int i = 0; i < cfg->num_term_contact; ++i) ARG_CHECK(cfg->term_contact[i] >= 0 && cfg->term_contact[i] < cfg->skel.num_bodies);
   ARG_CHECK(cfg->queue_len >= 1 && cfg->queue_len <= PBHC_MAX_QUEUE);
+  // parallel_serial_*: every listed joint a dof of the skeleton, one column of the [N,J] draws each
+  ARG_CHECK(cfg->ps_pd_num >= 0 && cfg->ps_pd_num <= cfg->skel.num_dof && cfg->ps_tau_num >= 0 && cfg->ps_tau_num <= cfg->skel.num_dof);
+  for (int d = 0; d < PBHC_MAX_DOF; ++d) {       // (the slot tables are read only when their switch is on)
+    if (cfg->ps_pd) ARG_CHECK(cfg->ps_pd_slot[d] >= -1 && cfg->ps_pd_slot[d] < cfg->ps_pd_num && (d < cfg->skel.num_dof || cfg->ps_pd_slot[d] == -1));
+    if (cfg->ps_tau) ARG_CHECK(cfg->ps_tau_slot[d] >= -1 && cfg->ps_tau_slot[d] < cfg->ps_tau_num && (d < cfg->skel.num_dof || cfg->ps_tau_slot[d] == -1));
+  }
   ARG_CHECK(cfg->feat_dim > 0 && cfg->feat_dim < 16384);
   // the step kernel addresses every per-env tensor with 32-bit element offsets from its base pointer
   ARG_CHECK((uint64_t)cfg->num_envs * (uint64_t)(cfg->skel.num_bodies * 13 > cfg->hist_dim + 64 ? cfg->skel.num_bodies * 13 : cfg->hist_dim + 64) < (1ull << 30));
@@ -922,6 +928,7 @@ static int env_step_check(PbhcEnv* e, const PbhcStepIO* io) {
     ARG_CHECK((uint64_t)e->cfg.num_envs * (uint64_t)(io->obs_pitch[g] ? io->obs_pitch[g] : e->cfg.groups[g].pitch) < (1ull << 30));   // 32-bit row offsets in the kernel
   }
   ARG_CHECK(io->hist_pitch == 0 || io->hist_pitch >= e->cfg.hist_dim);
+  ARG_CHECK(!e->cfg.noise_process || io->ou_state);
   return PBHC_OK;
 }
 

@@ -298,6 +298,10 @@ __device__ __forceinline__ void philox4x32(uint32_t k0, uint32_t k1, uint32_t c0
 }
 // uniform in [0,1): 24 mantissa bits
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+// Streams of k_env_step (counter word c2), each drawn by one site only, so that a switch turned on or off leaves every other draw of the
+// step unchanged: 1 torque RFI, 2 episodic DR (kp, kd, rfi limit, rao), 6 reset start phase + control delay, 9 default joint angles,
+// 11 termination gates (env word 0xFFFFFFFF), 12 / 13 reset-state noise (root / dofs), 14 / 15 obs.noise_process (OU step / stationary
+// redraw), 16 observation noise base, 17 parallel_serial_pd ratios, 18 / 19 parallel_serial_tau (episodic rao / per-step torque).
 // four uniforms of one Philox call, keyed (env, step, stream, idx): for draws that are consumed together
 __device__ __forceinline__ void rng_uniform4(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, uint32_t idx, float u[4]) {
   uint32_t o[4];

@@ -42,7 +42,12 @@ OBS_FEATURES = {
     "dr_friction": "DR_FRICTION", "dr_ctrl_delay": "DR_CTRL_DELAY", "relyaw": "RELYAW", "base_pos_z": "BASE_POS_Z",
     "dif_joint_angles": "DIF_JOINT_ANGLES", "dif_joint_velocities": "DIF_JOINT_VELOCITIES",
     "local_ref_rigid_body_vel": "LOCAL_REF_RIGID_BODY_VEL", "global_ref_rigid_body_vel": "GLOBAL_REF_RIGID_BODY_VEL",
+    # legged_robot_base.py:1136-1146.  dof_pos_noise / dof_vel_noise are the clean joint values (live views of the simulator's, :370-371),
+    # so they read the clean features; the two root-frame names read features of their own while obs.noise_process runs, and the clean
+    # ones when it is off (:373-379 aliases them): see NOISE_PROCESS_FEATURES
+    "base_ang_vel_noise": "BASE_ANG_VEL", "projected_gravity_noise": "PROJECTED_GRAVITY", "dof_pos_noise": "DOF_POS", "dof_vel_noise": "DOF_VEL",
 }
+NOISE_PROCESS_FEATURES = {"base_ang_vel_noise": "BASE_ANG_VEL_NOISE", "projected_gravity_noise": "PROJECTED_GRAVITY_NOISE"}
 # general tracking getters (general_tracking.py:821-954): plain features ...
 OBS_FEATURES_V2 = {
     "roll_pitch": "ROLL_PITCH", "root_height": "BASE_POS_Z", "contact_mask": "CONTACT_MASK", "ref_contact_mask": "REF_CONTACT_MASK",
@@ -89,6 +94,22 @@ def determine_obs_dim(cfg):
 import os as _os
 
 PACKED_MAPS = _os.environ.get("PBHC_PACKED_MAPS", "1") != "0"     # compact 16-bit observation maps staged in LDS (PbhcEnvConfig.map_image); 0: diagnosis only
+
+
+def _joint_idx(idx, D, what):
+    """domain_rand.<what>.joint_idx as a list of dof indices in [0, D) (D <= PBHC_MAX_DOF); torch's negative indices are taken modulo D, as the
+    reference's advanced indexing does.  Out-of-range and repeated entries are refused (the reference raises on the first, and on the
+    second its in-place `*=` / `+=` through the index would apply only one of the draws)"""
+    out = []
+    for j in list(idx):
+        j = int(j)
+        if not -D <= j < D or D > K["PBHC_MAX_DOF"]:
+            raise IndexError(f"domain_rand.{what}.joint_idx: {j} is out of range for {D} dofs (PBHC_MAX_DOF = {K['PBHC_MAX_DOF']})")
+        j %= D
+        if j in out:
+            raise ValueError(f"domain_rand.{what}.joint_idx lists dof {j} twice")
+        out.append(j)
+    return out
 
 
 class EnvLayout:
@@ -158,9 +179,22 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     c.kd_range[0], c.kd_range[1] = float(dr.kd_range[0]), float(dr.kd_range[1])
     c.randomize_rfi_lim = int(bool(dr.randomize_rfi_lim))
     c.rfi_lim_range[0], c.rfi_lim_range[1] = float(dr.rfi_lim_range[0]), float(dr.rfi_lim_range[1])
-    for unsupported in ("parallel_serial_pd", "parallel_serial_tau"):
-        if unsupported in dr and dr[unsupported].get("enable", False):
-            raise NotImplementedError(f"domain_rand.{unsupported}")
+    L.ps_pd_idx, L.ps_tau_idx = [], []
+    if "parallel_serial_pd" in dr and dr.parallel_serial_pd.get("enable", False):
+        # legged_robot_base.py:607-613: kp / kd scales of the listed joints *= U(ratio) at every episodic DR (after randomize_pd_gain)
+        pspd = dr.parallel_serial_pd
+        L.ps_pd_idx = _joint_idx(pspd.joint_idx, D, "parallel_serial_pd")
+        c.ps_pd, c.ps_pd_num = 1, len(L.ps_pd_idx)
+        c.ps_pd_ratio[0], c.ps_pd_ratio[1] = float(pspd.ratio[0]), float(pspd.ratio[1])
+    if "parallel_serial_tau" in dr and dr.parallel_serial_tau.get("enable", False):
+        # legged_robot_base.py:621-623 (rao_scale += rao_lim randn, episodic) and 822-829 (torque += rfi_lim torque_limit randn, per step)
+        pst = dr.parallel_serial_tau
+        L.ps_tau_idx = _joint_idx(pst.joint_idx, D, "parallel_serial_tau")
+        c.ps_tau, c.ps_tau_num = 1, len(L.ps_tau_idx)
+        c.ps_tau_rao_lim, c.ps_tau_rfi_lim = float(pst.rao_lim), float(pst.rfi_lim)
+    for i in range(K["PBHC_MAX_DOF"]):
+        c.ps_pd_slot[i] = L.ps_pd_idx.index(i) if i in L.ps_pd_idx else -1
+        c.ps_tau_slot[i] = L.ps_tau_idx.index(i) if i in L.ps_tau_idx else -1
     c.randomize_default_dof_pos = int(bool(dr.get("randomize_default_dof_pos", False)))     # legged_robot_base.py:632-635
     if c.randomize_default_dof_pos:
         c.dof_pos_range[0], c.dof_pos_range[1] = float(dr.dof_pos_range[0]), float(dr.dof_pos_range[1])
@@ -378,6 +412,22 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     feats = dict(OBS_FEATURES)
     if mode == 1:
         feats.update(OBS_FEATURES_V2)
+    npc = ob.get("noise_process", None)
+    if npc is not None and npc.get("enable", False):
+        # legged_robot_base.py:122-129 + utils/noise_tool.py: only OUProcess defines reset_part, which _reset_tasks_callback calls on every
+        # reset (:593-597); the other types raise NotImplementedError there on the first reset, so the reference cannot train with them
+        if npc.get("type") != "ou":
+            raise NotImplementedError(f"obs.noise_process.type {npc.get('type')!r}: only 'ou' can run in the reference's env (WhiteNoise, EmptyNoise "
+                                      "and PinkNoise define no reset_part, which the env calls on the first reset; utils/noise_tool.py)")
+        kw = npc.get("kwargs", {})
+        mu, sigma, theta = float(kw.mu), float(kw.sigma), float(kw.theta)
+        if not theta > 0.0:
+            raise ValueError(f"obs.noise_process.kwargs.theta must be > 0 (stationary std sigma / sqrt(2 theta)), got {theta}")
+        c.noise_process = 1
+        c.ou_mu, c.ou_theta, c.ou_sigma = mu, theta, sigma
+        c.ou_sqrt_dt, c.ou_sqrt_2theta = float(np.sqrt(dt)), float(np.sqrt(2 * theta))
+        c.ou_scale_rpy, c.ou_scale_ang_vel = float(npc.scale.rpy), float(npc.scale.base_ang_vel)
+        feats.update(NOISE_PROCESS_FEATURES)
     mult = lambda k: S if (k.startswith("future_motion_") and S) else 1       # future keys list their PER-STEP dim (obs_ppo_teacher.yaml)
     # widths of the tensors the env hands out: the future group is [N, S * per-step dim] (ppo_mimic.py:206-216)
     L.obs_dims = dims
@@ -410,6 +460,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
         "ANCHOR_REF_ROT": 6, "DIF_ROOT_VELOCITY": 3, "DIF_ROOT_ROT": 4, "DIF_ROOT_HEIGHT": 1, "REF_CONTACT_MASK": 2,
         "FUT_ROOT_HEIGHT": max(S, 1), "FUT_ROLL_PITCH": max(2 * S, 1), "FUT_BASE_LIN_VEL": max(3 * S, 1), "FUT_BASE_ANG_VEL": max(3 * S, 1),
         "FUT_DOF_POS": max(S * D, 1), "FUT_LOCAL_KEY_POS": max(S * Kb * 3, 1),
+        "BASE_ANG_VEL_NOISE": 3, "PROJECTED_GRAVITY_NOISE": 3,
     }
     # which features do the observation maps read?  the kernel skips the others (feat_off = -1)
     used = {"HISTORY", "ZERO"}
@@ -443,7 +494,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     off += fdim["HISTORY"]
     c.feat_dim = off
     # readiness class of every feature word (see the compact maps below): which phase of the step kernel produces it
-    CLASS0 = {"HISTORY", "ZERO", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJECTED_GRAVITY", "REF_MOTION_PHASE", "RELYAW", "ROLL_PITCH", "DR_BASE_COM",
+    CLASS0 = {"HISTORY", "ZERO", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJECTED_GRAVITY", "BASE_ANG_VEL_NOISE", "PROJECTED_GRAVITY_NOISE", "REF_MOTION_PHASE", "RELYAW", "ROLL_PITCH", "DR_BASE_COM",
               "DR_LINK_MASS", "DR_FRICTION", "DR_BASE_MASS", "REF_CONTACT_MASK", "FUT_ROOT_HEIGHT", "FUT_ROLL_PITCH", "FUT_BASE_LIN_VEL",
               "FUT_BASE_ANG_VEL", "FUT_DOF_POS", "FUT_LOCAL_KEY_POS"}
     CLASS2 = {"DOF_POS", "DOF_VEL", "ACTIONS", "DR_KP", "DR_KD", "DR_CTRL_DELAY", "BASE_POS_Z", "CONTACT_MASK"}
@@ -673,7 +724,5 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     g[K["PBHC_G_SOFT_VEL_VAL"]] = float(lc.soft_dof_vel_initial_limit)
     g[K["PBHC_G_SOFT_TAU_VAL"]] = float(lc.soft_torque_initial_limit)
     g[K["PBHC_G_NOISE_CURRICULUM"]] = float(ob.noise_initial_value) if ob.get("add_noise_currculum", False) else 1.0
-    if "noise_process" in ob and ob.noise_process.get("enable", False):
-        raise NotImplementedError("obs.noise_process")
     L.globals0 = g
     return c, L

@@ -221,6 +221,8 @@ class LeggedRobotMotionTracking:
         # (legged_robot_base.py:149-151,390-395)
         self.reinit_epis_rand = float(config.domain_rand.get("reinit_epis_rand", -1))
         self._reinit = ReinitSchedule(self.reinit_epis_rand)
+        if self._c.noise_process:                   # OUProcess.reset at construction (legged_robot_base.py:124-127): the stationary law
+            self._ou_state.copy_(self._ou_stationary(N))
         self.init_done = True
 
     def specialise(self, mode="jit", verbose=False):
@@ -293,6 +295,9 @@ class LeggedRobotMotionTracking:
         self.raw_default_dof_pos = self.default_dof_pos.clone()                    # legged_robot_base.py:81-93
         self.p_gains = torch.tensor([self._c.p_gains[i] for i in range(D)], device=dev)
         self.d_gains = torch.tensor([self._c.d_gains[i] for i in range(D)], device=dev)
+        # obs.noise_process: the OU state [N, 6] (rpy, angular velocity), drawn from its stationary law at construction (noise_tool.py
+        # OUProcess.reset); the step kernel reads and writes it in place, so a captured rollout graph carries it like any other state
+        self._ou_state = f(N, 6)                    # (its construction-time draw: the end of __init__)
 
     def _init_obs_buffers(self):
         L = self.layout
@@ -352,6 +357,7 @@ class LeggedRobotMotionTracking:
         io.default_dof_pos = p(self.default_dof_pos) if self._c.randomize_default_dof_pos else None      # per-env defaults only when they are randomised
         io.motion_start_times, io.motion_len, io.end_time_ratio_buf = p(self.motion_start_times), p(self.motion_len), p(self.end_time_ratio_buf)
         io.episode_sums, io.hist = p(self._episode_sums), p(self._hist)
+        io.ou_state = p(self._ou_state) if self._c.noise_process else None
         io.episode_length_buf, io.last_episode_length_buf = p(self._episode_length_buf), p(self.last_episode_length_buf)
         io.reset_buf, io.action_delay_idx = p(self.reset_buf), p(self.action_delay_idx)
         self._slot_clip = self._motion_lib.slot_table.contiguous()
@@ -429,12 +435,16 @@ class LeggedRobotMotionTracking:
 
     # ---- test / replay hooks: inject the random draws instead of the in-kernel Philox ---------
     def set_injected_draws(self, u_rfi=None, start_time=None, kp=None, kd=None, rfi_lim=None, rao=None, delay=None, dof_pos_bias=None, gate_u=None,
-                           reset_root=None, reset_dof_pos=None, reset_dof_vel=None):
+                           reset_root=None, reset_dof_pos=None, reset_dof_vel=None, ou_step=None, ou_reset=None, ps_kp=None, ps_kd=None, ps_rao=None,
+                           ps_tau=None):
         """Keeps the tensors alive and points the kernel at them (None -> in-kernel RNG).  reset_root [N,13] / reset_dof_pos, reset_dof_vel [N,D]:
-        the raw draws of the reset-state noise (PbhcStepIO.ovr_reset_*), consumed by the envs that reset."""
+        the raw draws of the reset-state noise (PbhcStepIO.ovr_reset_*), consumed by the envs that reset.  ou_step / ou_reset [N,6]: the normals
+        of the OU step (every env) and of its stationary redraw (envs that reset); ps_kp / ps_kd [N,J_pd]: the U(ratio) factors of
+        parallel_serial_pd; ps_rao / ps_tau [N,J_tau]: parallel_serial_tau's episodic and per-step normals."""
         self._overrides = dict(u_rfi=u_rfi, ovr_start_time=start_time, ovr_kp=kp, ovr_kd=kd, ovr_rfi_lim=rfi_lim, ovr_rao=rao, ovr_delay=delay,
                                ovr_dof_pos_bias=dof_pos_bias, ovr_gate_u=gate_u, ovr_reset_root=reset_root, ovr_reset_dof_pos=reset_dof_pos,
-                               ovr_reset_dof_vel=reset_dof_vel)
+                               ovr_reset_dof_vel=reset_dof_vel, ovr_ou_step=ou_step, ovr_ou_reset=ou_reset, ovr_ps_kp=ps_kp, ovr_ps_kd=ps_kd,
+                               ovr_ps_rao=ps_rao, ovr_ps_tau=ps_tau)
         self._io_epoch += 1
         for k, v in self._overrides.items():
             setattr(self._io, k, None if v is None else v.data_ptr())
@@ -611,6 +621,7 @@ class LeggedRobotMotionTracking:
         s.robot_root_states[:, 7:10] = ref["root_vel"]; s.robot_root_states[:, 10:13] = ref["root_ang_vel"]
         if c.reset_noise:
             self._reset_state_noise()
+        self._reset_all_noise_process_and_parallel_serial()
         self.extras["episode"] = {"rew_" + k: (v / self.max_episode_length_s).clone() for k, v in self.episode_sums.items()}
         self.extras["episode"]["end_epis_length"] = self.last_episode_length_buf.clone()
         self._episode_sums.zero_()
@@ -651,6 +662,31 @@ class LeggedRobotMotionTracking:
             self.action_delay_idx.copy_(torch.randint(dr.ctrl_delay_step_range[0], dr.ctrl_delay_step_range[1] + 1, (N,), device=dev, generator=self._gen))
         if dr.get("randomize_default_dof_pos", False):                            # legged_robot_base.py:632-635
             self.default_dof_pos.copy_(u(dr.dof_pos_range[0], dr.dof_pos_range[1]) + self.raw_default_dof_pos)
+
+    def _reset_all_noise_process_and_parallel_serial(self):
+        """The host-side forms of parallel_serial_pd / parallel_serial_tau (the episodic part) and of the OU redraw, for every env.  Drawn
+        LAST from the env's generator, so that every other draw of _reset_all_state is the same with the switches on or off (the reference's
+        draw order on its generator is not reproduced anyway); the arithmetic is the reference's: the factors multiply the gains that
+        _episodic_domain_randomization_all left, the normals add to the rao scale it drew."""
+        N, dev, c, L = self.num_envs, self.device, self._c, self.layout
+        if c.ps_pd:                    # legged_robot_base.py:607-613: compounds on the old scale when randomize_pd_gain is off
+            r = lambda: (c.ps_pd_ratio[1] - c.ps_pd_ratio[0]) * torch.rand(N, c.ps_pd_num, device=dev, generator=self._gen) + c.ps_pd_ratio[0]
+            self._kp_scale[:, L.ps_pd_idx] *= r()
+            self._kd_scale[:, L.ps_pd_idx] *= r()
+        if c.ps_tau and c.use_rao:     # :621-623, accumulating; without use_rao the scale never reaches the torque, so it is not drawn
+            self._rao_scale[:, L.ps_tau_idx] += c.ps_tau_rao_lim * torch.randn(N, c.ps_tau_num, device=dev, generator=self._gen)
+        if c.noise_process:            # _reset_tasks_callback -> noise_process.reset_part (:593-597)
+            self._ou_state.copy_(self._ou_stationary(N))
+
+    def _ou_stationary(self, n):
+        """n draws of the OU process's stationary law, mu + sigma / sqrt(2 theta) N(0,1) per component (noise_tool.py OUProcess.reset_part)"""
+        c = self._c
+        return torch.randn(n, 6, device=self.device, generator=self._gen) * c.ou_sigma / c.ou_sqrt_2theta + c.ou_mu
+
+    @property
+    def noise_process_state(self):
+        """the OU state of obs.noise_process [N, 6] (rpy, angular velocity), as the reference's env.noise_process.x; zeros when it is off"""
+        return self._ou_state
 
     def step(self, actor_state):
         """legged_robot_base.py:239-265 — one fused launch."""
