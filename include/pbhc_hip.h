@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define PBHC_ABI_VERSION 13
+#define PBHC_ABI_VERSION 14
 
 #define PBHC_OK 0
 #define PBHC_EINVAL (-22)   /* bad argument / size over a compile-time maximum */
@@ -438,12 +438,38 @@ typedef struct PbhcStepIO {
   int32_t obs_wide;
 } PbhcStepIO;
 
+/* The evaluation recorder (env.config.save_motion, motion_tracking.py:140-170,861-938): device-resident [N,T,...] buffers, T = total_steps =
+ * save_total_steps, one frame per env and control step, each env's frames contiguous.  Not part of PbhcEnvConfig: the step kernel and its
+ * specialised builds do not know the recorder exists. */
+#define PBHC_REC_SHARDS 128
+#define PBHC_REC_COUNTER_WORDS 4160   /* 32 * (2 + PBHC_REC_SHARDS) */
+typedef struct PbhcRecordIO {
+  int32_t total_steps;            /* T */
+  int32_t obs_group;              /* index of actor_obs in PbhcStepIO.obs */
+  /* device int32 [PBHC_REC_COUNTER_WORDS], zeroed by the caller.  Word 0: control steps seen so far — read by every workgroup, advanced
+   * (saturating at T + 3) by the one that finishes last; values 0..2 and >= T + 3 record nothing, value k writes frame k - 3 (the reference
+   * drops its first three records).  Words 32 and 32 * (2 + s), s < PBHC_REC_SHARDS, each on a 128-byte line of its own: the workgroups'
+   * two-level arrival ticket of the current launch (all back to 0 when the launch ends) */
+  int32_t* counter;
+  float* root_trans_offset;       /* [N,T,3]  root position - env origin */
+  float* root_rot;                /* [N,T,4]  xyzw */
+  float* root_lin_vel; float* root_ang_vel;   /* [N,T,3] */
+  float* dof; float* dof_vel;     /* [N,T,D] */
+  float* contact_mask;            /* [N,T,2]  contacts_filt */
+  float* pose_aa;                 /* [N,T,Bx,3] row 0: rotation vector of the root quaternion (scipy as_rotvec), rows 1..D: dof_axis * dof, rest 0 */
+  float* action;                  /* [N,T,D]  env.actions */
+  float* actor_obs;               /* [N,T,dim of group obs_group], dense */
+  int64_t* terminate;             /* [N,T]    reset_buf */
+  float* motion_times;            /* [N,T]    episode_length_buf * dt + motion_start_times */
+} PbhcRecordIO;
+
 typedef struct PbhcEnv PbhcEnv;   /* opaque */
 
 int pbhc_abi_version(void);
 const char* pbhc_last_error(void);
 int pbhc_sizeof_env_config(void);
 int pbhc_sizeof_step_io(void);
+int pbhc_sizeof_record_io(void);
 
 /* Load-time FK + filtered velocities of one clip -> packed frame rows.
  * Replaces Humanoid_Batch.fk_batch / _compute_velocity / _compute_angular_velocity
@@ -506,6 +532,11 @@ int pbhc_env_step(PbhcEnv* env, const PbhcStepIO* io, void* stream);
  * caller's choice, ordered by the caller after the launch and before the next launch / pbhc_policy_sample (which reads the step counter). */
 int pbhc_env_step_launch(PbhcEnv* env, const PbhcStepIO* io, void* stream);
 int pbhc_env_step_finish(PbhcEnv* env, const PbhcStepIO* io, void* stream);
+/* One frame of the evaluation recorder: k_record_motion on `stream`, to be called right after pbhc_env_step / pbhc_env_step_launch of the same
+ * `io` on the same stream (it reads the post-reset state that step left: root_states, dof_state, actions, contacts_filt, reset_buf,
+ * episode_length_buf, motion_start_times and the observation row obs[rec->obs_group]).  A plain launch with no host-side state: a stream
+ * capture may record it, the frame index lives in rec->counter. */
+int pbhc_record_motion(PbhcEnv* env, const PbhcStepIO* io, const PbhcRecordIO* rec, void* stream);
 /* Second half of a step launched with io->totals_out: `totals` = the element-wise sum over ranks of every shard's totals_out,
  * `num_envs_total` = the number of envs of all ranks.  Must run before the next pbhc_env_step of this env. */
 #define PBHC_NUM_TOTALS 64
@@ -745,6 +776,9 @@ enum PbhcDebugFn {
   PBHC_DBG_NUM
 };
 int pbhc_debug_rotations(int fn, const float* a, const float* b, const float* c, int n, float* out, void* stream);
+/* Test-only, host code: csrc/pbhc_math.h rotvec_from_quat (the recorder's pose_aa row 0) on n xyzw quaternions given in double, evaluated
+ * in double (out64 [n,3]) and — after rounding the quaternion to float — in float (out32 [n,3]); either output may be NULL. */
+int pbhc_debug_rotvec_host(const double* quat_xyzw, int n, double* out64, float* out32);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,7 @@ PbhcOutMap = _S["PbhcOutMap"]
 PbhcEnvConfig = _S["PbhcEnvConfig"]
 PbhcMotionTable = _S["PbhcMotionTable"]
 PbhcStepIO = _S["PbhcStepIO"]
+PbhcRecordIO = _S["PbhcRecordIO"]
 PbhcMlpSample = _S["PbhcMlpSample"]
 PbhcMlpInput = _S["PbhcMlpInput"]
 PbhcConvEncoder = _S["PbhcConvEncoder"]
@@ -92,7 +93,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_policy_sample", "pbhc_rollout_post", "pbhc_act_bwd_bias", "pbhc_env_finalize", "pbhc_act_bwd_partials", "pbhc_colsum_final", "pbhc_adam_clip2", "pbhc_debug_rotations", "pbhc_motion_build_batch",
            "pbhc_linear_act_fwd", "pbhc_env_config_lds_bytes", "pbhc_linear_act_fwd_out", "pbhc_debug_out_bwd_variant", "pbhc_gather_rows", "pbhc_linear_dgrad_act", "pbhc_gemm_debug_force_shape", "pbhc_linear_wgrad", "pbhc_linear_wgrad_parts", "pbhc_linear_act_fwd_strided",
            "pbhc_env_step_launch", "pbhc_env_step_finish", "pbhc_mlp_fwd", "pbhc_mlp_fwd_lds_bytes", "pbhc_mlp_pack", "pbhc_mlp_packed_floats", "pbhc_rollout_post2", "pbhc_mlp_fwd_sample", "pbhc_linear_out_bwd",
-           "pbhc_env_get_config", "pbhc_env_attach_specialised", "pbhc_env_is_specialised", "pbhc_env_config_finalize", "pbhc_kl_lr_rule", "pbhc_debug_fk", "pbhc_mlp_fwd_cat", "pbhc_conv_encoder_fwd", "pbhc_conv_encoder_lds_bytes"]
+           "pbhc_env_get_config", "pbhc_env_attach_specialised", "pbhc_env_is_specialised", "pbhc_env_config_finalize", "pbhc_kl_lr_rule", "pbhc_debug_fk", "pbhc_mlp_fwd_cat", "pbhc_conv_encoder_fwd", "pbhc_conv_encoder_lds_bytes",
+           "pbhc_record_motion", "pbhc_sizeof_record_io", "pbhc_debug_rotvec_host"]
 
 
 class PbhcError(RuntimeError):
@@ -109,7 +111,8 @@ def _load():
     lib.pbhc_last_error.restype = C.c_char_p
     if lib.pbhc_abi_version() != K["PBHC_ABI_VERSION"]:
         raise PbhcError("libpbhc_hip.so ABI version does not match include/pbhc_hip.h")
-    if lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO):
+    if (lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO)
+            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO)):
         raise PbhcError("struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h — rebuild")
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     lib.pbhc_motion_build.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, f, vp, vp, vp]
@@ -129,6 +132,8 @@ def _load():
     lib.pbhc_env_step_launch.argtypes = [vp, C.POINTER(PbhcStepIO), vp]
     lib.pbhc_env_step_finish.argtypes = [vp, C.POINTER(PbhcStepIO), vp]
     lib.pbhc_env_finalize.argtypes = [vp, vp, C.c_double, vp]
+    lib.pbhc_record_motion.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcRecordIO), vp]
+    lib.pbhc_debug_rotvec_host.argtypes = [vp, i, vp, vp]
     lib.pbhc_env_profile.argtypes = [vp, i]
     lib.pbhc_env_profile_read.argtypes = [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]
     lib.pbhc_env_profile_overhead.argtypes = [vp, vp, C.POINTER(C.c_float)]

@@ -822,7 +822,68 @@ class MHPPO:
         return obs
 
     def evaluate_policy(self):
+        if getattr(self.env, "save_motion", False):
+            return self._evaluate_and_record()
         return self.evaluate_policy_steps(int(self.env.max_episode_length))
+
+    @torch.no_grad()
+    def _evaluate_and_record(self):
+        """env.config.save_motion on (eval_agent.py with +opt=record): the reference's evaluation loop is `while True`, and a person stops it
+        once the env has dumped its recording; here the loop ends at the dump, i.e. when the recorder — which has been counting control steps
+        since the env was built, as the reference's lists do — has seen save_total_steps + 3 of them.  The steps run as replays of ONE captured
+        graph of up to EVAL_GRAPH_STEPS x (actor forward, fused env step, recorder frame) when the env allows it (`rollout_graph_safe`;
+        PBHC_ROLLOUT_GRAPH=0 or a failed capture: the eager loop); the remainder, and the first step (online GEMM selection must not run inside
+        a capture), run eagerly.  Leaves `self.eval_metrics`: the recording scored on the device (metrics.eval_batch_traj_device against the
+        clip of env 0, as sample_eps.py) + `first_termination_ratio` (ratio_eps.py) of the recorded `terminate`."""
+        from ..eval import metrics
+
+        env = self.env
+        self._eval_mode()
+        env.set_is_evaluating()
+        env.reset_all()
+        one = lambda: env.step({"actions": self.actor.act_inference(env.obs_buf_dict["actor_obs"])})[0]
+        total = env.layout.record["total_steps"] + 3
+        if not env.motion_recorded:
+            one()
+        chunk = min(self.EVAL_GRAPH_STEPS, total - env._rec_steps)
+        self._eval_used_graph = False
+        if chunk >= 2 and os.environ.get("PBHC_ROLLOUT_GRAPH", "1") != "0" and env.rollout_graph_safe(chunk):
+            g = self._capture_eval_steps(one, chunk)
+            while g is not None and total - env._rec_steps >= chunk and env.rollout_graph_safe(chunk):
+                g.replay()
+                env.after_graph_steps(chunk)
+                self._eval_used_graph = True
+        while not env.motion_recorded:
+            one()
+        rec = env.recorded_motion_device()
+        clip = env._motion_lib._clips[int(env._motion_lib.slot_clip[0])]
+        self.eval_metrics = metrics.eval_batch_traj_device(env.skeleton, rec, clip)
+        self.eval_metrics["first_termination_ratio"] = metrics.first_termination_ratio(rec["terminate"].cpu().numpy())
+        return env.obs_buf_dict
+
+    EVAL_GRAPH_STEPS = 24
+
+    def _capture_eval_steps(self, one, chunk):
+        """`chunk` evaluation steps as one hipGraph (nothing executes during the capture); None when the capture fails"""
+        env = self.env
+        g = torch.cuda.CUDAGraph()
+        side = self.__dict__.setdefault("_graph_stream", torch.cuda.Stream(device=self.device))
+        counter0 = env.common_step_counter
+        env.simulator.use_device_cursor()
+        try:
+            torch.cuda.synchronize()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                    for _ in range(chunk):
+                        one()
+            torch.cuda.current_stream().wait_stream(side)
+        except Exception as e:                                   # noqa: BLE001 (whatever the capture objects to: report once, go on eagerly)
+            print(f"[pbhc] evaluation graph capture failed ({type(e).__name__}: {e}); the evaluation stays eager")
+            g = None
+        finally:
+            env.common_step_counter = counter0               # the captured env.step() calls advanced it; after_graph_steps does, per replay
+        return g
 
     # ---- logging (mh_ppo.py:547-700, reduced to the Perf/* + Loss/* + Train/* scalars) ------
     def _post_epoch_logging(self, log, width=80, pad=40):

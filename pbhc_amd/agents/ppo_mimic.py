@@ -754,6 +754,9 @@ class PPO:
         return obs
 
     def evaluate_policy(self):
+        if getattr(self.env, "save_motion", False):
+            # the reference's recorder lives in LeggedRobotMotionTracking, which this agent's general-tracking env does not derive from
+            raise NotImplementedError("env.config.save_motion with ppo_mimic.PPO: the reference records with the motion-tracking env and MHPPO only")
         return self.evaluate_policy_steps(int(self.env.max_episode_length))
 
     def _post_epoch_logging(self, log, width=80, pad=40):

@@ -65,3 +65,17 @@ extern "C" int pbhc_debug_rotations(int fn, const float* a, const float* b, cons
   if (hipGetLastError() != hipSuccess) return PBHC_EHIP;
   return PBHC_OK;
 }
+
+// host code only: the recorder's rotation-vector routine in both precisions, for the CPU test against scipy's as_rotvec
+extern "C" int pbhc_debug_rotvec_host(const double* quat_xyzw, int n, double* out64, float* out32) {
+  if (!quat_xyzw || n < 0) {
+    snprintf(g_pbhc_err, sizeof(g_pbhc_err), "pbhc_debug_rotvec_host: bad argument (n %d)", n);
+    return PBHC_EINVAL;
+  }
+  for (int i = 0; i < n; ++i) {
+    const double* q = quat_xyzw + 4 * (size_t)i;
+    if (out64) rotvec_from_quat<double>(q[0], q[1], q[2], q[3], out64 + 3 * (size_t)i);
+    if (out32) rotvec_from_quat<float>((float)q[0], (float)q[1], (float)q[2], (float)q[3], out32 + 3 * (size_t)i);
+  }
+  return PBHC_OK;
+}

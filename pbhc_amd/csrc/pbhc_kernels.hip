@@ -238,6 +238,113 @@ __global__ __launch_bounds__(PBHC_G * DOF_FAR_EPB) void k_dof_far_any(const long
 }
 
 // =================================================================================================
+//  k_record_motion: one frame of the evaluation recorder (env.config.save_motion; motion_tracking.py:861-938 keeps twelve python lists of
+//  .cpu() copies and a scipy call per control step).  Launched right after k_env_step, only when the recorder is on; it copies the step's
+//  post-reset state into [N, T, ...] buffers whose frame index comes from a device-side counter, so a captured graph replays it.
+//  Layout: env n's T frames of a key are contiguous (what the reference's stack + transpose(0, 1) produces), i.e. a step writes N rows of
+//  `row` floats with a stride of T * row.  Mapping: the frame of one env is W = 546 words (v1 / 23 dof: actor_obs 380, pose_aa 81, dof,
+//  dof_vel, action 23 each, root 13, contacts 2, one scalar slot); ONE WORD PER LANE-ITEM over the flat index env * W + j, REC_ITEMS items
+//  per thread a block apart.  Consecutive lanes hold consecutive words of one destination row and run on into the env's next key, so a
+//  wave store is 64 dwords in one or two contiguous segments (one 256-B segment inside an actor_obs row of 1520 B) and the sources — [N, row]
+//  tensors — are read coalesced; every thread issues the loads of all its items before its first store, and with ~2 k workgroups at 4096
+//  envs the latency of the short rows is hidden by occupancy instead of by a loop (a first version — 8 envs per workgroup, key after key —
+//  was a chain of ~25 dependent round trips per wave: 0.9 TB/s).  Offsets are 64-bit: N * T * row passes 2^31 bytes.
+//  The counter: every workgroup reads it first; the LAST one to finish advances it.  "Last" is a two-level arrival ticket — PBHC_REC_SHARDS
+//  shard words on lines of their own, then one top word — because ~25 ns per same-address atomic made a single ticket word the whole cost
+//  of the kernel (124 us at 32 768 envs with 4096 workgroups, measured).
+// =================================================================================================
+#define REC_TPB 256
+#define REC_ITEMS 4
+struct RecSrc {
+  const float* root; const float* dof_state; const float* actions; const float* contacts_filt; const float* origins; const float* start;
+  const float* obs; const long long* ep_len; const long long* reset;
+  int obs_pitch, obs_dim;
+};
+__global__ __launch_bounds__(REC_TPB) void k_record_motion(RecSrc s, PbhcRecordIO r, const PbhcEnvConfig* __restrict__ cfgp, int N, int D, int Bx, float dt) {
+  __shared__ int s_cnt, s_last;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_cnt = __hip_atomic_load(r.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const int cnt = s_cnt, T = r.total_steps;
+  const int f = cnt - 3;                                    // the reference drops its first three records (v[3:])
+  if (f >= 0 && f < T) {
+    const int prow = Bx * 3;
+    const int W = s.obs_dim + prow + 3 * D + 16;            // + root_rot 4, root_trans_offset / lin vel / ang vel 3 each, contact 2, scalars 1
+    const unsigned total = (unsigned)N * (unsigned)W;       // (< 2^31: checked by pbhc_record_motion; only the DESTINATION offsets need 64 bits)
+    const unsigned base = blockIdx.x * (unsigned)(REC_TPB * REC_ITEMS) + tid;
+    int env0 = (int)(base / (unsigned)W), j0 = (int)(base - (unsigned)env0 * (unsigned)W);      // one division per thread, then steps of REC_TPB
+    float* dst[REC_ITEMS];
+    float val[REC_ITEMS];
+    long long term = 0;
+    long long* dst_term = nullptr;
+#pragma unroll
+    for (int it = 0; it < REC_ITEMS; ++it) {
+      const unsigned i = base + (unsigned)it * REC_TPB;
+      dst[it] = nullptr;
+      val[it] = 0.0f;
+      const int env = env0;
+      int j = j0;
+      j0 += REC_TPB;
+      while (j0 >= W) { j0 -= W; ++env0; }
+      if (i >= total) continue;
+      const size_t ef = (size_t)env * (size_t)T + (size_t)f;  // row index of (env, frame) in every [N, T, row] buffer
+      const float* root = s.root + (size_t)env * 13;
+      if (j < s.obs_dim) { dst[it] = r.actor_obs + ef * s.obs_dim + j; val[it] = s.obs[(size_t)env * s.obs_pitch + j]; continue; }
+      j -= s.obs_dim;
+      if (j < prow) {
+        const int b = j / 3, a = j - 3 * b;
+        float v = 0.0f;
+        if (b == 0) {
+          float rv[3];
+          rotvec_from_quat<float>(root[3], root[4], root[5], root[6], rv);
+          v = a == 0 ? rv[0] : (a == 1 ? rv[1] : rv[2]);
+        } else if (b <= D) {
+          v = cfgp->skel.dof_axis[b - 1][a] * s.dof_state[((size_t)env * D + (b - 1)) * 2];
+        }
+        dst[it] = r.pose_aa + ef * prow + j; val[it] = v; continue;
+      }
+      j -= prow;
+      if (j < D) { dst[it] = r.dof + ef * D + j; val[it] = s.dof_state[((size_t)env * D + j) * 2]; continue; }
+      j -= D;
+      if (j < D) { dst[it] = r.dof_vel + ef * D + j; val[it] = s.dof_state[((size_t)env * D + j) * 2 + 1]; continue; }
+      j -= D;
+      if (j < D) { dst[it] = r.action + ef * D + j; val[it] = s.actions[(size_t)env * D + j]; continue; }
+      j -= D;
+      if (j < 4) { dst[it] = r.root_rot + ef * 4 + j; val[it] = root[3 + j]; continue; }
+      j -= 4;
+      if (j < 3) { dst[it] = r.root_trans_offset + ef * 3 + j; val[it] = root[j] - s.origins[(size_t)env * 3 + j]; continue; }
+      j -= 3;
+      if (j < 3) { dst[it] = r.root_lin_vel + ef * 3 + j; val[it] = root[7 + j]; continue; }
+      j -= 3;
+      if (j < 3) { dst[it] = r.root_ang_vel + ef * 3 + j; val[it] = root[10 + j]; continue; }
+      j -= 3;
+      if (j < 2) { dst[it] = r.contact_mask + ef * 2 + j; val[it] = s.contacts_filt[(size_t)env * 2 + j]; continue; }
+      // the scalar slot: motion_times here, terminate (int64) beside it
+      dst[it] = r.motion_times + ef; val[it] = (float)s.ep_len[env] * dt + s.start[env];
+      dst_term = (long long*)r.terminate + ef; term = s.reset[env];
+    }
+#pragma unroll
+    for (int it = 0; it < REC_ITEMS; ++it)
+      if (dst[it]) *dst[it] = val[it];
+    if (dst_term) *dst_term = term;
+  }
+  // every workgroup has read the counter (above, before its barrier) by the time it arrives here: the last arrival advances it
+  if (tid == 0) {
+    const int nb = (int)gridDim.x, shard = (int)blockIdx.x % PBHC_REC_SHARDS;
+    const int in_shard = (nb - shard + PBHC_REC_SHARDS - 1) / PBHC_REC_SHARDS, shards = nb < PBHC_REC_SHARDS ? nb : PBHC_REC_SHARDS;
+    int last = 0;
+    if (__hip_atomic_fetch_add(r.counter + 32 * (2 + shard), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_shard - 1)
+      last = __hip_atomic_fetch_add(r.counter + 32, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == shards - 1;
+    s_last = last;
+  }
+  __syncthreads();
+  if (s_last) {                                             // tickets back to zero for the next launch, then the counter itself
+    for (int k = tid; k < PBHC_REC_SHARDS + 1; k += REC_TPB) __hip_atomic_store(r.counter + 32 * (1 + k), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store(r.counter, cnt < T + 3 ? cnt + 1 : cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// =================================================================================================
 //  standalone kernels: sim FK, motion state, load-time motion build
 // =================================================================================================
 __global__ __launch_bounds__(PBHC_G* PBHC_EPB) void k_sim_fk(PbhcSkeleton sk, const float* __restrict__ root_states, const float* __restrict__ dof_pos,
@@ -544,6 +651,7 @@ int pbhc_debug_read_wg_times(unsigned long long* out, int num_workgroups) {
 const char* pbhc_last_error(void) { return g_err; }
 int pbhc_sizeof_env_config(void) { return (int)sizeof(PbhcEnvConfig); }
 int pbhc_sizeof_step_io(void) { return (int)sizeof(PbhcStepIO); }
+int pbhc_sizeof_record_io(void) { return (int)sizeof(PbhcRecordIO); }
 
 static int check_skel(const PbhcSkeleton* sk) {
   ARG_CHECK(sk != nullptr);
@@ -989,6 +1097,31 @@ int pbhc_env_step_finish(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
   ARG_CHECK(e && io && io->frame_cursor && io->num_frames >= 1);
   hipLaunchKernelGGL(k_env_finalize, dim3(1), dim3(64 * PBHC_FIN_CHUNKS), 0, (hipStream_t)stream, e->d_cfg, e->d_glob, e->d_partials, 2 * e->nblocks, io->frame_cursor,
                      io->num_frames, (const double*)nullptr, io->totals_out, 0.0);
+  HIP_CHECK(hipGetLastError());
+  return PBHC_OK;
+}
+
+// the evaluation recorder's frame of the step just launched on `stream` (k_record_motion)
+int pbhc_record_motion(PbhcEnv* e, const PbhcStepIO* io, const PbhcRecordIO* rec, void* stream) {
+  ARG_CHECK(e && io && rec);
+  ARG_CHECK(e->cfg.tracking_mode == 0);            // the reference's general-tracking env has no recorder
+  ARG_CHECK(rec->total_steps >= 1 && rec->obs_group >= 0 && rec->obs_group < e->cfg.num_groups && rec->counter);
+  ARG_CHECK(rec->root_trans_offset && rec->root_rot && rec->root_lin_vel && rec->root_ang_vel && rec->dof && rec->dof_vel && rec->contact_mask);
+  ARG_CHECK(rec->pose_aa && rec->action && rec->actor_obs && rec->terminate && rec->motion_times);
+  ARG_CHECK(io->root_states && io->dof_state && io->actions && io->contacts_filt && io->env_origins && io->motion_start_times);
+  ARG_CHECK(io->episode_length_buf && io->reset_buf && io->obs[rec->obs_group]);
+  const int g = rec->obs_group, N = e->cfg.num_envs;
+  RecSrc s;
+  s.root = io->root_states; s.dof_state = io->dof_state; s.actions = io->actions; s.contacts_filt = io->contacts_filt;
+  s.origins = io->env_origins; s.start = io->motion_start_times; s.obs = io->obs[g];
+  s.ep_len = (const long long*)io->episode_length_buf; s.reset = (const long long*)io->reset_buf;
+  s.obs_dim = e->cfg.groups[g].dim;
+  s.obs_pitch = io->obs_pitch[g] ? io->obs_pitch[g] : e->cfg.groups[g].pitch;
+  ARG_CHECK((uint64_t)N * (uint64_t)(s.obs_dim + 3 * e->cfg.skel.num_bodies_ext + 3 * e->cfg.skel.num_dof + 16) < (1ull << 31) - REC_TPB * REC_ITEMS);   // 32-bit item index
+  const size_t items = (size_t)N * (size_t)(s.obs_dim + 3 * e->cfg.skel.num_bodies_ext + 3 * e->cfg.skel.num_dof + 16);
+  const size_t per_block = (size_t)REC_TPB * REC_ITEMS;
+  hipLaunchKernelGGL(k_record_motion, dim3((unsigned)((items + per_block - 1) / per_block)), dim3(REC_TPB), 0, (hipStream_t)stream, s, *rec, (const PbhcEnvConfig*)e->d_cfg, N,
+                     e->cfg.skel.num_dof, e->cfg.skel.num_bodies_ext, e->cfg.dt);
   HIP_CHECK(hipGetLastError());
   return PBHC_OK;
 }

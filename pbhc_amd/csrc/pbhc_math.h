@@ -314,4 +314,26 @@ __device__ __forceinline__ float rng_uniform(uint64_t seed, uint32_t env, uint32
   return u01(o[idx & 3]);
 }
 
+// Rotation vector of an xyzw quaternion as scipy's Rotation.from_quat(q).as_rotvec() forms it (the recorder's pose_aa row 0,
+// motion_tracking.py:902): normalise by the 4-norm, take the canonical sign (w >= 0) so that the angle 2 atan2(|v|, w) lies in [0, pi], then
+// v * angle / sin(angle / 2), with scipy's series 2 + angle^2 / 12 + 7 angle^4 / 2880 for angle <= 1e-3.  One template for the kernel
+// (float) and the host-side check against scipy (double, pbhc_debug_rotvec_host).
+template <typename T>
+__host__ __device__ __forceinline__ void rotvec_from_quat(T x, T y, T z, T w, T out[3]) {
+  T n;
+  if constexpr (sizeof(T) == 4) n = sqrtf(x * x + y * y + z * z + w * w); else n = sqrt(x * x + y * y + z * z + w * w);
+  x = x / n; y = y / n; z = z / n; w = w / n;
+  // scipy's canonical sign: w > 0, and at w == 0 (angle pi, where q and -q give opposite vectors) the first non-zero of x, y, z positive
+  if (w < (T)0 || (w == (T)0 && (x < (T)0 || (x == (T)0 && (y < (T)0 || (y == (T)0 && z < (T)0)))))) { x = -x; y = -y; z = -z; w = -w; }
+  T angle, scale;
+  if constexpr (sizeof(T) == 4) angle = 2.0f * atan2f(sqrtf(x * x + y * y + z * z), w); else angle = 2.0 * atan2(sqrt(x * x + y * y + z * z), w);
+  if (angle <= (T)1e-3) {
+    const T a2 = angle * angle;
+    scale = (T)2 + a2 / (T)12 + (T)7 * a2 * a2 / (T)2880;
+  } else {
+    if constexpr (sizeof(T) == 4) scale = angle / sinf(angle / 2.0f); else scale = angle / sin(angle / 2.0);
+  }
+  out[0] = scale * x; out[1] = scale * y; out[2] = scale * z;
+}
+
 }  // namespace pbhc

@@ -725,4 +725,34 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     g[K["PBHC_G_SOFT_TAU_VAL"]] = float(lc.soft_torque_initial_limit)
     g[K["PBHC_G_NOISE_CURRICULUM"]] = float(ob.noise_initial_value) if ob.get("add_noise_currculum", False) else 1.0
     L.globals0 = g
+    L.record = record_layout(ec, L, D, Bx, mode)
     return c, L
+
+
+RECORD_KEYS = ("root_trans_offset", "pose_aa", "dof", "root_rot", "actor_obs", "action", "terminate", "root_lin_vel", "root_ang_vel", "dof_vel",
+               "contact_mask", "motion_times")
+
+
+def record_layout(ec, L, D, Bx, mode):
+    """env.config.save_motion (opt/record.yaml; motion_tracking.py:140-170): the evaluation recorder's part of the layout, or None when the
+    key is absent or false.  It stays out of PbhcEnvConfig on purpose — the step kernel and its specialised builds are baked from that
+    struct and must not change with the recorder.  `rows`: per key the trailing shape of one frame ([N, T, *rows[key]] buffers)."""
+    if not ec.get("save_motion", False):
+        return None
+    if mode == 1:
+        # general_tracking.py's class derives from LeggedRobotBase, not from LeggedRobotMotionTracking: it has no _init_save_motion and
+        # never reads the key
+        raise NotImplementedError("env.config.save_motion: LeggedRobotGeneralTracking has no recorder in the reference (only "
+                                  "LeggedRobotMotionTracking records); it would be ignored there — refused here instead")
+    if "dump_motion_name" in ec:
+        raise NotImplementedError("env.config.dump_motion_name (motion_tracking.py:154-155 raises on it as well)")
+    T = int(ec.save_total_steps)
+    if T < 1:
+        raise _lib.PbhcError(f"env.config.save_total_steps must be >= 1, got {T}")
+    if "actor_obs" not in L.group_names[:-1]:
+        raise _lib.PbhcError("env.config.save_motion records obs group 'actor_obs', which this config does not have")
+    obs_dim = L.group_dims["actor_obs"]
+    rows = dict(root_trans_offset=(3,), pose_aa=(Bx, 3), dof=(D,), root_rot=(4,), actor_obs=(obs_dim,), action=(D,), terminate=(),
+                root_lin_vel=(3,), root_ang_vel=(3,), dof_vel=(D,), contact_mask=(2,), motion_times=())
+    return dict(total_steps=T, obs_group=L.group_names.index("actor_obs"), rows=rows, save_note=ec.get("save_note", None),
+                eval_timestamp=ec.get("eval_timestamp", None), ckpt_dir=ec.get("ckpt_dir", None))

@@ -9,6 +9,8 @@ Same quantities, names, units and aggregation as the reference's offline tools:
                             (+ E_contact_acc when both sides carry a contact mask);
   * `eval_smoothness`     = measure_traj.py:224-287: L2 norms of the finite-difference velocity / acceleration / jerk of bodies and joints;
   * `eval_batch_traj`     = sample_eps.py:21-97 / ratio_eps.py: per-episode metrics x 1e3 with per-frame differences, mean and std over episodes;
+  * `eval_batch_traj_device` = the same table from the env recorder's device-resident [N, T, ...] buffers: ONE batched FK launch set
+                            (`pbhc_motion_build_batch`, one clip per episode) and batched tensor code instead of a Python loop over episodes;
   * `first_termination_ratio` = ratio_eps.py (`calculate_average_first_one`): mean index of the first termination flag and its share of
                             the episode length.
 The metric arithmetic is plain tensor code (any device); only the FK needs the GPU library (there is no CPU FK in the product).
@@ -155,6 +157,80 @@ def eval_batch_traj(skeleton, saved_motion_dict, ref_motion, motion_len=None, de
             arr = np.array([total["_raw"][i][part][key] for i in range(N)])
             agg[key] = {"mean": float(np.mean(arr)), "std": float(np.std(arr))}
         total[part] = agg
+    return total
+
+
+def _mean_norm_rows(x):
+    """`_mean_norm` of every episode of a batch: x [N, T', ..., C] -> [N]"""
+    n = torch.norm(x, dim=-1)
+    while n.dim() > 1:
+        n = n.mean(dim=-1)
+    return n
+
+
+def eval_batch_traj_device(skeleton, recorded, ref_motion, motion_len=None):
+    """`eval_batch_traj` for a recording that is still on the device (env.recorded_motion_device(): dof, pose_aa, root_trans_offset,
+    motion_times, contact_mask, ... as [N, T, ...] tensors): the FK of all N x T frames is one `pbhc_motion_build_batch` call — one clip per
+    episode, so velocities and the filter stop at episode boundaries — and accuracy / smoothness of all episodes are evaluated together.
+    Same nested dict as `eval_batch_traj` (same fp32 arithmetic per element; only the order of the means' sums differs); one device -> host
+    copy of the [metrics, N] table at the end."""
+    import ctypes as C
+
+    from .. import _lib
+
+    dof = recorded["dof"]
+    N, L = dof.shape[0], dof.shape[1]
+    if motion_len is not None:
+        assert L == motion_len, f"Motion length {L} does not match the expected length {motion_len}"
+    dev = dof.device
+    D, Bx, B = skeleton.num_dof, skeleton.num_bodies_ext, skeleton.num_bodies
+    row = 2 * D + 2 + 13 * Bx
+    f32 = lambda t, *shape: t.to(torch.float32).reshape(*shape).contiguous()
+    pose, trans = f32(recorded["pose_aa"], N * L, -1, 3)[:, :Bx].contiguous(), f32(recorded["root_trans_offset"], N * L, 3)
+    contact = f32(recorded["contact_mask"], N * L, 2) if "contact_mask" in recorded else None
+    frame_clip = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(L).contiguous()
+    clip_start = (torch.arange(N + 1, dtype=torch.int32, device=dev) * L).contiguous()
+    clip_dt = torch.full((N,), 1.0 / 50, dtype=torch.float32, device=dev)                      # fps 50, as eval_batch_traj (sample_eps.py:40)
+    rows = torch.empty(N * L, row, device=dev)
+    scratch = torch.empty(N * L * Bx * 14, device=dev)
+    csk = skeleton.to_c()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pbhc_motion_build_batch(C.byref(csk), pose.data_ptr(), trans.data_ptr(), _lib.ptr(contact), N * L, N, frame_clip.data_ptr(),
+                                                      clip_start.data_ptr(), clip_dt.data_ptr(), rows.data_ptr(), scratch.data_ptr(), _lib.current_stream()),
+                   "pbhc_motion_build_batch")
+    o = 2 * D + 2
+    pg = rows[:, o:o + 3 * Bx].view(N, L, Bx, 3)[:, :, :B]
+    pq = rows[:, :D].view(N, L, D)
+    # the reference blends once, at episode 0's time stamps (sample_eps.py:47-48)
+    ref = blend_motion(trajectory_tables(skeleton, ref_motion, dev), recorded["motion_times"][0].to(torch.float32).reshape(-1))
+    rg, rq = ref["global_translation"][None], ref["dof_pos"][None]
+    d = lambda x: x[:, 1:] - x[:, :-1]                                                         # per-frame differences (delta_per_frame)
+    acc = {"E_gmpbpe": _mean_norm_rows(pg - rg), "E_mpbpe": _mean_norm_rows((pg - pg[..., 0:1, :]) - (rg - rg[..., 0:1, :])),
+           "E_mpjpe": _mean_norm_rows(pq - rq)}
+    pdv, rdv = d(pq), d(rq)
+    acc["E_mpjve"] = _mean_norm_rows(pdv - rdv)
+    acc["E_mpjae"] = _mean_norm_rows(d(pdv) - d(rdv))
+    pv, rv = d(pg), d(rg)
+    pa, ra = d(pv), d(rv)
+    acc["E_pbve"] = _mean_norm_rows(pv - rv)
+    acc["E_pbae"] = _mean_norm_rows(pa - ra)
+    acc["E_root_acc"] = _mean_norm_rows(pa[..., 0:1, :] - ra[..., 0:1, :])
+    acc["E_root_vel"] = _mean_norm_rows(pv[..., 0:1, :] - rv[..., 0:1, :])
+    if contact is not None and "contact_mask" in ref:
+        acc["E_contact_acc"] = torch.mean((contact.view(N, L, 2) - ref["contact_mask"][None]).abs(), dim=-1).mean(dim=-1)
+    smooth = {}
+    for tag, g, q in (("", pg, pq), ("ref_", rg, rq)):
+        v = d(g); a = d(v); j = d(a)
+        dv = d(q); da = d(dv); dj = d(da)
+        for name, x in (("vel", v), ("acc", a), ("jerk", j), ("dof_vel", dv), ("dof_acc", da), ("dof_jerk", dj)):
+            smooth[f"L2_{tag}{name}"] = _mean_norm_rows(x).expand(N)
+    names = [("accuracy", k) for k in acc] + [("smoothness", k) for k in smooth]
+    table = torch.stack([acc[k] for k in acc] + [smooth[k] for k in smooth]).to(torch.float64).cpu().numpy() * 1e3     # [metrics, N]
+    total = {"_raw": [{"accuracy": {}, "smoothness": {}} for _ in range(N)], "accuracy": {}, "smoothness": {}}
+    for (part, key), vals in zip(names, table):
+        for i in range(N):
+            total["_raw"][i][part][key] = float(vals[i])
+        total[part][key] = {"mean": float(np.mean(vals)), "std": float(np.std(vals))}
     return total
 
 

@@ -1,0 +1,148 @@
+"""env.config.save_motion (the evaluation recorder, opt/record.yaml) at the config level, and the recorder's rotation-vector routine against
+scipy's Rotation.as_rotvec — no GPU."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+from scipy.spatial.transform import Rotation
+
+from pbhc_amd import _lib
+from pbhc_amd.envs import env_config
+from pbhc_amd.envs.motion_tracking import _TopView
+from pbhc_amd.skeleton import Skeleton
+from pbhc_amd.utils.config import load_config
+from tests.helpers import GOLDEN
+
+RECORD = {"env.config.save_motion": True, "env.config.save_total_steps": 8, "env.config.save_note": "note", "env.config.eval_timestamp": "stamp",
+          "env.config.ckpt_dir": "/nonexistent"}
+# pose_aa row 0 against scipy in float64.  ROTVEC_FP32_MEASURED: the largest deviation of the straightforward float evaluation
+# (pbhc_math.h rotvec_from_quat<float>, host build) from scipy on the golden recording's quaternions and the edge cases below, as measured
+# by test_rotvec_float_error_bound (it prints the figure); ROTVEC_TOL = 4 x that, the margin the GPU's own atan2f / sqrtf / sinf rounding
+# gets (tests/test_gpu_record.py applies it to the kernel's output).
+ROTVEC_FP32_MEASURED = 2.7e-7          # measured 2.615e-07 (1.1 ulp of pi in float), rounded up
+ROTVEC_TOL = 4 * ROTVEC_FP32_MEASURED
+
+
+class _ML:
+    has_contact_mask = False
+
+
+def _build(cfgname, overrides, mode):
+    cfg = load_config(os.path.join(GOLDEN, "configs", cfgname), dict({"num_envs": 64, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"},
+                                                                     **overrides), now="t")
+    skel = Skeleton.from_motion_config(cfg.robot.motion)
+    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
+    return cfg, skel, env_config.build(_TopView(cfg.env.config), skel, _ML(), 64, "cpu", nl, seed=1, mode=mode)
+
+
+def test_save_motion_yields_the_recorder_layout():
+    cfg, skel, (c, L) = _build("v1_g1_23dof_walk.yaml", RECORD, 0)
+    R = L.record
+    D, Bx = skel.num_dof, skel.num_bodies_ext
+    assert R["total_steps"] == 8 and L.group_names[R["obs_group"]] == "actor_obs"
+    assert set(R["rows"]) == set(env_config.RECORD_KEYS)
+    assert R["rows"] == dict(root_trans_offset=(3,), pose_aa=(Bx, 3), dof=(D,), root_rot=(4,), actor_obs=(L.group_dims["actor_obs"],), action=(D,),
+                             terminate=(), root_lin_vel=(3,), root_ang_vel=(3,), dof_vel=(D,), contact_mask=(2,), motion_times=())
+    assert (R["save_note"], R["eval_timestamp"], R["ckpt_dir"]) == ("note", "stamp", "/nonexistent")
+    # every key of PbhcRecordIO that is a buffer has a row, and the library agrees on the struct
+    fields = {f[0] for f in _lib.PbhcRecordIO._fields_}
+    assert fields == set(R["rows"]) | {"total_steps", "obs_group", "counter"}
+    assert _lib.lib().pbhc_sizeof_record_io() == C.sizeof(_lib.PbhcRecordIO)
+
+
+def test_dump_motion_name_is_refused():
+    with pytest.raises(NotImplementedError, match="dump_motion_name"):
+        _build("v1_g1_23dof_walk.yaml", dict(RECORD, **{"env.config.dump_motion_name": "x"}), 0)
+
+
+def test_general_tracking_refuses_save_motion():
+    with pytest.raises(NotImplementedError, match="LeggedRobotGeneralTracking has no recorder"):
+        _build("v2_g1_23dof_student.yaml", RECORD, 1)
+    _, _, (c, L) = _build("v2_g1_23dof_student.yaml", {"env.config.save_motion": False}, 1)
+    assert L.record is None
+
+
+@pytest.mark.parametrize("overrides", [{}, {"env.config.save_motion": False}, RECORD], ids=["absent", "false", "true"])
+def test_config_struct_does_not_change_with_the_recorder(overrides):
+    """the struct the specialised step kernel is baked from: byte for byte that of the same config without the key (the recorder lives in the
+    layout and in PbhcRecordIO only); and no layout when the key is absent or false"""
+    _, _, (c0, L0) = _build("v1_g1_23dof_walk.yaml", {}, 0)
+    _, _, (c1, L1) = _build("v1_g1_23dof_walk.yaml", overrides, 0)
+
+    assert _struct_bytes_without_pointers(c0) == _struct_bytes_without_pointers(c1)
+    assert np.array_equal(L0.globals0, L1.globals0)
+    assert (L1.record is None) == (not overrides.get("env.config.save_motion", False))
+
+
+def _struct_bytes_without_pointers(s):
+    """bytes of a ctypes struct with every pointer field (addresses of host-built map tensors, different in every build) zeroed, recursively"""
+    out = bytearray()
+
+    def walk(v, ct):
+        if issubclass(ct, C.Structure):
+            for name, ft in ct._fields_:
+                walk(getattr(v, name), ft)
+        elif issubclass(ct, C.Array):
+            if issubclass(ct._type_, (C.Structure, C.Array)) or ct._type_ is C.c_void_p:
+                for i in range(ct._length_):
+                    walk(v[i], ct._type_)
+            else:
+                out.extend(bytes(v))
+        elif ct is C.c_void_p:
+            out.extend(b"\0" * 8)
+        else:
+            out.extend(bytes(ct(v)))
+
+    walk(s, type(s))
+    return bytes(out)
+
+
+# ---- the rotation vector ---------------------------------------------------------------------------------------------------------------
+def _edge_quaternions():
+    qs = [[0, 0, 0, 1.0], [0, 0, 0, -1.0], [1.0, 0, 0, 0], [0, 0, 1.0, 0], [0, -1.0, 0, 0],                    # identity (both signs), angle pi
+          [0.6, 0, 0, -0.8], [-0.1, 0.2, 0.3, -0.9], [0.5, 0.5, 0.5, -0.5]]                                      # w < 0
+    for ang in (1e-3, 1.0000001e-3, 9.99e-4, 1e-4, 3e-5, 1e-6, 1e-8, 1e-12):                                      # around and below the series switch
+        for axis in ([1.0, 0, 0], [0.3, -0.5, 0.81]):
+            a = np.array(axis) / np.linalg.norm(axis)
+            for sign in (1.0, -1.0):
+                qs.append(list(sign * np.concatenate([a * np.sin(ang / 2), [np.cos(ang / 2)]])))
+    for ang in (np.pi - 1e-4, np.pi - 1e-7, 3.0, 2.0):                                                            # near pi
+        qs.append([0, np.sin(ang / 2), 0, np.cos(ang / 2)])
+        qs.append([0, -np.sin(ang / 2), 0, -np.cos(ang / 2)])
+    return np.array(qs, dtype=np.float64)
+
+
+def _golden_quaternions():
+    g = np.load(f"{GOLDEN}/env_v1_walk_record.npz")
+    return np.concatenate([g["saved__root_rot"].reshape(-1, 4), g["replay_root"][..., 3:7].reshape(-1, 4)]).astype(np.float64)
+
+
+def _rotvec(q):
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    o64, o32 = np.zeros((len(q), 3)), np.zeros((len(q), 3), np.float32)
+    _lib.check(_lib.lib().pbhc_debug_rotvec_host(q.ctypes.data, len(q), o64.ctypes.data, o32.ctypes.data), "pbhc_debug_rotvec_host")
+    return o64, o32
+
+
+def test_rotvec_equals_scipy_in_float64():
+    """the kernel's routine (one template, instantiated for double on the host) against Rotation.as_rotvec: the same operations in the same
+    order, so equal to the last bit up to the libm behind each — a bound of 4 ulp of pi covers atan2 / sin differing by an ulp"""
+    gq = _golden_quaternions()
+    assert (gq[:, 3] < 0).any(), "the golden recording must hold a quaternion with w < 0"
+    for q in (_edge_quaternions(), gq):
+        o64, _ = _rotvec(q)
+        ref = Rotation.from_quat(q).as_rotvec()
+        assert np.abs(o64 - ref).max() <= 4 * np.spacing(np.pi), np.abs(o64 - ref).max()
+        ang = np.linalg.norm(o64, axis=1)
+        assert (ang <= np.pi + 1e-12).all()
+
+
+def test_rotvec_float_error_bound():
+    """the straightforward float evaluation against scipy float64 on the same (float-valued) quaternions: the measured figure behind ROTVEC_TOL"""
+    q = np.concatenate([_edge_quaternions(), _golden_quaternions()]).astype(np.float32).astype(np.float64)
+    _, o32 = _rotvec(q)
+    ref = Rotation.from_quat(q).as_rotvec()
+    err = np.abs(o32.astype(np.float64) - ref).max()
+    print(f"rotvec float vs scipy float64: max abs deviation {err:.3e} over {len(q)} quaternions (ROTVEC_FP32_MEASURED {ROTVEC_FP32_MEASURED:.1e})")
+    assert err <= ROTVEC_FP32_MEASURED
