@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define PBHC_ABI_VERSION 14
+#define PBHC_ABI_VERSION 15
 
 #define PBHC_OK 0
 #define PBHC_EINVAL (-22)   /* bad argument / size over a compile-time maximum */
@@ -102,6 +102,10 @@ enum PbhcRewardTerm {
   PBHC_R_FEET_HEADING_ALIGNMENT_CONTACT,
   PBHC_R_PENALTY_FEET_ORI,
   PBHC_R_PENALTY_FEET_ORI_CONTACT,
+  /* motion_tracking.py:78-94,1238-1244,1286-1292 (v1 env only): radial_velocity_potential of the flattened body / joint velocities,
+   * exp(-(1 - cos) / 0.75) r exp(0.4 (1 - r^2.5)), r = |cur| / |ref|; no sigma.  |ref| = 0 gives NaN, as there (inf x 0) */
+  PBHC_R_TELEOP_RADIAL_BODY_VELOCITY_EXTEND,
+  PBHC_R_TELEOP_RADIAL_JOINT_VELOCITY,
   PBHC_R_NUM_TERMS
 };
 
@@ -132,6 +136,11 @@ enum PbhcFeature {
    * PBHC_F_BASE_ANG_VEL / PBHC_F_PROJECTED_GRAVITY rotated by the Ornstein-Uhlenbeck-perturbed base orientation.  (Appended, so that every
    * other id keeps its value; with the process off the two names read the clean slots instead.) */
   PBHC_F_BASE_ANG_VEL_NOISE, PBHC_F_PROJECTED_GRAVITY_NOISE,
+  /* a constant one (indicator_guider); the feet rows of the contact forces [F,3] (feet_contact_force, legged_robot_base.py:1117-1118);
+   * local_ref_rigid_body_pos_relyaw [Bx,3]: the reference body VELOCITIES rotated by the inverse of the relative yaw (motion_tracking.py:
+   * 720-721 — not positions, whatever the name says); the v1 look-ahead joint rows [S,D] at (episode_length + 1 + i) dt + start
+   * (motion_tracking.py:562-599), pre-reset values */
+  PBHC_F_ONE, PBHC_F_FEET_CONTACT_FORCE, PBHC_F_REF_VEL_RELYAW, PBHC_F_FUT_REF_DOF_POS, PBHC_F_FUT_REF_DOF_VEL,
   PBHC_F_NUM
 };
 
@@ -342,6 +351,10 @@ typedef struct PbhcEnvConfig {
   float ps_pd_ratio[2];
   int32_t ps_tau, ps_tau_num, ps_tau_slot[PBHC_MAX_DOF];
   float ps_tau_rao_lim, ps_tau_rfi_lim;
+  /* which of the optional features an observation reads (the step computes no other): bit 0 PBHC_F_ONE, bit 1 PBHC_F_FEET_CONTACT_FORCE,
+   * bit 2 PBHC_F_REF_VEL_RELYAW (needs PBHC_F_RELYAW in the row).  future_ref_steps: obs.future_ref_steps when PBHC_F_FUT_REF_DOF_* are
+   * read, else 0 (tracking_mode 0).  radial_terms: bit 0 / bit 1 the body / joint radial-velocity term is configured. */
+  int32_t obs_extra, future_ref_steps, radial_terms, pad5_;
   int32_t pad2_;
   uint64_t seed;
 } PbhcEnvConfig;

@@ -57,7 +57,9 @@ enum {
   R_KEYN, R_LKEYN, R_LUPN, R_LLON, R_LVRN, R_BODYZ,                 // general tracking: log norms, body_z flag
   R_EXP0,                                  // [PBHC_NUM_SIGMA] exp(-err_k / sigma_k)
   R_FOOT0 = R_EXP0 + PBHC_NUM_SIGMA,       // per foot f: +4f: |F|, |F_xy|, F_z, |v|   (+8: |v_xy| x2; +10: |heading - root heading| x2; +12: |gravity_xy| in the foot frame x2)
-  R_NUM = R_FOOT0 + 14
+  R_RADB = R_FOOT0 + 14,                   // radial-velocity terms: cosine similarity, |cur| / |ref| of the flattened body velocities ...
+  R_RADJ = R_RADB + 2,                     // ... and of the joint velocities
+  R_NUM = R_RADJ + 2
 };
 static_assert(R_NUM <= 80, "RED region");
 
@@ -598,6 +600,14 @@ __device__ __forceinline__ f4 quat_from_euler_xyz(f3 rpy) {
   return mk4(cy * sr * cp - sy * cr * sp, cy * cr * sp + sy * sr * cp, sy * cr * cp - cy * sr * sp, cy * cr * cp + sy * sr * sp);
 }
 
+// radial_velocity_potential's two inputs (motion_tracking.py:80,86-88) from the three sums cur . ref, |cur|^2, |ref|^2: torch's
+// cosine_similarity (each norm clamped at eps = 1e-8) and the unguarded norm ratio
+__device__ __forceinline__ void radial_cos_ratio(float dot, float cc, float rr, float* out) {
+  const float nc = sqrtf(cc), nr = sqrtf(rr);
+  out[0] = dot / (fmaxf(nc, 1e-8f) * fmaxf(nr, 1e-8f));
+  out[1] = nc / nr;
+}
+
 // =================================================================================================
 //  k_env_step: LeggedRobotBase.step (legged_robot_base.py:239-338) for LeggedRobotMotionTracking
 // =================================================================================================
@@ -722,7 +732,8 @@ __device__ __forceinline__ bool is_special_term(int id) {     // the reward term
   return id == PBHC_R_TELEOP_CONTACT_MASK || id == PBHC_R_TELEOP_CONTACT_MASK_V2 || id == PBHC_R_TELEOP_BODY_POSITION_EXTEND || id == PBHC_R_PENALTY_ORIENTATION ||
          id == PBHC_R_FEET_AIR_TIME || id == PBHC_R_PENALTY_FEET_CONTACT_FORCES || id == PBHC_R_PENALTY_STUMBLE || id == PBHC_R_PENALTY_SLIPPAGE ||
          id == PBHC_R_FOOT_SLIP_PENALTY || id == PBHC_R_ALIVE || id == PBHC_R_FEET_HEADING_ALIGNMENT || id == PBHC_R_FEET_HEADING_ALIGNMENT_CONTACT ||
-         id == PBHC_R_PENALTY_FEET_ORI || id == PBHC_R_PENALTY_FEET_ORI_CONTACT;
+         id == PBHC_R_PENALTY_FEET_ORI || id == PBHC_R_PENALTY_FEET_ORI_CONTACT || id == PBHC_R_TELEOP_RADIAL_BODY_VELOCITY_EXTEND ||
+         id == PBHC_R_TELEOP_RADIAL_JOINT_VELOCITY;
 }
 constexpr bool obs_runs_complete(const PbhcEnvConfig& c) {
   for (int g = 0; g < c.num_groups; ++g)
@@ -1101,6 +1112,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   const u32 qoff = (u32)envc * (u32)(Q * D) + (u32)dc;
   // reductions of the two roles (role A: body sums, role B: joint-space sums); declared here, reduced after their loops
   float s_up = 0, s_lo = 0, s_vr = 0, s_feet = 0, s_rot = 0, s_vel = 0, s_ang = 0, s_maxn = 0, s_upn = 0, s_lon = 0, s_vrn = 0;
+  float s_rbd = 0, s_rbc = 0, s_rbr = 0;                     // radial-velocity terms: the three sums of this role's quantity (bodies / joints)
   float s_key = 0, s_keyn = 0, s_lkey = 0, s_lkeyn = 0, s_lkrot = 0, s_kvel = 0, s_kang = 0, s_lupn = 0, s_llon = 0, s_lvrn = 0, s_bodyz = 0;
 
   if (!roleB) {
@@ -1326,6 +1338,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     WAVE_LDS_FENCE();
     // =============== role B, interval 1: per-env scalars, reference frame ============================================================
     // ---- contacts (legged_robot_base.py:371-380); the other per-env scalars are role A's (behind its FK chain)
+    // feet_contact_force (legged_robot_base.py:1117-1118): the feet rows of this frame's contact forces, [foot][xyz]
+    if ((c.obs_extra & 2) && valid && lane < 3 * NF) feat[c.feat_off[PBHC_F_FEET_CONTACT_FORCE] + lane] = cf[3 * c.feet[lane / 3] + (lane % 3)];
     if (valid && lane < NF) {
       const int f = lane;
       float cn = norm3(ld3(cf + 3 * c.feet[f])) > 1.0f ? 1.0f : 0.0f;
@@ -1371,6 +1385,21 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         st3(rv + 3 * i, mk3(a * v0.x + bb * v1.x, a * v0.y + bb * v1.y, a * v0.z + bb * v1.z));
         f3 w0 = ld3(r0 + o_ang + 3 * i), w1 = ld3(r1 + o_ang + 3 * i);
         st3(rw + 3 * i, mk3(a * w0.x + bb * w1.x, a * w0.y + bb * w1.y, a * w0.z + bb * w1.z));
+      }
+    }
+    // ---- future_ref_dof_pos / future_ref_dof_vel (motion_tracking.py:562-599): the joint rows of future_ref_steps more lookups at
+    // (episode_length + 1 + i) dt + start, laid out [step][dof]; frame_blend clamps past the clip's end as the library does.  Pre-reset
+    // values: nothing refreshes them after a reset (they are computed in _pre_compute_observations_callback)
+    if (!MODE && c.future_ref_steps > 0 && valid) {
+      const int o_fp = c.feat_off[PBHC_F_FUT_REF_DOF_POS], o_fv = c.feat_off[PBHC_F_FUT_REF_DOF_VEL];
+      for (int i = 0; i < c.future_ref_steps; ++i) {
+        int g0, g1;
+        float bl;
+        frame_blend((float)(ep1 + 1 + i) * dt + start, m_len, m_nf, m_dt, &g0, &g1, &bl);
+        const float* a0 = tbl.frames + (size_t)(m_row0 + g0) * tbl.row;
+        const float* a1 = tbl.frames + (size_t)(m_row0 + g1) * tbl.row;
+        const float p0 = a0[dc], p1 = a1[dc], v0 = a0[D + dc], v1 = a1[D + dc];
+        if (lane < D) { feat[o_fp + i * D + lane] = (1.0f - bl) * p0 + bl * p1; feat[o_fv + i * D + lane] = (1.0f - bl) * v0 + bl * v1; }
       }
     }
     STAMPB(2);
@@ -1445,6 +1474,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       if (lane == 0) {
         feat[c.feat_off[PBHC_F_DR_FRICTION]] = fric;
         feat[c.feat_off[PBHC_F_ZERO]] = 0.0f;
+        if (c.obs_extra & 1) feat[c.feat_off[PBHC_F_ONE]] = 1.0f;
         if (MODE) feat[c.feat_off[PBHC_F_DR_BASE_MASS]] = bmass;
       }
     }
@@ -1486,6 +1516,14 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const int o_lbp = c.feat_off[PBHC_F_LOCAL_BODY_POS], o_lbr = c.feat_off[PBHC_F_LOCAL_BODY_ROT];
       const int o_dif = c.feat_off[PBHC_F_DIF_LOCAL_RIGID_BODY_POS], o_loc = c.feat_off[PBHC_F_LOCAL_REF_RIGID_BODY_POS];
       const int o_vr = c.feat_off[PBHC_F_VR_3POINT_POS], o_lv = c.feat_off[PBHC_F_LOCAL_REF_RIGID_BODY_VEL], o_gv = c.feat_off[PBHC_F_GLOBAL_REF_RIGID_BODY_VEL];
+      // local_ref_rigid_body_pos_relyaw (motion_tracking.py:684-685,720-721): calc_yaw_heading_quat_inv of the relative yaw, every lane for itself
+      const int o_ry = c.feat_off[PBHC_F_REF_VEL_RELYAW];
+      f4 ryq = mk4(0, 0, 0, 1);
+      if (c.obs_extra & 4) {
+        float sn, cs;
+        sincos_cw(feat[c.feat_off[PBHC_F_RELYAW]] * 0.5f, &sn, &cs);
+        ryq = mk4(0.0f, 0.0f, -sn, cs);
+      }
 #ifdef PBHC_ABL_EBODY
       for (int b = lane; b < 0; b += PBHC_G) {
 #else
@@ -1506,6 +1544,12 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         f3 dv = sub3(ld3(rv + 3 * b), ld3(bv + 3 * b));
         const float dv2 = (dv.x * dv.x + dv.y * dv.y + dv.z * dv.z) * (1.0f / 3.0f);
         s_vel += dv2;
+        if (c.radial_terms & 1) {                  // motion_tracking.py:1238-1242: cur = the body velocities, ref = dif + cur
+          const f3 cu = ld3(bv + 3 * b), rf = add3(dv, cu);
+          s_rbd += cu.x * rf.x + cu.y * rf.y + cu.z * rf.z;
+          s_rbc += cu.x * cu.x + cu.y * cu.y + cu.z * cu.z;
+          s_rbr += rf.x * rf.x + rf.y * rf.y + rf.z * rf.z;
+        }
         f3 dw3 = sub3(ld3(rw + 3 * b), ld3(bw + 3 * b));
         const float dw2 = (dw3.x * dw3.x + dw3.y * dw3.y + dw3.z * dw3.z) * (1.0f / 3.0f);
         s_ang += dw2;
@@ -1540,6 +1584,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         f3 rvel = ld3(rv + 3 * b);
         st3(feat + o_gv + 3 * b, rvel);
         st3(feat + o_lv + 3 * b, quat_rotate(hinv, rvel));
+        if (c.obs_extra & 4) st3(feat + o_ry + 3 * b, quat_rotate(ryq, rvel));
       }
       if (MODE && lane == 0) {
         // root differences (general_tracking.py:655-666) and the anchor observations / termination signals (:784-803)
@@ -1564,6 +1609,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     STAMP(23);
     GSUM(s_up); GSUM(s_lo); GSUM(s_vr); GSUM(s_feet); GSUM(s_rot); GSUM(s_vel); GSUM(s_ang); GSUM(s_upn); GSUM(s_lon); GSUM(s_vrn);
     s_maxn = group_max(s_maxn);
+    if (c.radial_terms & 1) {
+      GSUM(s_rbd); GSUM(s_rbc); GSUM(s_rbr);
+      if (valid && lane == 0) radial_cos_ratio(s_rbd, s_rbc, s_rbr, red + R_RADB);
+    }
     if (MODE) {
       GSUM(s_key); GSUM(s_keyn); GSUM(s_lkey); GSUM(s_lkeyn); GSUM(s_lkrot); GSUM(s_kvel); GSUM(s_kang); GSUM(s_lupn); GSUM(s_llon); GSUM(s_lvrn);
       s_bodyz = group_max(s_bodyz);
@@ -1664,6 +1713,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         feat[o_dja + dd] = dj; feat[o_djv + dd] = djv;
         s_maxjp = fmaxf(s_maxjp, fabsf(dj));
         s_jp2 += dj * dj; s_jv2 += djv * djv;
+        if (c.radial_terms & 2) {                  // motion_tracking.py:1286-1290: cur = dof_vel, ref = dif_joint_velocities + cur
+          const float cu = qd[dd], rf = djv + cu;
+          s_rbd += cu * rf; s_rbc += cu * cu; s_rbr += rf * rf;
+        }
         s_tau2 += tau[dd] * tau[dd];
         float la = pf_last_act - act[dd];
         s_ar += la * la;
@@ -1714,6 +1767,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     GSUM(s_jp2); GSUM(s_jv2); GSUM(s_tau2); GSUM(s_ar); GSUM(s_qd2); GSUM(s_qacc2); GSUM(s_lpos); GSUM(s_lvel); GSUM(s_ltau); GSUM(s_coll);
     s_maxjp = group_max(s_maxjp);
+    if (c.radial_terms & 2) {
+      GSUM(s_rbd); GSUM(s_rbc); GSUM(s_rbr);
+      if (valid && lane == 0) radial_cos_ratio(s_rbd, s_rbc, s_rbr, red + R_RADJ);
+    }
     if (close_any) {
       // one uniform per gate and STEP (torch.rand(1) < p on the host in the reference): keyed on the step counter only, the same for every env
       float ug[4];
@@ -1985,6 +2042,14 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
             for (int f = 0; f < PBHC_MAX_FEET; ++f) if (f < NF) misc[M_FAT0 + f] = nf[f];
           }
           raw = id == PBHC_R_FEET_AIR_TIME ? v : raw;
+        }
+        if ((TERM(TELEOP_RADIAL_BODY_VELOCITY_EXTEND) || TERM(TELEOP_RADIAL_JOINT_VELOCITY)) && c.radial_terms) {
+          // radial_velocity_potential (motion_tracking.py:78-94), no guard of its own: |ref| = 0 gives inf x 0 = NaN as there
+          const bool body = id == PBHC_R_TELEOP_RADIAL_BODY_VELOCITY_EXTEND;
+          const float* rs = red + (body ? R_RADB : R_RADJ);
+          const float cs = rs[0], r = rs[1];
+          const float v = expf(-(1.0f - cs) / 0.75f) * (r * expf(0.4f * (1.0f - r * r * sqrtf(r))));
+          raw = (body || id == PBHC_R_TELEOP_RADIAL_JOINT_VELOCITY) ? v : raw;
         }
         if (TERM(PENALTY_FEET_CONTACT_FORCES)) {
           float v = 0.0f;

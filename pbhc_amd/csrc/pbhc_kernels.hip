@@ -802,6 +802,10 @@ static int finalize_config(const PbhcEnvConfig* cfg, PbhcEnvConfig* fin, int* ld
     if (cfg->ps_pd) ARG_CHECK(cfg->ps_pd_slot[d] >= -1 && cfg->ps_pd_slot[d] < cfg->ps_pd_num && (d < cfg->skel.num_dof || cfg->ps_pd_slot[d] == -1));
     if (cfg->ps_tau) ARG_CHECK(cfg->ps_tau_slot[d] >= -1 && cfg->ps_tau_slot[d] < cfg->ps_tau_num && (d < cfg->skel.num_dof || cfg->ps_tau_slot[d] == -1));
   }
+  // the optional features / terms: flags within their ranges, the v1-only ones refused for general tracking
+  ARG_CHECK((cfg->obs_extra & ~7) == 0 && (cfg->radial_terms & ~3) == 0);
+  ARG_CHECK(cfg->future_ref_steps >= 0 && cfg->future_ref_steps <= PBHC_MAX_FUTURE);
+  ARG_CHECK(cfg->tracking_mode == 0 || (cfg->future_ref_steps == 0 && cfg->radial_terms == 0 && (cfg->obs_extra & 1) == 0));
   ARG_CHECK(cfg->feat_dim > 0 && cfg->feat_dim < 16384);
   // the step kernel addresses every per-env tensor with 32-bit element offsets from its base pointer
   ARG_CHECK((uint64_t)cfg->num_envs * (uint64_t)(cfg->skel.num_bodies * 13 > cfg->hist_dim + 64 ? cfg->skel.num_bodies * 13 : cfg->hist_dim + 64) < (1ull << 30));

@@ -34,6 +34,8 @@ TERM_SIGMAS = {
 }
 V2_ONLY_TERMS = {"teleop_key_body_position", "teleop_anchor_body_position", "teleop_anchor_body_rotation", "local_key_body_position",
                  "local_key_body_rotation", "key_body_velocity", "key_body_ang_velocity", "teleop_root_vel", "teleop_root_pose", "teleop_contact_mask_v2"}
+# motion_tracking.py defines these two (:1238-1244, 1286-1292); general_tracking.py does not
+V1_ONLY_TERMS = {"teleop_radial_body_velocity_extend", "teleop_radial_joint_velocity"}
 OBS_FEATURES = {
     "base_lin_vel": "BASE_LIN_VEL", "base_ang_vel": "BASE_ANG_VEL", "projected_gravity": "PROJECTED_GRAVITY", "dof_pos": "DOF_POS",
     "dof_vel": "DOF_VEL", "actions": "ACTIONS", "ref_motion_phase": "REF_MOTION_PHASE",
@@ -47,6 +49,12 @@ OBS_FEATURES = {
     # ones when it is off (:373-379 aliases them): see NOISE_PROCESS_FEATURES
     "base_ang_vel_noise": "BASE_ANG_VEL", "projected_gravity_noise": "PROJECTED_GRAVITY", "dof_pos_noise": "DOF_POS", "dof_vel_noise": "DOF_VEL",
 }
+# both envs: legged_robot_base.py:1117-1118; motion_tracking.py:950-952 / general_tracking.py:837-839 (the reference body VELOCITIES rotated by
+# the relative-yaw inverse heading, whatever the name says)
+OBS_FEATURES.update({"feet_contact_force": "FEET_CONTACT_FORCE", "local_ref_rigid_body_pos_relyaw": "REF_VEL_RELYAW"})
+# the v1 env only (motion_tracking.py:977-990): constants and the look-ahead joint rows
+OBS_FEATURES_V1 = {"indicator_guider": "ONE", "indicator_learner": "ZERO", "zero_vector": "ZERO",
+                   "future_ref_dof_pos": "FUT_REF_DOF_POS", "future_ref_dof_vel": "FUT_REF_DOF_VEL"}
 NOISE_PROCESS_FEATURES = {"base_ang_vel_noise": "BASE_ANG_VEL_NOISE", "projected_gravity_noise": "PROJECTED_GRAVITY_NOISE"}
 # general tracking getters (general_tracking.py:821-954): plain features ...
 OBS_FEATURES_V2 = {
@@ -341,7 +349,12 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     pen_names = set(rw.reward_penalty_reward_names)
     for i, name in enumerate(L.reward_names):
         key = "PBHC_R_" + name.upper()
-        if key not in K or (mode == 0 and name in V2_ONLY_TERMS):
+        if name == "feet_max_height_for_this_air":
+            # legged_robot_base.py:1022 applies `~` to self.last_contacts_filt, which _init_buffers (:68) creates as a FLOAT tensor and
+            # _post_compute_observations_callback (:405) only ever writes in place: torch raises TypeError on the term's first evaluation
+            raise NotImplementedError("reward term 'feet_max_height_for_this_air': the reference's env cannot run it (its first evaluation raises "
+                                      "TypeError: `~` on the float tensor last_contacts_filt, legged_robot_base.py:68,1022)")
+        if key not in K or (mode == 0 and name in V2_ONLY_TERMS) or (mode == 1 and name in V1_ONLY_TERMS):
             raise NotImplementedError(f"reward term {name!r} has no HIP implementation")
         c.term_id[i] = K[key]
         if name in ("feet_heading_alignment", "feet_heading_alignment_contact", "penalty_feet_ori", "penalty_feet_ori_contact"):
@@ -351,6 +364,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
         c.term_sum_col[i] = L.sum_names.index(name)
         for s in TERM_SIGMAS.get(name, []):
             c.sigma_active[s] = 1
+    c.radial_terms = (1 if "teleop_radial_body_velocity_extend" in L.reward_names else 0) | (2 if "teleop_radial_joint_velocity" in L.reward_names else 0)
     c.has_termination = int("termination" in scales)
     if c.has_termination:
         c.termination_scale = float(scales["termination"])
@@ -409,9 +423,14 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
             c.future_steps[i] = int(v)
         L.future_steps = steps
     Kb = len(key_ids)
+    Sr = int(ob.get("future_ref_steps", 0) or 0) if mode == 0 else 0         # motion_tracking.py:586: look-ahead steps of future_ref_dof_*
+    if Sr > K["PBHC_MAX_FUTURE"]:
+        raise _lib.PbhcError("too many future_ref_steps")
     feats = dict(OBS_FEATURES)
     if mode == 1:
         feats.update(OBS_FEATURES_V2)
+    else:
+        feats.update(OBS_FEATURES_V1)
     npc = ob.get("noise_process", None)
     if npc is not None and npc.get("enable", False):
         # legged_robot_base.py:122-129 + utils/noise_tool.py: only OUProcess defines reset_part, which _reset_tasks_callback calls on every
@@ -461,12 +480,15 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
         "FUT_ROOT_HEIGHT": max(S, 1), "FUT_ROLL_PITCH": max(2 * S, 1), "FUT_BASE_LIN_VEL": max(3 * S, 1), "FUT_BASE_ANG_VEL": max(3 * S, 1),
         "FUT_DOF_POS": max(S * D, 1), "FUT_LOCAL_KEY_POS": max(S * Kb * 3, 1),
         "BASE_ANG_VEL_NOISE": 3, "PROJECTED_GRAVITY_NOISE": 3,
+        "ONE": 1, "FEET_CONTACT_FORCE": 3 * len(feet), "REF_VEL_RELYAW": 3 * Bx, "FUT_REF_DOF_POS": max(Sr * D, 1), "FUT_REF_DOF_VEL": max(Sr * D, 1),
     }
     # which features do the observation maps read?  the kernel skips the others (feat_off = -1)
     used = {"HISTORY", "ZERO"}
     def mark(k):
         if k in feats:
             used.add(feats[k])
+            if feats[k] == "REF_VEL_RELYAW":
+                used.add("RELYAW")                   # the kernel derives the rotation from the relative yaw in the row
         elif mode == 1 and k in OBS_GATHERS_V2:
             used.update(OBS_GATHERS_V2[k])
 
@@ -482,6 +504,8 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
             feat_off[name] = off
             c.feat_off[K["PBHC_F_" + name]] = off
             off += n
+    c.obs_extra = (1 if "ONE" in used else 0) | (2 if "FEET_CONTACT_FORCE" in used else 0) | (4 if "REF_VEL_RELYAW" in used else 0)
+    c.future_ref_steps = Sr if ("FUT_REF_DOF_POS" in used or "FUT_REF_DOF_VEL" in used) else 0
     trash = off                       # features nobody reads share one scratch region at the end of the row
     for name, n in fdim.items():
         if name not in used:
@@ -494,7 +518,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
     off += fdim["HISTORY"]
     c.feat_dim = off
     # readiness class of every feature word (see the compact maps below): which phase of the step kernel produces it
-    CLASS0 = {"HISTORY", "ZERO", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJECTED_GRAVITY", "BASE_ANG_VEL_NOISE", "PROJECTED_GRAVITY_NOISE", "REF_MOTION_PHASE", "RELYAW", "ROLL_PITCH", "DR_BASE_COM",
+    CLASS0 = {"HISTORY", "ZERO", "ONE", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJECTED_GRAVITY", "BASE_ANG_VEL_NOISE", "PROJECTED_GRAVITY_NOISE", "REF_MOTION_PHASE", "RELYAW", "ROLL_PITCH", "DR_BASE_COM",
               "DR_LINK_MASS", "DR_FRICTION", "DR_BASE_MASS", "REF_CONTACT_MASK", "FUT_ROOT_HEIGHT", "FUT_ROLL_PITCH", "FUT_BASE_LIN_VEL",
               "FUT_BASE_ANG_VEL", "FUT_DOF_POS", "FUT_LOCAL_KEY_POS"}
     CLASS2 = {"DOF_POS", "DOF_VEL", "ACTIONS", "DR_KP", "DR_KD", "DR_CTRL_DELAY", "BASE_POS_Z", "CONTACT_MASK"}
@@ -541,6 +565,13 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
         if key not in feats:
             raise NotImplementedError(f"observation {key!r} has no HIP implementation")
         f = feats[key]
+        if key == "zero_vector":                         # obs_dims.zero_vector zeros (motion_tracking.py:983-984)
+            return [feat_off["ZERO"]] * dims[key]
+        if key in ("future_ref_dof_pos", "future_ref_dof_vel"):
+            if not Sr:
+                raise _lib.PbhcError(f"observation {key!r} needs obs.future_ref_steps > 0")
+            if dims[key] != Sr * D:
+                raise _lib.PbhcError(f"obs_dims[{key}]={dims[key]} does not match future_ref_steps x dofs = {Sr * D}")
         if dims[key] > fdim[f]:
             raise _lib.PbhcError(f"obs_dims[{key}]={dims[key]} exceeds the feature size {fdim[f]}")
         idx = list(range(feat_off[f], feat_off[f] + dims[key]))
