@@ -27,7 +27,7 @@ class LeggedRobotGeneralTracking(LeggedRobotMotionTracking):
         self.key_body_id = L.key
         self.anchor_index = int(self._c.anchor_index)
         self.num_key_bodies = len(L.key)
-        self.tar_obs_steps = torch.tensor(getattr(L, "future_steps", []), dtype=torch.long, device=self.device)     # PPO reads len(env.tar_obs_steps)
+        self.tar_obs_steps = torch.tensor(L.future_steps, dtype=torch.long, device=self.device)     # PPO reads len(env.tar_obs_steps)
         self.curr_motion_ids = self._motion_lib.slot_clip
         self.num_motions = self._motion_lib._num_unique_motions
         self.motion_start_idx = 0

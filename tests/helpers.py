@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (fixtures -> oracle objects)."""
 import os
+import types
 
 import numpy as np
 import torch
@@ -34,6 +35,23 @@ def fixture_config(name, num_envs, overrides=None):
     for k in list(cfg.obs.noise_scales.keys()):
         cfg.obs.noise_scales[k] = 0.0
     return cfg
+
+
+def build_env_config(cfgname, overrides=None, *, num_envs, seed, general, has_contact_mask, mutate=None):
+    """A fixture tree with `overrides` through env_config.build on the CPU (the header is enough: no compiled library, no GPU) ->
+    (cfg, skel, c, L).  `mutate(cfg)` edits the loaded tree before the build, for what load_config overrides cannot express."""
+    from pbhc_amd.envs import env_config
+    from pbhc_amd.envs.motion_tracking import _TopView
+    from pbhc_amd.skeleton import Skeleton
+
+    cfg = load_config(os.path.join(GOLDEN, "configs", cfgname), dict({"num_envs": num_envs, "simulator._target_": STUB}, **(overrides or {})), now="t")
+    if mutate is not None:
+        mutate(cfg)
+    skel = Skeleton.from_motion_config(cfg.robot.motion)
+    motion_lib = types.SimpleNamespace(has_contact_mask=has_contact_mask)
+    c, L = env_config.build(_TopView(cfg.env.config), skel, motion_lib, num_envs, "cpu", len(cfg.domain_rand.get("randomize_link_body_names", [])),
+                            seed=seed, mode=1 if general else 0)
+    return cfg, skel, c, L
 
 
 def state_dict_from_golden(g, prefix="state0__", step=None):

@@ -13,9 +13,8 @@ import numpy as np
 import pytest
 
 from pbhc_amd.envs import env_config
-from pbhc_amd.skeleton import Skeleton
 from pbhc_amd.utils.config import load_config
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, build_env_config
 
 DERIVED = json.load(open(os.path.join(GOLDEN, "config_derived.json")))
 CONFIGS = sorted(DERIVED.keys())
@@ -41,20 +40,13 @@ def test_two_independent_resolvers_agree_on_the_whole_tree(name):
     assert json.dumps(a, sort_keys=True) == json.dumps(b, sort_keys=True)
 
 
+def _reference_target(cfg):
+    cfg.env.config["_target_"] = "humanoidverse.envs.motion_tracking.general_tracking.LeggedRobotGeneralTracking"
+
+
 def _build(name):
-    from pbhc_amd.envs.motion_tracking import _TopView
-
-    cfg = load_config(os.path.join(GOLDEN, "configs", name), {"num_envs": 8}, now="t")
     general = name.startswith("v2_")
-    if general:
-        cfg.env.config["_target_"] = "humanoidverse.envs.motion_tracking.general_tracking.LeggedRobotGeneralTracking"
-    sk = Skeleton.from_motion_config(cfg.robot.motion)
-
-    class ML:
-        has_contact_mask = "walk" not in name
-
-    c, L = env_config.build(_TopView(cfg.env.config), sk, ML(), 8, "cpu", len(cfg.domain_rand.randomize_link_body_names), seed=0, mode=1 if general else 0)
-    return cfg, sk, c, L
+    return build_env_config(name, num_envs=8, seed=0, general=general, has_contact_mask="walk" not in name, mutate=_reference_target if general else None)
 
 
 @pytest.mark.parametrize("name", CONFIGS)

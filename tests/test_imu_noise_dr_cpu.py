@@ -1,17 +1,12 @@
 """obs.noise_process (OU IMU noise) and domain_rand.parallel_serial_pd / parallel_serial_tau at the config level (no GPU): what
 env_config.build puts into the ABI, what it refuses, and that the switches off leave the config as it was."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from pbhc_amd import _lib
-from pbhc_amd.envs import env_config
-from pbhc_amd.envs.motion_tracking import _TopView
-from pbhc_amd.skeleton import Skeleton
-from pbhc_amd.utils.config import load_config
-from tests.helpers import GOLDEN
+from tests.helpers import build_env_config
 
 K = _lib.K
 OU = {"obs.noise_process.enable": True, "obs.noise_process.type": "ou", "obs.noise_process.kwargs.mu": 0.1,
@@ -27,28 +22,21 @@ NEW_FIELDS = {"noise_process", "ou_mu", "ou_theta", "ou_sigma", "ou_sqrt_dt", "o
 CONFIGS = [("v1_g1_23dof_walk.yaml", 0), ("v2_g1_23dof_student.yaml", 1), ("v2_g1_23dof_teacher.yaml", 1), ("v2_g1_29dof_teacher.yaml", 1)]
 
 
-class _ML:
-    has_contact_mask = False
-
-
-def _load(cfgname, overrides):
-    return load_config(os.path.join(GOLDEN, "configs", cfgname), dict({"num_envs": 64, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"},
-                                                                       **overrides), now="t")
+def add_noise_names(cfg):
+    """the four names in actor_obs (+ their dims / scales, as a yaml that uses them lists them)"""
+    ob = cfg.obs
+    ob.obs_dict.actor_obs = list(ob.obs_dict.actor_obs) + NOISE_NAMES
+    D = len(cfg.robot.dof_names)
+    ob.obs_dims = list(ob.obs_dims) + [{"base_ang_vel_noise": 3}, {"projected_gravity_noise": 3}, {"dof_pos_noise": D}, {"dof_vel_noise": D}]
+    for k in NOISE_NAMES:
+        ob.obs_scales[k] = 1.0
+        ob.noise_scales[k] = 0.0
 
 
 def _build(cfgname, overrides, mode, noise_names=False):
-    cfg = _load(cfgname, overrides)
-    if noise_names:           # the four names in actor_obs (+ their dims / scales, as a yaml that uses them lists them)
-        ob = cfg.obs
-        ob.obs_dict.actor_obs = list(ob.obs_dict.actor_obs) + NOISE_NAMES
-        D = len(cfg.robot.dof_names)
-        ob.obs_dims = list(ob.obs_dims) + [{"base_ang_vel_noise": 3}, {"projected_gravity_noise": 3}, {"dof_pos_noise": D}, {"dof_vel_noise": D}]
-        for k in NOISE_NAMES:
-            ob.obs_scales[k] = 1.0
-            ob.noise_scales[k] = 0.0
-    skel = Skeleton.from_motion_config(cfg.robot.motion)
-    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
-    return cfg, env_config.build(_TopView(cfg.env.config), skel, _ML(), 64, "cpu", nl, seed=1, mode=mode)
+    cfg, _, c, L = build_env_config(cfgname, overrides, num_envs=64, seed=1, general=mode == 1, has_contact_mask=False,
+                                    mutate=add_noise_names if noise_names else None)
+    return cfg, (c, L)
 
 
 def _fields(c):

@@ -8,32 +8,20 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, build_env_config
 from tools.gen_obs_reward_terms_golden import FUTURE_REF_STEPS, RADIAL, V1_ACTOR, V1_CRITIC, V2_ACTOR, ZERO_VECTOR, overrides
 
 WALK, HORSE, STUDENT, TEACHER = "v1_g1_23dof_walk.yaml", "v1_g1_23dof_horse_stance.yaml", "v2_g1_23dof_student.yaml", "v2_g1_29dof_teacher.yaml"
-
-
-class _ML:
-    has_contact_mask = True
 
 
 BASE = {"num_envs": 4, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"}
 
 
 def _build(cfgname, general, ov=None, names=False):
-    from pbhc_amd.envs import env_config
-    from pbhc_amd.envs.motion_tracking import _TopView
-    from pbhc_amd.skeleton import Skeleton
     from pbhc_amd.utils.config import load_config
 
-    cfg = load_config(f"{GOLDEN}/configs/{cfgname}", dict(BASE), now="t")
-    o = dict(overrides(cfg, general) if names else {}, **(ov or {}))
-    cfg = load_config(f"{GOLDEN}/configs/{cfgname}", dict(BASE, **o), now="t")
-    skel = Skeleton.from_motion_config(cfg.robot.motion)
-    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
-    c, L = env_config.build(_TopView(cfg.env.config), skel, _ML(), 4, "cpu", nl, seed=1, mode=1 if general else 0)
-    return cfg, skel, c, L
+    o = dict(overrides(load_config(f"{GOLDEN}/configs/{cfgname}", dict(BASE), now="t"), general) if names else {}, **(ov or {}))
+    return build_env_config(cfgname, o, num_envs=4, seed=1, general=general, has_contact_mask=True)
 
 
 def _add_obs(cfgname, key, dim, group="actor_obs", extra=None):
@@ -151,7 +139,7 @@ def _digest(c, L):
     h = hashlib.sha256()
     h.update(np.asarray([c.feat_dim, c.hist_dim, c.num_terms] + [c.term_id[i] for i in range(c.num_terms)], dtype=np.int64).tobytes())
     h.update(repr(sorted(L.feat_off.items())).encode())
-    h.update(L.map_image.cpu().numpy().tobytes() if hasattr(L, "map_image") else b"")
+    h.update(L.map_image.cpu().numpy().tobytes() if L.map_image is not None else b"")
     return h.hexdigest()[:16]
 
 

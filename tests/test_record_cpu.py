@@ -1,7 +1,6 @@
 """env.config.save_motion (the evaluation recorder, opt/record.yaml) at the config level, and the recorder's rotation-vector routine against
 scipy's Rotation.as_rotvec — no GPU."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -9,10 +8,7 @@ from scipy.spatial.transform import Rotation
 
 from pbhc_amd import _lib
 from pbhc_amd.envs import env_config
-from pbhc_amd.envs.motion_tracking import _TopView
-from pbhc_amd.skeleton import Skeleton
-from pbhc_amd.utils.config import load_config
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, build_env_config
 
 RECORD = {"env.config.save_motion": True, "env.config.save_total_steps": 8, "env.config.save_note": "note", "env.config.eval_timestamp": "stamp",
           "env.config.ckpt_dir": "/nonexistent"}
@@ -24,16 +20,9 @@ ROTVEC_FP32_MEASURED = 2.7e-7          # measured 2.615e-07 (1.1 ulp of pi in fl
 ROTVEC_TOL = 4 * ROTVEC_FP32_MEASURED
 
 
-class _ML:
-    has_contact_mask = False
-
-
 def _build(cfgname, overrides, mode):
-    cfg = load_config(os.path.join(GOLDEN, "configs", cfgname), dict({"num_envs": 64, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"},
-                                                                     **overrides), now="t")
-    skel = Skeleton.from_motion_config(cfg.robot.motion)
-    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
-    return cfg, skel, env_config.build(_TopView(cfg.env.config), skel, _ML(), 64, "cpu", nl, seed=1, mode=mode)
+    cfg, skel, c, L = build_env_config(cfgname, overrides, num_envs=64, seed=1, general=mode == 1, has_contact_mask=False)
+    return cfg, skel, (c, L)
 
 
 def test_save_motion_yields_the_recorder_layout():

@@ -1,15 +1,10 @@
 """termination.terminate_when_dof_far and noise_to_initial_level at the config level (no GPU): what env_config.build puts into the ABI."""
-import os
-
 import numpy as np
 import pytest
 
 from pbhc_amd import _lib
-from pbhc_amd.envs import env_config
-from pbhc_amd.envs.motion_tracking import LeggedRobotMotionTracking, _TopView
-from pbhc_amd.skeleton import Skeleton
-from pbhc_amd.utils.config import load_config
-from tests.helpers import GOLDEN
+from pbhc_amd.envs.motion_tracking import LeggedRobotMotionTracking
+from tests.helpers import build_env_config
 
 K = _lib.K
 TC = "env.config.termination_curriculum.terminate_when_dof_far_curriculum."
@@ -18,16 +13,9 @@ DOF_FAR = {"env.config.termination.terminate_when_dof_far": True, TC + "enable":
 NOISE = {"env.config.noise_to_initial_level": 0.5}
 
 
-class _ML:
-    has_contact_mask = False
-
-
 def _build(cfgname, overrides, mode):
-    cfg = load_config(os.path.join(GOLDEN, "configs", cfgname), dict({"num_envs": 64, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"},
-                                                                     **overrides), now="t")
-    skel = Skeleton.from_motion_config(cfg.robot.motion)
-    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
-    return cfg, env_config.build(_TopView(cfg.env.config), skel, _ML(), 64, "cpu", nl, seed=1, mode=mode)
+    cfg, _, c, L = build_env_config(cfgname, overrides, num_envs=64, seed=1, general=mode == 1, has_contact_mask=False)
+    return cfg, (c, L)
 
 
 def test_build_accepts_dof_far_and_reset_noise():
