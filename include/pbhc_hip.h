@@ -586,7 +586,8 @@ int pbhc_rollout_post2(const float* rew, const float* values, const int64_t* res
 
 /* GAE + returns + normalised advantages.  Replaces MHPPO._compute_returns (mh_ppo.py:348-395).
  * rewards/values/returns [T,N,R], dones [T,N] bool, last_values [N,R], advantages [T,N].
- * stats: device double[4] scratch. */
+ * stats: device scratch of 2 * ceil(T*N / 256) + 2 doubles: per-block partial sums, then the mean and the unbiased std of the unnormalised
+ * advantages at stats[2 * ceil(T*N / 256)] and the element behind it (the data-parallel path re-normalises with them). */
 int pbhc_gae(const float* rewards, const float* values, const uint8_t* dones, const float* last_values, int T, int N, int R,
              float gamma, float lam, float* returns, float* advantages, double* stats, void* stream);
 
@@ -753,7 +754,9 @@ int pbhc_gather_rows(const PbhcGatherJob* jobs, int num_jobs, const int64_t* ind
 /* nn.utils.clip_grad_norm_(max_norm) + torch.optim.Adam.step() (mh_ppo.py:519-524; weight_decay > 0: torch.optim.AdamW, decoupled,
  * ppo_mimic.py:184-190,682-686) over ONE flat fp32 segment of n
  * parameters (param/grad/exp_avg/exp_avg_sq flat views; lr and step are device scalars, step is incremented).
- * scratch: 512 doubles.  norm_out (may be NULL): the pre-clip gradient norm. */
+ * scratch: 512 doubles.  norm_out (may be NULL): the pre-clip gradient norm.
+ * beta1 / beta2 act at their float values: beta2 = 0.999f is 0.99900001, so exp_avg_sq is 1.3e-5 (relative) below a double-beta Adam's while
+ * the bias correction uses the same value and the parameter step agrees to rounding (tests/test_gpu_ppo_kernels.py). */
 int pbhc_adam_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int n, const float* lr, float* step, float max_norm, float beta1,
                    float beta2, float eps, float weight_decay, double* scratch, float* norm_out, void* stream);
 /* Two consecutive segments (actor [0,n0), critic [n0,n0+n1): MHPPO's two clip_grad_norm_ + two Adam steps, mh_ppo.py:519-524) in ONE launch

@@ -45,6 +45,33 @@ def gaussian_entropy(std):
     return (0.5 + 0.5 * math.log(2 * math.pi) + torch.log(std)).sum(dim=-1)
 
 
+def losses(mu, sigma, value, b, c, kl_form=1):
+    """The loss arithmetic of one minibatch (mh_ppo.py:433-480,509-511; ppo_mimic.py:612-660) on the network outputs, in the dtype of its
+    inputs: mu / sigma [B,A], value [B,R]; b: the storage keys actions, actions_log_prob, action_mean, action_sigma, advantages, values,
+    returns; c: clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss.  kl_form 1: mh_ppo's log(sigma / old + 1e-5), 2:
+    ppo_mimic's log(sigma / (old + 1e-5)).  Returns actor_loss, critic_loss, (surrogate, value loss, entropy, mean KL (no grad))."""
+    logp = gaussian_log_prob(b["actions"], mu, sigma)
+    entropy = gaussian_entropy(sigma)
+    with torch.no_grad():
+        old_s, old_m = b["action_sigma"], b["action_mean"]
+        lograt = torch.log(sigma / old_s + 1.0e-5) if kl_form == 1 else torch.log(sigma / (old_s + 1e-5))
+        kl_mean = torch.sum(lograt + (old_s.square() + (old_m - mu).square()) / (2.0 * sigma.square()) - 0.5, axis=-1).mean()
+    adv = b["advantages"].squeeze()
+    ratio = torch.exp(logp - b["actions_log_prob"].squeeze())
+    s1 = -adv * ratio
+    s2 = -adv * torch.clamp(ratio, 1.0 - c.clip_param, 1.0 + c.clip_param)
+    surrogate = torch.max(s1, s2).mean()
+    if c.use_clipped_value_loss:
+        vclip = b["values"] + (value - b["values"]).clamp(-c.clip_param, c.clip_param)
+        vl = torch.max((value - b["returns"]).pow(2), (vclip - b["returns"]).pow(2)).sum(dim=-1).mean()
+    else:
+        vl = (b["returns"] - value).pow(2).sum(dim=-1).mean()
+    ent = entropy.mean()
+    actor_loss = surrogate - c.entropy_coef * ent
+    critic_loss = c.value_loss_coef * vl
+    return actor_loss, critic_loss, (surrogate, vl, ent, kl_mean)
+
+
 class MHPPOUpdate:
     def __init__(self, actor_params, critic_params, cfg):
         """actor_params: dict with 'std' and 'actor_module.module.{0,2,4,6}.{weight,bias}';
@@ -67,37 +94,19 @@ class MHPPOUpdate:
     def update(self, b):
         c = self.cfg
         mu, sigma = self.actor_dist(b["actor_obs"])
-        logp = gaussian_log_prob(b["actions"], mu, sigma)
         value = self.critic(b["critic_obs"])
-        entropy = gaussian_entropy(sigma)
+        actor_loss, critic_loss, (surrogate, vl, ent, kl_mean) = losses(mu, sigma, value, b, c, kl_form=1)
         if c.desired_kl is not None and c.schedule == "adaptive":
-            with torch.no_grad():
-                old_s, old_m = b["action_sigma"], b["action_mean"]
-                kl = torch.sum(torch.log(sigma / old_s + 1.0e-5) + (old_s.square() + (old_m - mu).square()) / (2.0 * sigma.square()) - 0.5, axis=-1)
-                kl_mean = kl.mean()
-                if kl_mean > c.desired_kl * 2.0:
-                    self.lr_a = max(1e-5, self.lr_a / 1.5)
-                    self.lr_c = max(1e-5, self.lr_c / 1.5)
-                elif kl_mean < c.desired_kl / 2.0 and kl_mean > 0.0:
-                    self.lr_a = min(1e-2, self.lr_a * 1.5)
-                    self.lr_c = min(1e-2, self.lr_c * 1.5)
-                for g in self.opt_a.param_groups:
-                    g["lr"] = self.lr_a
-                for g in self.opt_c.param_groups:
-                    g["lr"] = self.lr_c
-        adv = b["advantages"].squeeze()
-        ratio = torch.exp(logp - b["actions_log_prob"].squeeze())
-        s1 = -adv * ratio
-        s2 = -adv * torch.clamp(ratio, 1.0 - c.clip_param, 1.0 + c.clip_param)
-        surrogate = torch.max(s1, s2).mean()
-        if c.use_clipped_value_loss:
-            vclip = b["values"] + (value - b["values"]).clamp(-c.clip_param, c.clip_param)
-            vl = torch.max((value - b["returns"]).pow(2), (vclip - b["returns"]).pow(2)).sum(dim=-1).mean()
-        else:
-            vl = (b["returns"] - value).pow(2).sum(dim=-1).mean()
-        ent = entropy.mean()
-        actor_loss = surrogate - c.entropy_coef * ent
-        critic_loss = c.value_loss_coef * vl
+            if kl_mean > c.desired_kl * 2.0:
+                self.lr_a = max(1e-5, self.lr_a / 1.5)
+                self.lr_c = max(1e-5, self.lr_c / 1.5)
+            elif kl_mean < c.desired_kl / 2.0 and kl_mean > 0.0:
+                self.lr_a = min(1e-2, self.lr_a * 1.5)
+                self.lr_c = min(1e-2, self.lr_c * 1.5)
+            for g in self.opt_a.param_groups:
+                g["lr"] = self.lr_a
+            for g in self.opt_c.param_groups:
+                g["lr"] = self.lr_c
         self.opt_a.zero_grad()
         self.opt_c.zero_grad()
         actor_loss.backward()

@@ -16,7 +16,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .ppo import gaussian_entropy, gaussian_log_prob
+from .ppo import losses
 
 CONV = {5: ([20, 10], [2, 2], [1, 1]), 10: ([20, 10], [4, 2], [2, 1]), 20: ([40, 20], [6, 4], [2, 2])}     # encoder_modules.py:60-77
 
@@ -108,9 +108,7 @@ class PPOMimicUpdate:
     def update_ppo(self, b):
         c, ac = self.cfg, self.ac
         mu, sigma = ac.dist(b, hist_encoding=False)
-        logp = gaussian_log_prob(b["actions"], mu, sigma)
         value = ac.evaluate(b)
-        entropy = gaussian_entropy(sigma)
         priv_latent = ac.priv(b["priv_obs"])
         with torch.no_grad():
             hist_latent = ac.history(b["prop_history"])
@@ -118,26 +116,15 @@ class PPOMimicUpdate:
         sch = c.priv_reg_coef_schedual
         stage = min(max(self.counter - sch[2], 0) / sch[3], 1)
         coef = stage * (sch[1] - sch[0]) + sch[0]
+        actor_loss, critic_loss, (surrogate, vl, ent, kl) = losses(mu, sigma, value, b, c, kl_form=2)
         if c.desired_kl is not None and c.schedule == "adaptive":
-            with torch.no_grad():
-                old_s, old_m = b["action_sigma"], b["action_mean"]
-                kl = torch.sum(torch.log(sigma / (old_s + 1e-5)) + (old_s ** 2 + (old_m - mu) ** 2) / (2.0 * sigma ** 2) - 0.5, axis=-1).mean()
-                if kl > c.desired_kl * 2.0:
-                    self.lr = max(1e-5, self.lr / 1.5)
-                elif kl < c.desired_kl / 2.0 and kl > 0.0:
-                    self.lr = min(1e-2, self.lr * 1.5)
-                for g in self.opt.param_groups:
-                    g["lr"] = self.lr
-        adv = torch.squeeze(b["advantages"])
-        ratio = torch.exp(logp - torch.squeeze(b["actions_log_prob"]))
-        surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - c.clip_param, 1.0 + c.clip_param)).mean()
-        if c.use_clipped_value_loss:
-            vclip = b["values"] + (value - b["values"]).clamp(-c.clip_param, c.clip_param)
-            vl = torch.max((value - b["returns"]).pow(2), (vclip - b["returns"]).pow(2)).sum(dim=-1).mean()
-        else:
-            vl = (b["returns"] - value).pow(2).sum(dim=-1).mean()
-        ent = entropy.mean()
-        total = surrogate - c.entropy_coef * ent + c.value_loss_coef * vl + coef * priv_reg
+            if kl > c.desired_kl * 2.0:
+                self.lr = max(1e-5, self.lr / 1.5)
+            elif kl < c.desired_kl / 2.0 and kl > 0.0:
+                self.lr = min(1e-2, self.lr * 1.5)
+            for g in self.opt.param_groups:
+                g["lr"] = self.lr
+        total = actor_loss + critic_loss + coef * priv_reg
         self.opt.zero_grad()
         total.backward()
         torch.nn.utils.clip_grad_norm_(list(ac.p.values()), c.max_grad_norm)

@@ -568,7 +568,7 @@ __global__ __launch_bounds__(GAE_TPB) void k_adv_norm(float* __restrict__ adv, s
   const double n = (double)TN;
   const double mean_d = s1[0] / n;
   const double var = (s2[0] - n * mean_d * mean_d) / (n - 1.0);       // torch.std: unbiased
-  const double sd_d = sqrt(var > 0.0 ? var : 0.0);
+  const double sd_d = sqrt(var < 0.0 ? 0.0 : var);                    // (T*N = 1: 0 / 0 stays NaN, as torch.std of one element)
   if (blockIdx.x == 0 && threadIdx.x == 0) { part[2 * nblocks] = mean_d; part[2 * nblocks + 1] = sd_d; }
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= TN) return;

@@ -238,18 +238,23 @@ def fresh_episode_state(orc):
 # The reference draws torch.rand_like per observation group and step (helpers.py:128-152): its stream cannot be reproduced, so noise-on
 # parity is checked against the KERNEL's own generator: Philox4x32-7 keyed (seed, env, step counter, 16, 0) -> first word -> re-keyed by
 # (row, element) -> bijective finaliser -> 24-bit uniform.
-def _philox4x32_7_word0(seed, env_ids, step_ctr):
+def _philox4x32_7(seed, c0, c1, c2, c3):
+    """csrc/pbhc_math.h philox4x32 (7 rounds) with key (seed lo, seed hi) on the counter words (c0, c1, c2, c3), broadcast against each
+    other: the four output words as uint64 arrays holding 32-bit values."""
     M = np.uint64(0xFFFFFFFF)
-    k0 = np.full(env_ids.shape, seed & 0xFFFFFFFF, np.uint64)
-    k1 = np.full(env_ids.shape, (seed >> 32) & 0xFFFFFFFF, np.uint64)
-    c0, c1 = env_ids.astype(np.uint64), np.full(env_ids.shape, step_ctr, np.uint64)
-    c2, c3 = np.full(env_ids.shape, 16, np.uint64), np.zeros(env_ids.shape, np.uint64)
+    c0, c1, c2, c3 = (a.astype(np.uint64) & M for a in np.broadcast_arrays(*(np.asarray(c, np.int64) for c in (c0, c1, c2, c3))))
+    k0 = np.full(c0.shape, seed & 0xFFFFFFFF, np.uint64)
+    k1 = np.full(c0.shape, (seed >> 32) & 0xFFFFFFFF, np.uint64)
     for _ in range(7):
         p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
         n0, n1, n2, n3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M, p1 & M, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M, p0 & M
         c0, c1, c2, c3 = n0, n1, n2, n3
         k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    return c0.astype(np.uint64)
+    return c0, c1, c2, c3
+
+
+def _philox4x32_7_word0(seed, env_ids, step_ctr):
+    return _philox4x32_7(seed, env_ids, step_ctr, 16, 0)[0]
 
 
 def expected_obs_noise(seed, env_ids, step_ctr, group_index, noise, scale, noise_cur=1.0):
