@@ -15,126 +15,31 @@ MI355X-first differences (same maths, pinned by tests/golden/ppo_v2.npz): as pbh
 synchronisation inside an iteration, fused sample / bootstrap / GAE / loss / clip+AdamW kernels over flat parameter buffers,
 the motion embedding computed once per forward for actor and critic, env observations written straight into the rollout slabs,
 one flat RCCL gradient all-reduce per optimiser step when envs are sharded over ranks.
+
+What it shares with MHPPO is agents/base.py; the RL rollout is agents/rollout.py.
 """
 from __future__ import annotations
 
-import os
-import time
-from collections import deque
-
 import torch
-import torch.distributed as dist
 
 from .. import _lib
 from .. import dist as pdist
+from . import fused_mlp, rollout
 from .agent_modules import Actor, ActorCritic
-from .mh_ppo import PhaseTimer, _load_checkpoint, _make_writer, policy_forward_graphs
-from .modules import BaseModule, RolloutStorage, apply_cat, apply_into
+from .base import FlatAdamView, OnDeviceAgent, _load_checkpoint, switch_on
+from .modules import BaseModule, apply_cat, apply_into
 
 
-class _FlatAdamWView:
-    """torch.optim.AdamW-format state_dict()/load_state_dict() over a set of parameters of the flat buffers."""
-
-    def __init__(self, algo, which):
-        self.algo, self.which = algo, which            # which: 0 = self.optimizer (all parameters), 1 = hist_encoder_optimizer
-
-    def _entries(self):
-        a = self.algo
-        names = [n for n, _ in a.alg.named_parameters()]
-        if self.which == 1:
-            names = [n for n in names if n.startswith("actor_module.history_encoder.")]
-        elif a.dagger_only:                                  # optim.AdamW(self.alg.actor.parameters()) (ppo_mimic.py:186-187)
-            names = [n for n in names if n.startswith("actor_module.")]
-        return names
-
-    def state_dict(self):
-        a = self.algo
-        state = {}
-        stepped = float(a._adam_step[self.which]) > 0
-        for i, n in enumerate(self._entries()):
-            if not stepped or (self.which == 0 and not a._is_main(n)):       # never stepped: torch keeps no state for it
-                continue
-            o, k, shape = a._slice_of[n]
-            state[i] = {"step": a._adam_step[self.which].detach().clone().cpu(), "exp_avg": a._mflat[self.which][o:o + k].view(shape).clone(),
-                        "exp_avg_sq": a._vflat[self.which][o:o + k].view(shape).clone()}
-        group = {"lr": float(a._lr[0]) if self.which == 0 else float(a._lr_hist[0]), "betas": tuple(a.betas), "eps": a.adam_eps, "weight_decay": a.weight_decay,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "params": list(range(len(self._entries())))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_state_dict(self, sd):
-        a = self.algo
-        for i, n in enumerate(self._entries()):
-            if i in sd["state"]:
-                e = sd["state"][i]
-                o, k, _ = a._slice_of[n]
-                a._mflat[self.which][o:o + k].copy_(e["exp_avg"].reshape(-1).to(a.device))
-                a._vflat[self.which][o:o + k].copy_(e["exp_avg_sq"].reshape(-1).to(a.device))
-                a._adam_step[self.which] = float(e["step"])
-        if self.which == 0:
-            a._lr[:] = float(sd["param_groups"][0]["lr"])
-
-    @property
-    def param_groups(self):
-        return [{"lr": float(self.algo._lr[0])}]
-
-
-class PPO:
+class PPO(OnDeviceAgent):
     def __init__(self, env, config, log_dir=None, device="cpu"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.PbhcError("pbhc_amd.agents.ppo_mimic.PPO runs on the GPU only")
-        self.env = env
-        self.config = config
-        self.log_dir = log_dir
-        self.writer = _make_writer(log_dir)
-        self.start_time = self.stop_time = 0
-        self.collection_time = self.learn_time = 0
-        self._timer = PhaseTimer()
-        self._init_config()
-        self.tot_timesteps = 0
-        self.tot_time = 0
-        self.current_learning_iteration = 0
-        self.ep_infos = []
-        self.rewbuffer = deque(maxlen=100)
-        self.lenbuffer = deque(maxlen=100)
-        N = self.env.num_envs
-        self.cur_reward_sum = torch.zeros(N, dtype=torch.float, device=self.device)
-        self.cur_episode_length = torch.zeros(N, dtype=torch.float, device=self.device)
-        self._ep_stats = torch.zeros(3, dtype=torch.float64, device=self.device)
-        self.world_size, self.rank = pdist.world(), pdist.rank()
-        self._dp = pdist.active()                    # data-parallel exchanges on (more than one rank, or a forced one-rank rehearsal)
-        # algo.config.sync_env_statistics: "rollout" (default; True means the same) | "step" (exact single-process equivalence) | False
-        self._stat_mode = {True: "rollout", False: None, None: None}.get(config.get("sync_env_statistics", "rollout"), config.get("sync_env_statistics", "rollout"))
-        if self._dp and self._stat_mode and hasattr(self.env, "enable_global_statistics"):
-            self.env.enable_global_statistics(mode=self._stat_mode)     # sigma / episode-length curricula from the batch of all ranks' envs
-        _ = self.env.reset_all()
+        super().__init__(env, config, log_dir, device)
         self.learn = self.learn_RL if not self.train_distill else self.learn_distill
 
     def _init_config(self):
+        super()._init_config()
         c = self.config
         self.num_envs = self.env.config.num_envs
-        self.algo_obs_dim_dict = self.env.config.robot.algo_obs_dim_dict
-        self.num_act = self.env.config.robot.actions_dim
-        self.save_interval = c.save_interval
-        self.logging_interval = c.get("logging_interval", 10)
-        self.num_steps_per_env = c.num_steps_per_env
-        self.load_optimizer = c.load_optimizer
-        self.num_learning_iterations = c.num_learning_iterations
-        self.init_at_random_ep_len = c.init_at_random_ep_len
-        self.desired_kl = c.desired_kl
-        self.schedule = c.schedule
         self.learning_rate = c.learning_rate
-        self.clip_param = c.clip_param
-        self.num_learning_epochs = c.num_learning_epochs
-        self.num_mini_batches = c.num_mini_batches
-        self.gamma = c.gamma
-        self.lam = c.lam
-        self.value_loss_coef = c.value_loss_coef
-        self.entropy_coef = c.entropy_coef
-        self.max_grad_norm = c.max_grad_norm
-        self.use_clipped_value_loss = c.use_clipped_value_loss
-        self.num_rew_fn = self.env.num_rew_fn
         self.priv_reg_coef_schedual = c.priv_reg_coef_schedual
         self.counter = 0
         self.train_distill = c.get("teacher_model_path", None) is not None
@@ -174,13 +79,6 @@ class PPO:
         self.config.teacher_module_dict = md
 
     # ------------------------------------------------------------------------------------
-    def setup(self):
-        from .gemm_tuning import enable as _enable_gemm_tuning
-
-        _enable_gemm_tuning()
-        self._setup_models_and_optimizer()
-        self._setup_storage()
-
     def _setup_models_and_optimizer(self):
         c = self.config
         if self.env.config.use_vec_reward:
@@ -236,7 +134,6 @@ class PPO:
             self._slice_of[nme] = (o, k, tuple(p.shape))
             o += k
         self._std_slice = self._slice_of["std"][:2]
-        self._main_has_std = self._is_main("std")
         self._lr = torch.full((2,), float(self.learning_rate), device=dev)          # [0] is THE learning rate (the loss kernel adapts both)
         self._lr_hist = torch.full((1,), float(self.learning_rate), device=dev)     # hist_encoder_optimizer keeps its initial lr (ppo_mimic.py:184)
         self._adam_step = torch.zeros(2, device=dev)
@@ -245,12 +142,14 @@ class PPO:
         self._loss_scalars = torch.zeros(4, device=dev)
         self._g_sigma = torch.zeros(self.num_act, device=dev)
         self.betas, self.adam_eps, self.weight_decay = (0.9, 0.999), 1e-8, 0.01     # torch.optim.AdamW defaults
-        self.optimizer = _FlatAdamWView(self, 0)
-        self.hist_encoder_optimizer = _FlatAdamWView(self, 1)
+        # kept for checkpoint (de)serialisation in torch.optim.AdamW's format.  `optimizer`: AdamW over every parameter — distillation: over
+        # the actor's (ppo_mimic.py:186-187) — of which only the main segment is ever stepped; `hist_encoder_optimizer`: the history encoder
+        names = [n for n, _ in named if not self.dagger_only or n.startswith("actor_module.")]
+        ent = lambda ns, live: [(*self._slice_of[n], live(n)) for n in ns]
+        self.optimizer = FlatAdamView(self, ent(names, self._is_main), self._mflat[0], self._vflat[0], self._adam_step[0:1], self._lr, self.weight_decay)
+        self.hist_encoder_optimizer = FlatAdamView(self, ent([n for n in names if n.startswith("actor_module.history_encoder.")], lambda n: True),
+                                                   self._mflat[1], self._vflat[1], self._adam_step[1:2], self._lr_hist, self.weight_decay, load_lr=False)
         # every update zeroes its segment of `_gflat` before its backward: the MLP stacks may store their gradients into it directly
-        from . import fused_mlp
-        from .modules import BaseModule
-
         self._direct_stacks = {"main": [], "hist": []}
         lo = self._gflat.data_ptr()
         for m in self.alg.modules():
@@ -262,41 +161,15 @@ class PPO:
     def _zero_grads(self, which):
         """zero one segment of the flat gradient buffer ("main": everything but the history encoder, "hist": the history encoder) and tell
         the declared stacks living in it that their next backward may store instead of accumulate"""
-        from . import fused_mlp
-
         (self._gflat[: self._n_main] if which == "main" else self._gflat[self._o_hist:]).zero_()
         for q in self._direct_stacks[which]:
             fused_mlp.grads_zeroed(q)
 
     def _setup_storage(self):
-        st = self.storage = RolloutStorage(self.env.num_envs, self.num_steps_per_env, self.device)
         S = len(self.env.tar_obs_steps)
-        self._obs_width = {}
-        for k, d in self.algo_obs_dim_dict.items():
-            w = d * S if k in ("future_motion_targets", "teacher_future_motion_targets") else d      # ppo_mimic.py:206-216
-            self._obs_width[k] = w
-            st.register_key(k, shape=(w,), dtype=torch.float, pad_rows=True, tail_slab=True)
-        st.register_key("actions", shape=(self.num_act,), dtype=torch.float)
-        st.register_key("rewards", shape=(self.num_rew_fn,), dtype=torch.float)
-        st.register_key("dones", shape=(1,), dtype=torch.bool)
-        st.register_key("values", shape=(self.num_rew_fn,), dtype=torch.float)
-        st.register_key("returns", shape=(self.num_rew_fn,), dtype=torch.float)
-        st.register_key("advantages", shape=(1,), dtype=torch.float)
-        st.register_key("actions_log_prob", shape=(1,), dtype=torch.float)
-        st.register_key("action_mean", shape=(self.num_act,), dtype=torch.float)
-        st.register_key("action_sigma", shape=(self.num_act,), dtype=torch.float)
-        if self.train_distill:
-            st.register_key("teacher_actions", shape=(self.num_act,), dtype=torch.float)
-        T, N = self.num_steps_per_env, self.env.num_envs
-        self._gae_stats = torch.zeros(2 * ((T * N + 255) // 256) + 4, dtype=torch.float64, device=self.device)
-        self._last_obs = {k: st.with_tail(k)[T] for k in self._obs_width}      # the observations after the last step: slab T of the same buffers
-        self._sample_seed = pdist.rank_seed(int(torch.randint(0, 2**62, (1,)).item()))
-        if not hasattr(self.env, "globals") or not hasattr(self.env, "set_obs_outputs"):
-            raise _lib.PbhcError("pbhc_amd PPO drives the fused pbhc_amd env (needs env.globals / env.set_obs_outputs)")
-        self._mb = (T * N) // self.num_mini_batches
-        self._loss_scratch = torch.zeros(_lib.lib().pbhc_ppo_loss_scratch_floats(self._mb), device=self.device)
-        self._grad_mu = torch.zeros(self._mb, self.num_act, device=self.device)
-        self._grad_value = torch.zeros(self._mb, self.num_rew_fn, device=self.device)
+        # ppo_mimic.py:206-216: the future targets of all S steps in one row
+        self._obs_width = {k: d * S if k in ("future_motion_targets", "teacher_future_motion_targets") else d for k, d in self.algo_obs_dim_dict.items()}
+        self._register_storage(self._obs_width, {"teacher_actions": self.num_act} if self.train_distill else {})
 
     def _eval_mode(self):
         self.alg.eval()
@@ -330,51 +203,21 @@ class PPO:
 
     # ---- learn loop (ppo_mimic.py:267-311) ---------------------------------------------------
     def learn_RL(self, num_iterations=None):
-        if self.init_at_random_ep_len:
-            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
-        obs_dict = self.env.reset_all()
-        self._train_mode()
-        n = self.num_learning_iterations if num_iterations is None else num_iterations
-        tot_iter = self.current_learning_iteration + n
-        for it in range(self.current_learning_iteration, tot_iter):
-            self.hist_encoding = it % self.dagger_update_freq == 0
-            self._timer.start()
-            obs_dict = self._rollout_step(obs_dict)           # ends with _timer.split(): collection | learning
+        def train():
             loss_dict = self._training_step()
-            if self.hist_encoding:
-                loss_dict = self._training_step_dagger()
-            self._timer.split()
-            self._post_epoch_logging(dict(it=it, loss_dict=loss_dict, num_learning_iterations=n))
-            if self.log_dir is not None and it % self.save_interval == 0 and self.rank == 0:
-                self.current_learning_iteration = it
-                self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
-            self.ep_infos.clear()
-        self.current_learning_iteration = tot_iter
-        if self.log_dir is not None and self.rank == 0:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+            return self._training_step_dagger() if self.hist_encoding else loss_dict
+
+        def before(it):
+            self.hist_encoding = it % self.dagger_update_freq == 0
+
+        self._learn_loop(num_iterations, self._rollout_step, train, before)
 
     # ---- distillation (ppo_mimic.py:313-357,533-549,711-724) ----------------------------------
     def learn_distill(self, num_iterations=None):
-        if self.init_at_random_ep_len:
-            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
-        obs_dict = self.env.reset_all()
-        self._train_mode()
-        n = self.num_learning_iterations if num_iterations is None else num_iterations
-        tot_iter = self.current_learning_iteration + n
-        for it in range(self.current_learning_iteration, tot_iter):
+        def before(it):
             self.hist_encoding = True
-            self._timer.start()
-            obs_dict = self._rollout_step_distill(obs_dict)
-            loss_dict = self._training_step_distill()
-            self._timer.split()
-            self._post_epoch_logging(dict(it=it, loss_dict=loss_dict, num_learning_iterations=n))
-            if self.log_dir is not None and it % self.save_interval == 0 and self.rank == 0:
-                self.current_learning_iteration = it
-                self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
-            self.ep_infos.clear()
-        self.current_learning_iteration = tot_iter
-        if self.log_dir is not None and self.rank == 0:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+        self._learn_loop(num_iterations, self._rollout_step_distill, self._training_step_distill, before)
 
     def teacher_actor_act_step(self, obs_dict, hist_encoding=True):
         return self.teacher_actor(obs_dict, hist_encoding, obs_key="teacher_actor_obs", target_key="teacher_future_motion_targets")
@@ -447,7 +290,7 @@ class PPO:
         """once per update, on the shuffled [T * N, C] tensors: the actor's and the critic's first-layer inputs with their observation columns in
         place — [actor_obs | (motion embedding, latent)] and [actor_obs | priv_obs | (motion embedding)] — so that an optimiser step copies 19 + 13 MB
         of encoder outputs where four `torch.cat` moved 110 MB (PBHC_ASSEMBLE_INPUTS=0: the concatenations)"""
-        if os.environ.get("PBHC_ASSEMBLE_INPUTS", "1") == "0" or not all(k in shuffled for k in ("actor_obs", "priv_obs")):
+        if not switch_on("PBHC_ASSEMBLE_INPUTS") or not all(k in shuffled for k in ("actor_obs", "priv_obs")):
             return
         a = self.alg.actor
         ao, po = shuffled["actor_obs"], shuffled["priv_obs"]
@@ -464,198 +307,73 @@ class PPO:
         shuffled["_xin_actor"], shuffled["_xin_critic"] = bufs
 
     def _rollout_step(self, obs_dict):
-        """ppo_mimic.py:371-438.  Per control step: encoders + actor + critic forward, ONE sample/log-prob/buffer-write kernel, the fused env
-        step writing the next observations into the next rollout slab, ONE bootstrap/done/episode-stat kernel.  Round 4, as MHPPO's rollout
-        (mh_ppo.py `_rollout_step`): the MLP stacks (actor, critic, privileged encoder) run as ONE launch each from packed weights — constant
-        over the rollout — and the T control steps are ONE captured hipGraph (fork / join edges instead of stream events; the steps read the
-        replay frame from the device-side cursor); the first rollout, and any rollout the env cannot promise to be free of host-side events
-        (`rollout_graph_safe`), runs the loop step by step with one captured forward per step."""
-        from . import fused_mlp
-        from .mh_ppo import MHPPO
-
-        st, env, lib = self.storage, self.env, _lib.lib()
-        T, N, A, R = self.num_steps_per_env, env.num_envs, self.num_act, self.num_rew_fn
+        """ppo_mimic.py:371-438 through agents/rollout.py.  Per control step: encoders + actor (+ critic) forward, sampling, the fused env step,
+        ONE bootstrap/done/episode-stat kernel.  The MLP stacks (actor, critic, privileged encoder; PBHC_STACK_NETS_V2=0: none) run as ONE launch
+        each from packed weights; the actor stack reads [actor_obs | motion embedding | latent] as three column segments (no concatenated copy)
+        and samples in its last epilogue.  The critic runs once after the loop on the motion embeddings the per-step forwards left in
+        `_emb_buf` (PBHC_CRITIC_BATCHED=0: the critic stack inside every control step, the plain `_forward`)."""
+        st, env, a = self.storage, self.env, self.alg.actor
+        T, N, A = self.num_steps_per_env, env.num_envs, self.num_act
         keys = list(self._obs_width.keys())
-        K = _lib.K
-        counter = env.globals[K["PBHC_G_STEP_COUNTER"]:].data_ptr()
+        mode = bool(self.hist_encoding)                    # the captured forward depends on the latent source
+        batched = rollout.critic_batched(env)
         with torch.inference_mode():
             sigma = self.__dict__.get("_sigma_buf")
             if sigma is None:
                 sigma = self._sigma_buf = torch.empty(A, device=self.device)          # fixed address: the captured sampling kernel reads it
             sigma.copy_(self.alg.sigma())
-            for k in keys:
-                getattr(st, k)[0].copy_(obs_dict[k])
-            mode = bool(self.hist_encoding)                    # the captured forward depends on the latent source
-            a = self.alg.actor
-            split = os.environ.get("PBHC_ROLLOUT_SPLIT", "1") != "0" and hasattr(env, "set_finalize_stream")
-            # The critic's values feed only the time-out bootstrap and GAE, both after the rollout: evaluated ONCE over all T + 1 slabs
-            # (whole-chip GEMM tiles) on the motion embeddings the per-step forwards left in `_emb_buf`, as MHPPO does (PBHC_CRITIC_BATCHED=0:
-            # the critic stack inside every control step)
-            batched = split and os.environ.get("PBHC_CRITIC_BATCHED", "1") != "0"
+            if batched and (self.__dict__.get("_emb_buf") is None or self._emb_buf.shape != (T + 1, N, a.motion_encoder.output_dim)):
+                self._emb_buf = torch.zeros(T + 1, N, a.motion_encoder.output_dim, device=self.device)
             nets = (a.actor_module, a.priv_encoder) if batched else (a.actor_module, self.alg.critic, a.priv_encoder)
-            stacks = [m.module for m in nets if m is not None and isinstance(m, BaseModule) and m._fused]
-            stacks = [q for q in stacks if os.environ.get("PBHC_STACK_NETS_V2", "1") != "0" and fused_mlp.pack_stack(q)]
-            encoders = [e for e in (a.motion_encoder, a.history_encoder if mode else None) if e is not None and hasattr(e, "prepare_inference")]
-            for e in encoders:
-                e.prepare_inference()                          # weights re-laid-out once per rollout, in place (the captured graph reads them)
-            if batched:
-                E = a.motion_encoder.output_dim
-                if self.__dict__.get("_emb_buf") is None or self._emb_buf.shape != (T + 1, N, E):
-                    self._emb_buf = torch.zeros(T + 1, N, E, device=self.device)
-                    self._time_outs = torch.zeros(T, N, 1, dtype=torch.bool, device=self.device)
-            fuse_sample = False
-            try:
-                if batched:
-                    # the actor stack reads [actor_obs | motion embedding | latent] as three column segments (no concatenated copy) and samples in
-                    # its last epilogue, keyed by a snapshot of the step counter + the step index: the keys pbhc_policy_sample forms from the live
-                    # counter, without waiting for the previous step's reduction (as MHPPO; PBHC_FUSED_SAMPLE=0: the separate sampling kernel)
-                    a_seq = a.actor_module.module if isinstance(a.actor_module, BaseModule) else None
-                    cat_ok = a_seq is not None and any(q is a_seq for q in stacks)
-                    fuse_sample = cat_ok and os.environ.get("PBHC_FUSED_SAMPLE", "1") != "0"
-                    if fuse_sample:
-                        if self.__dict__.get("_ctr0") is None:
-                            self._ctr0 = torch.zeros(1, dtype=torch.float64, device=self.device)
-                        env.wait_finalize()
-                        self._ctr0.copy_(env.globals[K["PBHC_G_STEP_COUNTER"]:K["PBHC_G_STEP_COUNTER"] + 1])
+            a_seq = a.actor_module.module if isinstance(a.actor_module, BaseModule) else None
+            P = lambda x: x.data_ptr()
 
-                    def eager_fwd(t):
-                        b = {k: getattr(st, k)[t] for k in keys}
-                        emb = a.motion_encoder(b["future_motion_targets"], out=self._emb_buf[t])
-                        latent = a.history_encoding(b["prop_history"]) if mode else a.priv_encoding(b["priv_obs"])
-                        xs = [b["actor_obs"], emb, latent]
-                        if fuse_sample:
-                            smp = dict(std=sigma, seed=self._sample_seed, counter=self._ctr0.data_ptr(), counter_offset=t, actions=st.actions[t],
-                                       action_mean=st.action_mean[t], action_sigma=st.action_sigma[t], logp=st.actions_log_prob[t])
-                            if fused_mlp.forward_cat_inference(a_seq, xs, sample=smp) is False:
-                                raise _lib.PbhcError("pbhc_mlp_fwd_cat does not apply to this policy (PBHC_FUSED_SAMPLE=0)")
-                            return st.action_mean[t], None
-                        mu = fused_mlp.forward_cat_inference(a_seq, xs) if cat_ok else False
-                        return (a.actor_module(torch.cat(xs, dim=-1)) if mu is False else mu), None
-                else:
-                    eager_fwd = lambda t: self._forward({k: getattr(st, k)[t] for k in keys}, mode)[:2]
-                # the dependent chain of a control step is env step -> policy forward -> sampling -> env step; the env step's one-workgroup
-                # reduction and the bootstrap / episode-statistics kernel run next to the policy forward on a branch stream (joined before the
-                # sampling kernel, which reads the step counter the reduction advances)
-                cur = torch.cuda.current_stream()
-                br = None
-                if split:
-                    br = self.__dict__.get("_branch_stream") or torch.cuda.Stream(device=self.device)
-                    self._branch_stream = br
-                    env.set_finalize_stream(br)
-                post_done = [self.__dict__.setdefault("_post_done", torch.cuda.Event())]
-                sc = self.__dict__.get("_step_ptrs")
-                if sc is None or sc[0] is not st or sc[2] != batched:
-                    P = lambda x: x.data_ptr()
-                    sc = (st, [dict(sample=(P(st.actions[t]), P(st.action_mean[t]), P(st.action_sigma[t]), P(st.actions_log_prob[t]), None if batched else P(st.values[t])),
-                                    post=(P(st.rewards[t]), P(st.dones[t])), values=None if batched else P(st.values[t]),
-                                    tout=P(self._time_outs[t]) if batched else None, act={"actions": st.actions[t]},
-                                    obs_out={k: getattr(st, k)[t + 1] for k in keys} if t + 1 < T else self._last_obs) for t in range(T)], batched)
-                    self._step_ptrs = sc
-                steps = sc[1]
-                sum_p, len_p, stat_p, gamma = self.cur_reward_sum.data_ptr(), self.cur_episode_length.data_ptr(), self._ep_stats.data_ptr(), float(self.gamma)
+            def forward(t):
+                b = {k: getattr(st, k)[t] for k in keys}
+                if not batched:
+                    return self._forward(b, mode)[:2]
+                emb = a.motion_encoder(b["future_motion_targets"], out=self._emb_buf[t])
+                latent = a.history_encoding(b["prop_history"]) if mode else a.priv_encoding(b["priv_obs"])
+                xs = [b["actor_obs"], emb, latent]
+                if d.fuse_sample:
+                    smp = dict(std=sigma, seed=self._sample_seed, counter=self._ctr0.data_ptr(), counter_offset=t, actions=st.actions[t],
+                               action_mean=st.action_mean[t], action_sigma=st.action_sigma[t], logp=st.actions_log_prob[t])
+                    if fused_mlp.forward_cat_inference(a_seq, xs, sample=smp) is False:
+                        raise _lib.PbhcError("pbhc_mlp_fwd_cat does not apply to this policy (PBHC_FUSED_SAMPLE=0)")
+                    return st.action_mean[t], None
+                mu = fused_mlp.forward_cat_inference(a_seq, xs) if any(q is a_seq for q in d.packed) else False
+                return (a.actor_module(torch.cat(xs, dim=-1)) if mu is False else mu), None
 
-                def run_loop(cur, fwd_call):
-                    stream = cur.cuda_stream
-                    if split:
-                        br.wait_stream(cur)
-                    for t in range(T):
-                        sp = steps[t]
-                        mu, value = fwd_call(t)
-                        if split and t > 0:
-                            cur.wait_event(post_done[0])
-                            env.finalize_joined()
-                        if not fuse_sample:
-                            _lib.check(lib.pbhc_policy_sample(mu.data_ptr(), sigma.data_ptr(), None if batched else value.data_ptr(), N, A, R, self._sample_seed, counter,
-                                                              *sp["sample"], stream), "pbhc_policy_sample")
-                        env.set_obs_outputs(sp["obs_out"])
-                        nxt, rewards, dones, infos = env.step(sp["act"])
-                        ps = br.cuda_stream if split else stream
-                        # (batched critic: values == NULL — the time-out bootstrap is added after the loop — and the step's time-out flags are kept)
-                        _lib.check(lib.pbhc_rollout_post2(rewards.data_ptr(), sp["values"], dones.data_ptr(), infos["time_outs"].data_ptr(), N, R, gamma, *sp["post"],
-                                                          sum_p, len_p, stat_p, sp["tout"], ps), "pbhc_rollout_post2")
-                        if split:
-                            post_done[0].record(br)
-                    if split:
-                        cur.wait_stream(br)
-
-                graph_ok = (os.environ.get("PBHC_ROLLOUT_GRAPH", "1") != "0" and split and self.__dict__.get("_rollouts_done", 0) >= 1
-                            and not self.__dict__.get("_rollout_graph_failed", False) and hasattr(env, "rollout_graph_safe") and env.rollout_graph_safe(T))
-                ran = False
-                if graph_ok:
-                    env.simulator.use_device_cursor()
-                    key = (id(st), env._io_epoch, env.simulator.replay_version, bool(getattr(env, "is_specialised", False)), N, T, mode, bool(stacks), batched, fuse_sample)
-                    gc = self.__dict__.get("_rollout_graph")
-                    if gc is None or gc[0] != key:
-                        gc = MHPPO._capture_rollout(self, key, run_loop, eager_fwd, env, post_done, T)
-                    if gc is not None:
-                        gc[1].replay()
-                        env.after_graph_steps(T)
-                        ran = True
-                self._rollout_used_graph = ran
-                if not ran:
-                    run_loop(cur, policy_forward_graphs(self, eager_fwd, key=(mode, bool(stacks), batched, fuse_sample)))      # (one captured forward per step)
-                if split:
-                    env.set_finalize_stream(None)
-            finally:
-                for q in stacks:
-                    fused_mlp.release_stack(q)
-                for e in encoders:
-                    e.release_inference()
-            last_values = None
-            if batched:
-                # ppo_mimic.py:384-386, 425-431 for all steps at once: values of every slab + the bootstrap values of GAE (slab T: the
-                # observations after the last step) from one launch set, then rewards += gamma * values * time_outs
+            def critic_rows():
                 self._emb_buf[T].copy_(a.motion_encoding(self._last_obs["future_motion_targets"]))
                 rows = lambda k: st.with_tail(k).flatten(0, 1)
-                vals = self.alg.critic(torch.cat([rows("actor_obs"), rows("priv_obs"), self._emb_buf.flatten(0, 1)], dim=-1)).view(T + 1, N, R)
-                st.values.copy_(vals[:T])
-                st.rewards.addcmul_(st.values, self._time_outs.to(torch.float32), value=float(self.gamma))
-                last_values = vals[T]
-            st.step = T
-            self._rollouts_done = self.__dict__.get("_rollouts_done", 0) + 1
-            if self._dp and self._stat_mode == "rollout":
-                self.env.sync_globals()                # sigma / curricula / log means: the mean over the ranks, once per rollout
-            self._timer.split()
-            self._compute_returns(self._last_obs, last_values=last_values)
-        return self._last_obs
+                return torch.cat([rows("actor_obs"), rows("priv_obs"), self._emb_buf.flatten(0, 1)], dim=-1)
 
-    def _compute_returns(self, last_obs_dict, last_values=None):
-        """ppo_mimic.py:443-491 in one HIP pass (scalar reward: R = 1, normalisation over all [T,N] entries)."""
-        st = self.storage
-        if last_values is None:
-            last_values = self.alg.evaluate(last_obs_dict).detach()
-        last_values = last_values.contiguous()
-        T, N, R = self.num_steps_per_env, self.env.num_envs, self.num_rew_fn
-        adv = st.advantages
-        _lib.check(_lib.lib().pbhc_gae(st.rewards.data_ptr(), st.values.data_ptr(), st.dones.data_ptr(), last_values.data_ptr(), T, N, R,
-                                       float(self.gamma), float(self.lam), st.returns.data_ptr(), adv.data_ptr(), self._gae_stats.data_ptr(),
-                                       _lib.current_stream()), "pbhc_gae")
-        if self._dp:
-            nb = (T * N + 255) // 256
-            mean_l, std_l = self._gae_stats[2 * nb].float(), self._gae_stats[2 * nb + 1].float()
-            adv.copy_(pdist.global_normalize_(adv * (std_l + 1e-8) + mean_l))
-        return st.returns, adv
+            d = rollout.RolloutSpec(
+                keys=keys, batched=batched, forward=forward, sigma=sigma, sample_stack=a_seq if batched else None, key_extra=(mode, batched),
+                stacks=[m.module for m in nets if m is not None and isinstance(m, BaseModule) and m._fused] if switch_on("PBHC_STACK_NETS_V2") else [],
+                encoders=[e for e in (a.motion_encoder, a.history_encoder if mode else None) if e is not None and hasattr(e, "prepare_inference")],
+                graph_allowed=lambda: True, critic=self.alg.critic, critic_rows=critic_rows,
+                sample_ptrs=lambda t: (P(st.actions[t]), P(st.action_mean[t]), P(st.action_sigma[t]), P(st.actions_log_prob[t]), None if batched else P(st.values[t])))
+            return rollout.collect(self, d, obs_dict)
+
+    def _critic_values(self, obs_dict):
+        return self.alg.evaluate(obs_dict)
 
     # ---- updates (ppo_mimic.py:493-709) ------------------------------------------------------
     UPDATE_KEYS = ["actor_obs", "priv_obs", "future_motion_targets", "prop_history", "actions", "values", "advantages", "returns", "actions_log_prob",
                    "action_mean", "action_sigma"]
 
+    METERS = ["Value", "Entropy", "Surrogate", "priv_reg_loss", "Actor_Load_Balancing_Loss", "Critic_Load_Balancing_Loss"]
+
     def _training_step(self, indices=None):
-        names = ["Value", "Entropy", "Surrogate", "priv_reg_loss", "Actor_Load_Balancing_Loss", "Critic_Load_Balancing_Loss"]
-        meters = torch.zeros(len(names) + 4, device=self.device)          # one fill: the meters and, behind them, the loss kernel's running sums
-        loss = {k: meters[i] for i, k in enumerate(names[:4])}
-        loss["_acc"] = meters[len(names):]                     # {surrogate, value, entropy, kl} summed by the loss kernel itself
+        meters, loss = self._begin_meters(self.METERS, summed=4)      # (the two load-balancing meters stay zero: no mixture-of-experts stacks here)
         for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, keys=self.UPDATE_KEYS, indices=indices,
                                                        on_gather=self._assemble_inputs):
             self._update_ppo(batch, loss)
-        acc = loss.pop("_acc")
-        loss["Surrogate"] += acc[0]; loss["Value"] += acc[1]; loss["Entropy"] += acc[2]
-        n = self.num_learning_epochs * self.num_mini_batches
-        self.storage.clear()
         self.update_counter()
         self.learning_rate = self._lr[0:1]
-        means = meters[:len(names)] / n                        # (the two load-balancing meters stay zero: no mixture-of-experts stacks here)
-        return {k: means[i] for i, k in enumerate(names)}
+        return self._end_meters(self.METERS, meters, loss)
 
     def _training_step_dagger(self, indices=None):
         loss = {"hist_latent_loss": torch.zeros((), device=self.device)}
@@ -740,10 +458,6 @@ class PPO:
     def inference_model(self):
         return {"actor": self.alg.actor}
 
-    def get_example_obs(self):
-        obs = self.env.reset_all()
-        return {k: v.clone() for k, v in obs.items()}
-
     @torch.no_grad()
     def evaluate_policy_steps(self, Nsteps):
         self._eval_mode()
@@ -759,33 +473,9 @@ class PPO:
             raise NotImplementedError("env.config.save_motion with ppo_mimic.PPO: the reference records with the motion-tracking env and MHPPO only")
         return self.evaluate_policy_steps(int(self.env.max_episode_length))
 
-    def _post_epoch_logging(self, log, width=80, pad=40):
-        self.tot_timesteps += self.num_steps_per_env * self.env.num_envs * self.world_size
-        if log["it"] % self.logging_interval != 0:
-            return
-        for c, l in self._timer.resolve():                  # device time of every iteration since the last logging interval
-            self.collection_time, self.learn_time = c, l
-            self.tot_time += c + l
-        log["collection_time"], log["learn_time"] = self.collection_time, self.learn_time
-        it_time = self.collection_time + self.learn_time
-        if self.rank != 0:
-            return
-        stats = self._ep_stats.tolist()
-        self._ep_stats.zero_()
-        fps = int(self.num_steps_per_env * self.env.num_envs * self.world_size / max(it_time, 1e-9))
-        it, w = log["it"], self.writer
-        for k, v in log["loss_dict"].items():
-            w.add_scalar("Loss/" + k, float(v), it)
+    def _log_scalars(self, w, it):
         w.add_scalar("Loss/learning_rate", float(self._lr[0]), it)
         w.add_scalar("Policy/mean_noise_std", float(self.alg.std.detach().mean()), it)
-        w.add_scalar("Perf/total_fps", fps, it)
-        w.add_scalar("Perf/collection_time", log["collection_time"], it)
-        w.add_scalar("Perf/learning_time", log["learn_time"], it)
-        if stats[2] > 0:
-            w.add_scalar("Train/mean_reward", stats[0] / stats[2], it)
-            w.add_scalar("Train/mean_episode_length", stats[1] / stats[2], it)
-        for k, v in (self.env.read_log() if hasattr(self.env, "read_log") else {}).items():
-            w.add_scalar("Env/" + k, float(v), it)
-        ld = ", ".join(f"{k} {float(v):.4f}" for k, v in log["loss_dict"].items() if "Load_Balancing" not in k)
-        print(f"[it {it}] fps {fps}  collect {log['collection_time']:.3f}s  learn {log['learn_time']:.3f}s  {ld}  lr {float(self._lr[0]):.2e}  "
-              f"ep_rew {stats[0] / max(stats[2], 1):.3f}  ep_len {stats[1] / max(stats[2], 1):.1f}", flush=True)
+
+    def _log_line(self, loss_dict):
+        return ", ".join(f"{k} {float(v):.4f}" for k, v in loss_dict.items() if "Load_Balancing" not in k) + f"  lr {float(self._lr[0]):.2e}"

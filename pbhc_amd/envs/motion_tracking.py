@@ -11,6 +11,7 @@ goes through `pbhc_env_step`; construction fails if libpbhc_hip.so is missing.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import importlib
 import os
@@ -405,6 +406,27 @@ class LeggedRobotMotionTracking:
             if nxt - self.common_step_counter <= num_steps:
                 return False
         return True
+
+    def graph_key(self):
+        """everything a captured env step froze: the io struct (its epoch moves with every pointer the env re-points), the simulator's replay
+        window (a new one is picked up lazily inside the next step(), i.e. AFTER a caller has read this key: the version itself belongs to it),
+        which kernel — generic or specialised — the launch names, and the batch size"""
+        return (self._io_epoch, self.simulator.replay_version, self.is_specialised, self.num_envs)
+
+    @contextlib.contextmanager
+    def graph_steps(self, renew_events):
+        """`with env.graph_steps(...)`: the step() calls inside are being recorded into a graph, not run.  They read the replay frame from the
+        device-side cursor from now on; the host-side counter they advance is put back (after_graph_steps advances it, per replay).
+        renew_events: the steps ran with a finalize stream — its events were recorded INSIDE the capture and are edges of the graph now, not
+        events a later eager step may wait on."""
+        self.simulator.use_device_cursor()
+        counter0 = self.common_step_counter
+        try:
+            yield
+        finally:
+            self.common_step_counter = counter0
+            if renew_events:
+                self._step_done, self._fin_done, self._fin_pending = torch.cuda.Event(), torch.cuda.Event(), False
 
     def after_graph_steps(self, num_steps):
         """host-side book-keeping of `num_steps` control steps that ran inside a graph replay"""
@@ -815,6 +837,15 @@ class LeggedRobotMotionTracking:
         if not self._rec_dumped and self._rec_steps >= self.layout.record["total_steps"] + 3:
             self._rec_dumped = True
             self._dump_motion()
+
+    @property
+    def recorded_steps(self):
+        """control steps the recorder has seen since the env was built"""
+        return self._rec_steps
+
+    def clip_of_env(self, i):
+        """the motion clip env `i` tracks (what its recording is scored against)"""
+        return self._motion_lib._clips[int(self._motion_lib.slot_clip[i])]
 
     @property
     def motion_recorded(self):

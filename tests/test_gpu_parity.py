@@ -861,6 +861,80 @@ def test_rollout_batched_critic_equals_per_step_critic(agent):
             assert torch.equal(a[k], b[k]), k
 
 
+def _l2c2_agent(enable, plain_stacks=False):
+    """one rollout + one update (a fixed permutation) of MHPPO with the L2C2 regulariser on (both weights zero) or off, from the same seeds.
+    plain_stacks: what switching L2C2 on does to the two MLP stacks — plain autograd over the library's GEMMs — without L2C2."""
+    from pbhc_amd.agents.mh_ppo import MHPPO
+
+    torch.manual_seed(11)
+    np.random.seed(11)
+    cfg, env = build_hip_env("v1_g1_23dof_walk.yaml", 64, noise_off=False,
+                             overrides={"algo.config.l2c2": {"enable": enable, "lambda_value": 0.0, "lambda_policy": 0.0}})
+    algo = MHPPO(env=env, config=cfg.algo.config, log_dir=None, device=DEV)
+    algo.setup()
+    if plain_stacks:
+        algo.actor.actor_module._fused = algo.critic.critic_module._fused = False
+    algo._train_mode()
+    algo._rollout_step(env.reset_all())
+    torch.cuda.synchronize()
+    st = algo.storage
+    out = {"rollout": {k: getattr(st, k).clone() for k in st.stored_keys}, "used_graph": algo._rollout_used_graph,
+           "tails": {k: st.with_tail(k).clone() for k in ("actor_obs", "critic_obs")}}
+    n = st.num_envs * st.num_transitions_per_env
+    algo._training_step(indices=torch.randperm(n, generator=torch.Generator().manual_seed(23)).to(DEV))
+    torch.cuda.synchronize()
+    out["update"] = {k: getattr(algo, k).clone() for k in ("_pflat", "_mflat", "_vflat", "_lr")}
+    return out
+
+
+# MHPPO's eager update (`_update_ppo_eager`) against the fused-kernel update of the default agent, after one rollout + one `_training_step` (20
+# optimiser steps) at 64 envs: per buffer (max |a - b|, ||a - b||_2 / ||b||_2), measured before the agents were refactored, once on each of two
+# MI355X machines (first / second: _pflat 2.06e-4 / 1.11e-4 and 8.24e-6 / 5.65e-6, _mflat 6.82e-7 / 3.65e-7 and 1.10e-5 / 6.93e-6, _vflat
+# 9.02e-10 / 2.10e-9 and 3.17e-6 / 4.97e-6).  Each entry is the larger of its two figures — the _pflat and _mflat pairs from the first machine, the
+# _vflat pair from the second.  The bounds are 4x these (GEMM selection differs between machines); the learning rates — a discrete branch per
+# optimiser step — were equal.
+L2C2_MEASURED = {"_pflat": (2.060011e-04, 8.240801e-06), "_mflat": (6.820774e-07, 1.096137e-05), "_vflat": (2.095476e-09, 4.965393e-06)}
+# The L2C2 agent's rollout against the DEFAULT agent's: the stacks run as plain library GEMMs + the sampling kernel there, as one packed launch with
+# the sampling in its epilogue here, so the keys agree to rounding, not bit for bit.  max |a - b| per key, the larger of the same two measurements
+# (they agreed on the observations, actions and log-probabilities; rewards 1.19e-7 / 1.53e-7, values 1.94e-7 / 1.79e-7, returns 7.15e-7 / 4.77e-7,
+# advantages 2.15e-6 / 1.67e-6, action_mean 1.64e-7 / 1.42e-7); bounds 4x.  dones and action_sigma were equal.
+L2C2_ROLLOUT_MEASURED = {"actor_obs": 2.384186e-07, "critic_obs": 2.384186e-07, "actions": 2.384186e-07, "rewards": 1.527e-07, "values": 1.937151e-07,
+                         "returns": 7.152557e-07, "advantages": 2.145767e-06, "actions_log_prob": 7.629395e-06, "action_mean": 1.639128e-07}
+
+
+def test_l2c2_rollout_keeps_next_obs_and_eager_update_matches_fused_update():
+    """The L2C2 branch of MHPPO (mh_ppo.py:488-507; `_need_next`): the rollout stays out of the hipGraph and stores the next observations of every
+    step — slab t + 1 of the same buffer; with both L2C2 weights zero the eager update it forces is the fused-kernel update to rounding, the
+    learning rates exactly.  The rollout does not depend on the update form: every key is bit-identical to the agent without L2C2 — whose stacks
+    run the way L2C2 makes them run (plain autograd over library GEMMs; against the default packed-stack forward the keys differ by rounding,
+    so that pair is held to 4x its measured differences, L2C2_ROLLOUT_MEASURED)."""
+    on, off, off_plain = _l2c2_agent(True), _l2c2_agent(False), _l2c2_agent(False, plain_stacks=True)
+    assert on["used_graph"] is False
+    T = on["rollout"]["actions"].shape[0]
+    for k in ("actor_obs", "critic_obs"):
+        for t in range(T):
+            assert torch.equal(on["rollout"]["next_" + k][t], on["tails"][k][t + 1]), (k, t)
+    assert set(on["rollout"]) - set(off["rollout"]) == {"next_actor_obs", "next_critic_obs"} and set(off["rollout"]) == set(off_plain["rollout"])
+    diff = lambda a, b: (float((a.double() - b.double()).abs().max()), float((a.double() - b.double()).norm() / b.double().norm()))
+    for k in off["rollout"]:
+        print(f"l2c2 rollout {k}: max |on - off| {diff(on['rollout'][k], off['rollout'][k])[0]:.3e}, |on - off_plain| {diff(on['rollout'][k], off_plain['rollout'][k])[0]:.3e}")
+    for k in L2C2_MEASURED:
+        print(f"l2c2 update {k}: (max abs, rel l2) on vs off {diff(on['update'][k], off['update'][k])}, on vs off_plain {diff(on['update'][k], off_plain['update'][k])}")
+    print(f"l2c2 update _lr: on {on['update']['_lr'].tolist()} off {off['update']['_lr'].tolist()}")
+    for k in off_plain["rollout"]:
+        assert torch.equal(on["rollout"][k], off_plain["rollout"][k]), k
+    assert set(off["rollout"]) == set(L2C2_ROLLOUT_MEASURED) | {"dones", "action_sigma"}
+    for k in off["rollout"]:
+        if k in L2C2_ROLLOUT_MEASURED:
+            assert diff(on["rollout"][k], off["rollout"][k])[0] <= 4 * L2C2_ROLLOUT_MEASURED[k], k
+        else:
+            assert torch.equal(on["rollout"][k], off["rollout"][k]), k
+    assert torch.equal(on["update"]["_lr"], off["update"]["_lr"])
+    for k, (m_abs, m_rel) in L2C2_MEASURED.items():
+        d_abs, d_rel = diff(on["update"][k], off["update"][k])
+        assert d_abs <= 4 * m_abs and d_rel <= 4 * m_rel, (k, d_abs, d_rel)
+
+
 def test_learn_runs_two_iterations():
     from pbhc_amd.agents.mh_ppo import MHPPO
 
