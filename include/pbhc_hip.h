@@ -445,10 +445,8 @@ typedef struct PbhcStepIO {
    * env in this step, after its torques and before its observations — `_update_tasks_callback` with domain_rand.reinit_epis_rand > 0
    * (legged_robot_base.py:390-395 -> _episodic_domain_randomization(all env ids) :599-635).  Same draws as a reset's (Philox streams / ovr_*). */
   int32_t redraw_all;
-  /* written by pbhc_env_step_launch itself (callers leave it 0): 1 when every observation row may be stored 16 bytes per lane — obs[g]
-   * 16-byte aligned, its pitch a multiple of 4 floats and >= the row width rounded up to 4 (the env-owned and the rollout-buffer rows are:
-   * padded to 128-byte lines); the words between a row's width and that bound are then written (zeros). */
-  int32_t obs_wide;
+  /* reserved: callers leave it 0, the library ignores it (it keeps the struct's size and the kernel-argument offsets of ABI version 11) */
+  int32_t reserved0;
 } PbhcStepIO;
 
 /* The evaluation recorder (env.config.save_motion, motion_tracking.py:140-170,861-938): device-resident [N,T,...] buffers, T = total_steps =

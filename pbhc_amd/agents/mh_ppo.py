@@ -36,7 +36,6 @@ class MHPPO(OnDeviceAgent):
         self.actor_learning_rate = c.actor_learning_rate
         self.critic_learning_rate = c.critic_learning_rate
         self.cfg_l2c2 = c.l2c2 if "l2c2" in c else None
-        self._dp_buckets = int(switch("PBHC_DP_GRAD_BUCKETS"))
 
     # ------------------------------------------------------------------------------------
     def _setup_models_and_optimizer(self):
@@ -116,7 +115,6 @@ class MHPPO(OnDeviceAgent):
             self.critic.critic_module._fused = False
         obs = self.algo_obs_dim_dict
         self._register_storage(obs, {"next_" + k: d for k, d in obs.items()} if self._need_next else {})
-        self._update_streams = switch_on("PBHC_UPDATE_STREAMS")      # measured slower (37.0 vs 34.5 ms per update): off
 
     def _eval_mode(self):
         self.actor.eval(); self.critic.eval()
@@ -257,23 +255,10 @@ class MHPPO(OnDeviceAgent):
         if self._need_next:
             return self._update_ppo_eager(b, loss)
         lib = _lib.lib()
-        # The two networks are independent until the loss kernel: the critic's forward runs on the branch stream next to the actor's, and
-        # autograd replays each backward on the stream its forward ran on — the narrow layers of one network (128 / 23 / 21 columns: fewer
-        # output tiles than CUs) share the chip with the wide layers of the other.  Measured on MI355X (4096 envs): 37.0 ms per update
-        # against 34.5 ms on one stream — the wide GEMMs are tuned to own the chip and lose more than the narrow ones gain — so this
-        # stays an experiment behind PBHC_UPDATE_STREAMS=1.
-        two = self._update_streams
-        cur, br = torch.cuda.current_stream(), self._branch_stream
-        if two:
-            br.wait_stream(cur)
-            with torch.cuda.stream(br):
-                value = self.critic.critic_module(b["critic_obs"])
-            mu = self.actor.actor_module(b["actor_obs"])
-            cur.wait_stream(br)
-            value.record_stream(cur)                     # allocated on the branch stream, read by the loss kernel on this one
-        else:
-            mu = self.actor.actor_module(b["actor_obs"])
-            value = self.critic.critic_module(b["critic_obs"])
+        # One stream for both networks: with the critic on a stream of its own the update measured 37.0 ms against 34.5 ms (MI355X, 4096 envs) —
+        # the wide GEMMs are tuned to own the chip and lose more than the narrow ones gain.
+        mu = self.actor.actor_module(b["actor_obs"])
+        value = self.critic.critic_module(b["critic_obs"])
         B = mu.shape[0]
         if B != self._mb:
             raise _lib.PbhcError("minibatch size changed")
@@ -293,28 +278,13 @@ class MHPPO(OnDeviceAgent):
             # ONE all-reduce per optimiser step (north_star: "a single RCCL all-reduce of policy gradients per PPO update"): actor + critic
             # segments and, in the slot behind them, the minibatch KL mean (the adaptive learning-rate rule, mh_ppo.py:455-466, needs the
             # mean over ALL ranks' samples) — averaged by the collective itself (ReduceOp.AVG), 5.2 MB, latency-bound on xGMI.
-            # PBHC_DP_GRAD_BUCKETS=2: the round-2 form — the critic's 3.8 MB exchanged while the actor's backward runs, the actor's 1.45 MB
-            # exposed — one more collective launch per step for ~25 us of hidden wire time; bench.py's dp1_rehearsal is the meter.
             self._gflat[na + nc:na + nc + 1].copy_(self._loss_scalars[3:4])
-            if self._dp_buckets == 2:
-                torch.autograd.backward([value], [self._grad_value])
-                h_c = pdist.all_reduce(self._gflat[na:na + nc + 1], async_op=True)
-                torch.autograd.backward([mu], [self._grad_mu])
-                h_a = pdist.all_reduce(self._gflat[:na], async_op=True)
-                h_a.wait(); h_c.wait()
-                self._gflat.div_(self.world_size)
-            else:
-                self._backward_both(mu, value)
-                pdist.allreduce_mean_(self._gflat[:na + nc + 1])
+            self._backward_both(mu, value)
+            pdist.allreduce_mean_(self._gflat[:na + nc + 1])
             if adapt:                                    # the rule on the all-rank KL mean: one launch (pdist.kl_lr_rule_ is its host-tensor form)
                 _lib.check(lib.pbhc_kl_lr_rule(self._lr.data_ptr(), 2, self._gflat[na + nc:].data_ptr(), float(self.desired_kl), st), "pbhc_kl_lr_rule")
         else:
-            if two:
-                br.wait_stream(cur)                      # the loss kernel's gradients are ready for the critic's backward on its stream
-                torch.autograd.backward([mu, value], [self._grad_mu, self._grad_value])
-                cur.wait_stream(br)
-            else:
-                self._backward_both(mu, value)
+            self._backward_both(mu, value)
         self._adam2(zero_grad=1)
         self._gflat_clean = True
         if "_acc" not in loss:                            # ("_acc": summed by the loss kernel's finishing block)

@@ -5,13 +5,9 @@
 // pbhc_env_attach_specialised).  Expects <hip/hip_runtime.h>, include/pbhc_hip.h, pbhc_math.h and `using namespace pbhc` before it.
 #pragma once
 
-#ifndef PBHC_G
 #define PBHC_G 32     // lanes per env
-#endif
-#ifndef PBHC_EPB
 #define PBHC_EPB 4    // envs per workgroup
-#endif
-#define PBHC_NP 64    // partial sums per workgroup
+#define PBHC_NP 64   // partial sums per workgroup
 
 #ifdef PBHC_STATIC_CFG
 #include PBHC_STATIC_CFG
@@ -138,7 +134,6 @@ __device__ const PartTab kPartTab[4] = {make_part_tab(false, false), make_part_t
 // v_add_f32_dpp / v_max_f32_dpp), and one v_permlane16_swap_b32 (gfx950) exchanges the odd rows of one copy with the even rows of the
 // other, so rows {0,1} and {2,3} — the two envs of the wave — each end up holding their 32-lane result: 7 instructions, no LDS.
 // Inactive lanes read as 0 (bound_ctrl), a row never mixes envs, and the swap pairs row 0 with 1 and row 2 with 3 only.
-#if PBHC_G == 32
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
@@ -158,37 +153,13 @@ __device__ __forceinline__ float group_max(float v) {      // operands are >= 0 
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_int(v), __float_as_int(v), false, false);
   return fmaxf(__int_as_float(r[0]), __int_as_float(r[1]));
 }
-#else
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int m = PBHC_G / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, PBHC_G);
-  return v;
-}
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int m = PBHC_G / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, PBHC_G));
-  return v;
-}
-#endif
 // element `i` of a tensor at a UNIFORM base pointer with the byte offset formed in 32 bits: the compiler emits the SGPR-base form of
 // global_load / global_store (one 32-bit offset VGPR per access instead of a 64-bit address built in the VALU).  Callers keep
 // (elements x sizeof) below 2^32 (checked on the host at pbhc_env_create / pbhc_env_step).
 // Outputs of the step are STREAMING stores (round 4): nothing in this launch reads them back, and as ordinary stores their 27 MB per 4096 envs
 // allocate in — and wash out — the XCDs' L2 that also serves the launch's own reads: 18.0 -> 17.1 us at 4096 envs, 100 -> 89.6 us at 32 768 on
-// one box (profiles/round4_k_env_step_variants.txt (j)).  -DPBHC_NO_NT_STORES: ordinary stores.
-#ifndef PBHC_NO_NT_STORES
+// one box (profiles/round4_k_env_step_variants.txt (j)).  Loads stay ordinary: streaming loads of the per-env inputs measured slower ((k) there).
 #define NTST(lhs, v) __builtin_nontemporal_store((v), &(lhs))
-#else
-#define NTST(lhs, v) ((lhs) = (v))
-#endif
-// ... and the per-env inputs (replay frame, env state, history: each read by exactly one lane of one launch) as streaming loads
-// (-DPBHC_NT_LOADS, measurement: see (k) in the variants file); the motion table's rows and the constant tables stay ordinary loads — those
-// are what the L2 is for
-#ifdef PBHC_NT_LOADS
-#define NTLD(expr) __builtin_nontemporal_load(&(expr))
-#else
-#define NTLD(expr) (expr)
-#endif
 typedef float pbhc_f32x4 __attribute__((ext_vector_type(4)));
 template <class T> __device__ __forceinline__ T& at(T* p, unsigned int i) { return *(T*)((char*)p + (size_t)(unsigned int)(i * (unsigned int)sizeof(T))); }
 template <class T> __device__ __forceinline__ const T& at(const T* p, unsigned int i) { return *(const T*)((const char*)p + (size_t)(unsigned int)(i * (unsigned int)sizeof(T))); }
@@ -426,7 +397,7 @@ __host__ __device__ inline float skj_word(const PbhcSkeleton& sk, int i) {
   return 0.0f;
 }
 __host__ __device__ constexpr bool skel_fk_jump(int num_bodies_ext, int max_depth) {
-#ifdef PBHC_FK_WALK           // (measurement aid: the chain walk)
+#ifdef PBHC_FK_WALK           // (how a build of a shipped skeleton exercises the chain walk: tests/test_gpu_specialise.py)
   return false;
 #else
   return num_bodies_ext <= PBHC_G && max_depth + 1 <= 16;
@@ -747,8 +718,7 @@ constexpr bool obs_runs_complete(const PbhcEnvConfig& c) {
 // feature index space, every row written by the reference waves, and a history no larger than those arrays / the registers).  That is
 // 5 KB of LDS per workgroup for the walk config: 29.6 KB instead of 39.5 — FIVE workgroups per CU instead of four.  The launch is bound by
 // what a CU holds in flight (an env's chain is ~11 us whatever the env count), so occupancy is throughput.
-#define PBHC_SEG 128                                      // floats of an observation row composed in LDS and stored 16 bytes per lane at a time
-struct StepLds { int stride, hist_in_bodies, map_words, bytes, stage; };
+struct StepLds { int stride, hist_in_bodies, map_words, bytes; };
 __host__ __device__ constexpr StepLds step_lds_plan(const PbhcEnvConfig& c, bool use_runs) {
   const int Bx = c.skel.num_bodies_ext, p = (Bx + 3) & ~3;
   const Lds lo(Bx, c.tracking_mode);
@@ -756,27 +726,13 @@ __host__ __device__ constexpr StepLds step_lds_plan(const PbhcEnvConfig& c, bool
   bool all_b = true;
   for (int g = 0; g < c.num_groups; ++g)
     if (c.groups[g].role != 1) all_b = false;
-#ifdef PBHC_NO_HISTB          // (measurement aid: the round-3 LDS plan)
-  const bool hb = false;
-#else
   const bool hb = use_runs && all_b && hoff + c.hist_dim == c.feat_dim && ((c.hist_dim + 3) & ~3) <= 13 * p && c.hist_dim <= (384 / PBHC_G) * PBHC_G;
-#endif
   const int feat_words = hb ? hoff : c.feat_dim;
-  // (hist_in_bodies builds also compose their rows in a PBHC_SEG-float staging segment per env: obs_write_wide)
-  const int stage = lo.feat + ((feat_words + 3) & ~3);
-#ifdef PBHC_WIDE_ROWS
-  const int stride = stage + (hb ? PBHC_SEG : 0);
-#else
-  const int stride = stage;
-#endif
+  const int stride = lo.feat + ((feat_words + 3) & ~3);
   const int mapw = use_runs ? 0 : c.map_lds_words;
-#ifdef PBHC_WIDE_ROWS
-  const bool skc_lds = true;                                  // (the second staging segment lives there)
-#else
   const bool skc_lds = !cfg_fk_jump(c);                       // the pointer-jumping chain keeps its constants in registers (fk_jump_wave)
-#endif
   const int words = PBHC_EPB * stride + (skc_lds ? ((Bx * (11 + PBHC_MAX_DEPTH) + 3) & ~3) : 0) + mapw;
-  return StepLds{stride, hb ? 1 : 0, mapw, words * 4, stage};
+  return StepLds{stride, hb ? 1 : 0, mapw, words * 4};
 }
 // the uniform of element j of row `stream`: the first word of the env's Philox quad of this step (keyed by env / step only: every lane
 // computes the same one, so the value does not depend on WHICH lane writes element j), re-keyed by (row, j) and passed through a bijective
@@ -837,105 +793,24 @@ __device__ __forceinline__ void obs_write_runs(const PbhcOutMap& m, uint32_t str
   }
 }
 
+// PBHC_MIN_WAVES: waves per SIMD the register allocation must allow.  A workgroup puts one wave on every SIMD, so waves per SIMD =
+// workgroups per CU = what the LDS plan admits (160 KB).
+// (waves_per_eu pins the allocation target too: LDS admits no more than PBHC_MIN_WAVES waves per SIMD, so aiming at a higher occupancy
+// — the compiler stopped at 96 VGPRs and spilled — buys nothing)
 #ifdef PBHC_STATIC_CFG
-constexpr int spec_min_waves() {
+constexpr int spec_min_waves() {                             // the config's own plan, at most 5 here — 6 would leave 80 VGPRs
   const int n = (160 * 1024) / step_lds_plan(kStaticCfg, obs_runs_complete(kStaticCfg)).bytes;
   return n < 1 ? 1 : (n > 5 ? 5 : n);
 }
-#endif
-// The same rows 16 BYTES PER LANE (round 4).  At 32 768 envs the launch is bound by the vector-memory pipeline, not by bytes or arithmetic
-// (profiles/round4_k_env_step_memory_pipeline.txt: the address unit of a CU busy 65 % of the launch, 92 wave-instructions per wave of which
-// nearly all carried 4 bytes per lane), and a third of those instructions were the dword stores of these rows.  A row is composed PBHC_SEG
-// floats at a time in a staging segment of the env's LDS — every run piece that falls into the segment written by the lanes as above
-// (lane <-> element: consecutive LDS words), same arithmetic, same noise words — and leaves as ONE ds_read_b128 + global_store_dwordx4 per
-// segment: a quarter of the store instructions, whole 128-byte lines.  DS instructions of a wave execute in order, so one segment buffer
-// serves all segments of all rows.  PASS 0: every segment for an env that keeps its state, the segments without post-reset features for
-// a terminated one; PASS 1 (after bar3): the remaining segments of a terminated env.  Needs io.obs_wide (rows 16-byte aligned, padded).
-__device__ __forceinline__ void wide_compose(const PbhcOutMap& m, int s0, uint32_t stream, int lane, const float* feat, const float* fhist, int hoff, float* stg,
-                                             float clipobs, float noise_cur, const uint32_t* pre) {
-  const int s1 = min(s0 + PBHC_SEG, m.dim);
-#pragma unroll
-  for (int r = 0; r < m.num_runs; ++r) {
-    const PbhcObsRun& R = m.runs[r];
-    const int lo = max(R.dst, s0), hi = min(R.dst + R.len, s1);            // this run's piece of the segment, in row elements
-    if (lo >= hi) continue;
-#pragma unroll
-    for (int i0 = lo; i0 < hi; i0 += PBHC_G) {
-      const int j = min(i0 + lane, hi - 1);                                   // (lanes past the piece repeat its last element: one basic block)
-      float x = (R.src >= hoff ? fhist : feat)[R.src + (j - R.dst)];
-      if (R.noise != 0.0f) x = x + (obs_noise_u(pre, stream, (uint32_t)j) * 2.0f - 1.0f) * (R.noise * noise_cur);
-      x = x * R.scale;
-      if (m.clip) x = __builtin_amdgcn_fmed3f(x, -clipobs, clipobs);
-      stg[j - s0] = x;
-    }
-  }
-  if (s1 == m.dim && (m.dim & 3) != 0 && lane < 4 - (m.dim & 3)) stg[m.dim - s0 + lane] = 0.0f;      // the row's padding up to a whole quad
-}
-__device__ __forceinline__ void wide_flush(const PbhcOutMap& m, int s0, int lane, const float* stg, float* __restrict__ outg, unsigned int ob) {
-  const int nq = (min(s0 + PBHC_SEG, m.dim) - s0 + 3) >> 2;
-  const int q = min(lane, nq - 1);
-  const float4 v = *reinterpret_cast<const float4*>(stg + 4 * q);
-  *reinterpret_cast<float4*>(&at(outg, ob + (unsigned int)(s0 + 4 * q))) = v;
-}
-constexpr bool seg_has_late(const PbhcOutMap& m, int s0) {
-  for (int r = 0; r < m.num_runs; ++r)
-    if ((m.runs[r].late & 1) && m.runs[r].dst < s0 + PBHC_SEG && m.runs[r].dst + m.runs[r].len > s0) return true;
-  return false;
-}
-template <int PASS>
-__device__ __forceinline__ void obs_write_wide(const PbhcOutMap& m, uint32_t stream, int lane, const float* feat, const float* fhist, int hoff, float* stagel,
-                                               float* __restrict__ outg, unsigned int ob, float clipobs, float noise_cur, const uint32_t* pre, bool rs) {
-#pragma unroll
-  for (int s0 = 0; s0 < m.dim; s0 += PBHC_SEG) {
-    const bool has_late = seg_has_late(m, s0);
-    if (PASS == 1 && !has_late) continue;
-    const bool doit = PASS == 0 ? (!rs || !has_late) : rs;
-    if (doit) {
-      wide_compose(m, s0, stream, lane, feat, fhist, hoff, stagel, clipobs, noise_cur, pre);
-      WAVE_LDS_FENCE();
-      wide_flush(m, s0, lane, stagel, outg, ob);
-      WAVE_LDS_FENCE();
-    }
-  }
-}
-// The common case — neither env of the wave resets — as ONE basic block: every segment of the row, composed alternately in two staging
-// buffers, segment k leaving (ds_read_b128 + store) after segment k+1 has been composed: the flush's LDS round trip and the next
-// segment's feature reads are in flight together (with one buffer every segment waited out compose -> read-back -> store: ~300 cycles
-// each, 11 segments per env).  `stg2`: the second buffer (the skeleton image's LDS, dead since the FK).
-__device__ __forceinline__ void obs_write_wide_all(const PbhcOutMap& m, uint32_t stream, int lane, const float* feat, const float* fhist, int hoff, float* stg0, float* stg1,
-                                                   float* __restrict__ outg, unsigned int ob, float clipobs, float noise_cur, const uint32_t* pre, int* parity) {
-  int par = *parity;
-#pragma unroll
-  for (int s0 = 0; s0 < m.dim; s0 += PBHC_SEG) {
-    wide_compose(m, s0, stream, lane, feat, fhist, hoff, par ? stg1 : stg0, clipobs, noise_cur, pre);
-    WAVE_LDS_FENCE();
-    wide_flush(m, s0, lane, par ? stg1 : stg0, outg, ob);
-    par ^= 1;
-  }
-  *parity = par;
-}
-
-// MODE 0: LeggedRobotMotionTracking (motion_tracking.py), MODE 1: LeggedRobotGeneralTracking (general_tracking.py)
-template <int MODE>
-// waves per SIMD the register allocation must allow: the v1 kernel's LDS footprint admits 4 workgroups = 16 waves per CU (<= 128 VGPRs);
-// general tracking holds twice the LDS per env (2 workgroups per CU)
-#ifndef PBHC_MIN_WAVES
-#ifdef PBHC_STATIC_CFG
-// a workgroup puts one wave on every SIMD: waves per SIMD = workgroups per CU = what the config's LDS plan admits (160 KB), at most 5 here —
-// 6 would leave 80 VGPRs
 #define PBHC_MIN_WAVES spec_min_waves()
 #else
+// the v1 kernel's LDS footprint admits 4 workgroups = 16 waves per CU (<= 128 VGPRs); general tracking holds twice the LDS per env
 #define PBHC_MIN_WAVES (MODE ? 2 : 4)
 #endif
-#endif
-// (waves_per_eu pins the allocation target too: LDS admits no more than PBHC_MIN_WAVES waves per SIMD, so aiming at a higher occupancy
-// — the compiler stopped at 96 VGPRs and spilled — buys nothing)
+// MODE 0: LeggedRobotMotionTracking (motion_tracking.py), MODE 1: LeggedRobotGeneralTracking (general_tracking.py)
 // The first eight parameters are the addresses (and two scalars) the first memory round trip of a workgroup hangs on — a copy of what `io`
-// and the config also hold — so that each role can request the episode clock / the replay frame first thing.  Measured and NOT adopted:
-// preloading them into SGPRs at wave launch (PBHC_KERNARG_PRELOAD=14 -> -mllvm -amdgpu-kernarg-preload-count): the reference waves then
-// enter their role 395 cycles into the launch instead of 1 525 and issue these loads at once — and the data is back at the same 6 k cycles:
-// with every workgroup of the chip in its prologue the first round trip is the HBM burst itself (12.7 MB at ~5 TB/s), not the issue time
-// (profiles/round4_k_env_step_prologue.txt).
+// and the config also hold — so that each role can request the episode clock / the replay frame first thing.
+template <int MODE>
 __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_waves_per_eu(PBHC_MIN_WAVES, PBHC_MIN_WAVES))) void k_env_step(
                                                               const long long* __restrict__ a_ep_len, const float* __restrict__ a_start, const float* __restrict__ a_frame_root,
                                                               const float* __restrict__ a_frame_q, const float* __restrict__ a_frame_qd, const int32_t* __restrict__ a_cursor,
@@ -949,12 +824,6 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   // The config is read through the CONSTANT address space: the kernel never writes it, and saying so lets the compiler keep its
   // scalars in SGPRs across the kernel's global stores.
   WG_STAMP(0);
-#ifdef PBHC_STAGGER
-  // experiment: every other workgroup starts PBHC_STAGGER x ~1 us late, so that one half of a CU's workgroups is in its load burst while
-  // the other half computes (see DESIGN §4 for what it measured)
-  if (blockIdx.x & 1)
-    for (int i = 0; i < PBHC_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
   typedef const PbhcEnvConfig __attribute__((address_space(4))) ConstCfg;
   ConstCfg& rt = *(ConstCfg*)cfgp;
 #ifdef PBHC_STATIC_CFG
@@ -975,12 +844,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   // that two neighbouring workgroups share into TWO L2s, each of which fetches it and writes its half back as a partial line.  XCD x
   // takes a CONTIGUOUS range of env blocks instead (bijective for any block count), so neighbours meet in one L2: whole-line write-backs,
   // one fetch per line.  (The partial-sum rows stay indexed by env block: k_env_finalize adds them up in the same order as ever.)
-#ifdef PBHC_NO_XCD_MAP
-  const u32 wgb = blockIdx.x;
-#else
   const u32 nb_ = gridDim.x, xq_ = nb_ >> 3, xr_ = nb_ & 7u, xcd_ = blockIdx.x & 7u;
   const u32 wgb = xcd_ * xq_ + min(xcd_, xr_) + (blockIdx.x >> 3);
-#endif
   const int env = (int)wgb * PBHC_EPB + le;
   const bool valid = env < N;
   float* S = smem + (size_t)le * lds_stride;
@@ -1030,41 +895,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   // waves still have the reward phase and the rest of the reset in front of them
   const bool dr_on_b = hist_b;
   // ... and the runs the host marked (PbhcObsRun.late bit 1) are written by the dynamics waves after their phase H (OBS_GROUPS_HELP_RUNS)
-#if defined(PBHC_STATIC_CFG) && !defined(PBHC_WIDE_ROWS) && !defined(PBHC_NO_ROW_HELP)
   constexpr bool row_help = hist_b;
-#else
-  constexpr bool row_help = false;
-#endif
   constexpr int RUN_WHO = row_help ? 1 : 0;
   float* const histl = hist_b ? bp : feat + hoff;
   const float* const fhist = histl - hoff;
-#ifdef PBHC_STATIC_CFG
-  float* const stagel = S + step_lds_plan(kStaticCfg, use_runs).stage;       // (hist_b builds only)
-  float* const stage2 = skc + le * PBHC_SEG;                                  // second staging segment: the skeleton image, dead since the FK (bar1)
-  static_assert(!hist_b || PBHC_EPB * PBHC_SEG <= SKC_WORDS, "second staging buffer");
-#ifndef PBHC_WIDE_ROWS        // the 16-byte form is opt-in (-DPBHC_WIDE_ROWS): measured, not adopted — see obs_write_wide
-  const bool wide = false;
-#else
-  const bool wide = hist_b && io.obs_wide != 0;
-#endif
-#define OBS_GROUPS_WIDE_ALL()                                                                                                       \
-  { int par_ = 0;                                                                                                                   \
-  _Pragma("unroll") for (int g = 0; g < PBHC_MAX_GROUPS; ++g) {                                                                     \
-    if (g >= c.num_groups) continue;                                                                                                \
-    const int pitch_g = io.obs_pitch[g] ? io.obs_pitch[g] : c.groups[g].pitch;                                                      \
-    obs_write_wide_all(c.groups[g], 16 + g, lane, feat, fhist, hoff, stagel, stage2, io.obs[g], (u32)env * (u32)pitch_g, clipobs, noise_cur, nzb, &par_); \
-  } }
-#define OBS_GROUPS_WIDE(PASS, RS)                                                                                                   \
-  _Pragma("unroll") for (int g = 0; g < PBHC_MAX_GROUPS; ++g) {                                                                     \
-    if (g >= c.num_groups) continue;                                                                                                \
-    const int pitch_g = io.obs_pitch[g] ? io.obs_pitch[g] : c.groups[g].pitch;                                                      \
-    obs_write_wide<PASS>(c.groups[g], 16 + g, lane, feat, fhist, hoff, stagel, io.obs[g], (u32)env * (u32)pitch_g, clipobs, noise_cur, nzb, RS); \
-  }
-#else
-  const bool wide = false;
-#define OBS_GROUPS_WIDE(PASS, RS)
-#define OBS_GROUPS_WIDE_ALL()
-#endif
   const int o_pos = 2 * D + 2, o_rot = o_pos + 3 * Bx, o_vel = o_rot + 4 * Bx, o_ang = o_vel + 3 * Bx;     // columns of a packed motion-table row
   STAMP(0);
 
@@ -1121,8 +955,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // for itself — 10 of its 25 load instructions and 9 % of the bytes a workgroup pulls through the CU's vector-memory pipeline, which
     // is what bounds the launch at large env counts (profiles/round4_k_env_step_memory_pipeline.txt).
     // the replay frame first: its addresses are in SGPRs since the wave was launched
-    const float fq = NTLD(at(a_frame_q + fk * D, eDc + dc)), fqd = NTLD(at(a_frame_qd + fk * D, eDc + dc));
-    const float froot = NTLD(at(a_frame_root + fk * 13, (u32)envc * 13u + (u32)min(lane, 12)));
+    const float fq = at(a_frame_q + fk * D, eDc + dc), fqd = at(a_frame_qd + fk * D, eDc + dc);
+    const float froot = at(a_frame_root + fk * 13, (u32)envc * 13u + (u32)min(lane, 12));
     __builtin_amdgcn_sched_barrier(0);
     float4 kr[5];                                              // fk_jump: this lane's body constants, straight into registers
     if (fk_jump) {
@@ -1134,12 +968,12 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const int tl_ = min(lane, PBHC_MAX_TERMS - 1);
       pf_tid = c.term_id[tl_]; pf_tscale = c.term_scale[tl_]; pf_tpen = c.term_penalty[tl_]; pf_tsrc = c.term_src[tl_];
       pf_colterm = c.sum_col_term[lane];                     // lane i <-> episode_sums column i: the term that accumulates into it
-      sumrow = NTLD(at(io.episode_sums, (u32)envc * (u32)c.num_sum_cols + (u32)min(lane, c.num_sum_cols - 1)));
+      sumrow = at(io.episode_sums, (u32)envc * (u32)c.num_sum_cols + (u32)min(lane, c.num_sum_cols - 1));
       pf_sigma = (float)glob[PBHC_G_SIGMA + min(lane, PBHC_NUM_SIGMA - 1)];
       pf_pen_scale = (float)glob[PBHC_G_PENALTY_SCALE]; pf_far_thr = (float)glob[PBHC_G_MOTION_FAR_THR];
       if (c.terminate_when_dof_far) pf_dof_far = glob[PBHC_G_DOF_FAR_HIT] != 0.0;
       if (c.noise_process) ou_x = at(io.ou_state, (u32)envc * 6u + (u32)min(lane, 5));
-      kpA = NTLD(at(io.kp_scale, eDc + dc)); kdA = NTLD(at(io.kd_scale, eDc + dc));                // phase H (a reset replaces them in registers)
+      kpA = at(io.kp_scale, eDc + dc); kdA = at(io.kd_scale, eDc + dc);                // phase H (a reset replaces them in registers)
       dpA = io.default_dof_pos ? at(io.default_dof_pos, eDc + dc) : c.default_dof_pos[dc];
       adelay = io.action_delay_idx[envc];
       etr_old = io.end_time_ratio_buf[envc];
@@ -1155,12 +989,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     WAVE_LDS_FENCE();
     // =============== role A, interval 1: rigid-body state of the new frame (sim-stub FK), wave-local ==============================
-#ifndef PBHC_ABL_FK
     if (fk_jump) fk_jump_wave(kr, fk_rounds, B, Bx, lane, valid, root, q, qd, bp, bq, bv, bw);
     else fk_walk_wave(skc, B, Bx, lane, valid, root, q, qd, bp, bq, bv, bw);
-#else       // (timing ablations, -DPBHC_ABL_*: what a phase costs is read off the launch time without it; results are meaningless)
-    if (valid && lane < Bx) { st3(bp + 3 * lane, ld3(root)); st4(bq + 4 * lane, ld4(root + 3)); st3(bv + 3 * lane, ld3(root + 7)); st3(bw + 3 * lane, ld3(root + 10)); }
-#endif
     // ---- obs.noise_process (legged_robot_base.py:357-358, noise_tool.py OUProcess.step): x += theta (mu - x) dt + sigma randn sqrt(dt), every
     // env, before termination; lane k < 6 holds component k, every lane gets the stepped state for the noisy features below
     float oux[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1174,11 +1004,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // ---- phase C: per-env scalars of the root state (legged_robot_base.py:346-380).  One lane per quantity and ONE code path per function:
     // lanes 0-2 evaluate the three atan2 (yaw, heading, roll), lane 3 the asin of the pitch, lanes 4-6 the three base-frame rotations (lane 0
     // doing all of it in turn was ~450 instructions; roll and pitch only exist where an observation reads them: general tracking).
-#ifdef PBHC_ABL_PHASEC
-    if (false) {
-#else
     if (valid) {
-#endif
       const f4 rq4 = ld4(root + 3);
       if (lane < 3) {
         float sinr, cosr, sinp, siny, cosy;
@@ -1211,11 +1037,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     // the observation-noise base of this env and step (obs_noise_u): ONE Philox call per env, here — these waves wait at bar1 —, handed
     // to whichever wave writes a row through LDS
-#ifndef PBHC_ABL_RNG
     philox4x32((uint32_t)rt.seed, (uint32_t)(rt.seed >> 32), env, step_ctr, 16, 0u, nzb);
-#else
-    nzb[0] = env ^ step_ctr; nzb[1] = nzb[2] = nzb[3] = 0;
-#endif
     if (valid && lane == 0) misc[M_NZB] = __uint_as_float(nzb[0]);
     WAVE_LDS_FENCE();
     STAMP(2);
@@ -1224,7 +1046,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // the episode clock first: its addresses are in SGPRs since the wave was launched, and the reference rows' addresses hang on it
     ep1 = a_ep_len[envc] + 1;
     start = a_start[envc];
-    const float frootB = NTLD(at(a_frame_root + fk * 13, (u32)envc * 13u + (u32)min(lane, 12)));      // phase C below
+    const float frootB = at(a_frame_root + fk * 13, (u32)envc * 13u + (u32)min(lane, 12));      // phase C below
     __builtin_amdgcn_sched_barrier(0);
     // the skeleton constants for the dynamics waves' FK: ONE copy per workgroup, the first thing these two waves request (an L2 hit)
 #define SKC_REGSB ((SKC_WORDS + 2 * 64 - 1) / (2 * 64))
@@ -1235,15 +1057,6 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       for (int u = 0; u < SKC_REGSB; ++u) skregB[u] = skc_img[min(wl + u * 128, n - 1)];
     }
     __builtin_amdgcn_sched_barrier(0);
-#ifdef PBHC_PTR_BURST
-    // (measurement aid, neutral: the ~30 tensor addresses of this prologue fetched from the argument segment as ONE burst of scalar loads
-    // instead of one or two at a time in front of their first use)
-    asm volatile("" ::"s"(io.episode_length_buf), "s"(io.motion_start_times), "s"(io.motion_ids), "s"(io.env_origins), "s"(io.frame_root), "s"(io.feet_air_time),
-                 "s"(io.last_contacts), "s"(io.frame_contact), "s"(io.action_queue), "s"(io.actions_in), "s"(io.dof_state), "s"(io.kp_scale), "s"(io.kd_scale),
-                 "s"(io.rfi_lim_scale));
-    asm volatile("" ::"s"(io.rao_scale), "s"(io.u_rfi), "s"(io.last_actions), "s"(io.last_dof_vel), "s"(io.action_delay_idx), "s"(io.motion_len), "s"(io.dr_base_com),
-                 "s"(io.dr_friction), "s"(io.dr_link_mass), "s"(tbl.frames));
-#endif
     STAMPB(10);
     LOAD_CLIP_ID();
     // =============== role B, interval 0: every other load of the step.  ORDER (loads return in issue order): (1) the env scalars the
@@ -1252,7 +1065,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // two table rows.  Round 3 issued (2) BEHIND (3), i.e. after the first round trip had come back: two full trips to memory (6.5 k cycles
     // to this role's first stamp) where one and an L2 hit do.  Then _pre_physics_step (motion_tracking.py:749-768) and the torques from the
     // pre-step state (legged_robot_base.py:795-838).
-    const float fat = NTLD(at(io.feet_air_time, (u32)envc * (u32)NF + (u32)min(lane, NF - 1))), lastc = NTLD(at(io.last_contacts, (u32)envc * (u32)NF + (u32)min(lane, NF - 1)));
+    const float fat = at(io.feet_air_time, (u32)envc * (u32)NF + (u32)min(lane, NF - 1)), lastc = at(io.last_contacts, (u32)envc * (u32)NF + (u32)min(lane, NF - 1));
     // the frame's contact forces (3 B floats per env): whole quads 16 bytes per lane + the remainder, two load instructions instead of four
     float4 creg4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float cregr = 0.0f;
@@ -1261,23 +1074,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const u32 cbase = (u32)envc * (u32)(B * 3);
       const int nq = (B * 3) >> 2;
       const float* qa = &at(csrc, cbase + 4u * (u32)min(lane, nq - 1));
-      creg4 = make_float4(NTLD(qa[0]), NTLD(qa[1]), NTLD(qa[2]), NTLD(qa[3]));               // (4-byte aligned rows: the compiler's own dwordx4, as for the table rows)
-      if ((B * 3) & 3) cregr = NTLD(at(csrc, cbase + (u32)min(4 * nq + lane, B * 3 - 1)));
+      creg4 = make_float4(qa[0], qa[1], qa[2], qa[3]);               // (4-byte aligned rows: the compiler's own dwordx4, as for the table rows)
+      if ((B * 3) & 3) cregr = at(csrc, cbase + (u32)min(4 * nq + lane, B * 3 - 1));
     }
-    // operands of the pre-physics step / torques / joint-space sums: consumed after bar1 — requested behind phase D, where the reference rows'
-    // 32 registers are free again: 13 registers off this prologue's peak (92 -> 76 VGPRs; 18.0 / 95.0 -> 18.0 / 92.0 us at 4096 / 32 768 envs,
-    // profiles/round4_k_env_step_variants.txt (i); -DPBHC_EARLY_OPERANDS: with the prologue's other loads, as before).  A sixth workgroup per CU,
-    // which 76 registers admit (-DPBHC_MIN_WAVES=6: resident by hipOccupancyMaxActiveBlocksPerMultiprocessor), measured no further gain.
-#define LOAD_STEP_OPERANDS()                                                                                                          \
-    _Pragma("unroll") for (int k = 0; k < PBHC_MAX_QUEUE; ++k) qold[k] = NTLD(at(io.action_queue, qoff + (u32)(min(k, Q - 1) * D)));       \
-    a_in = NTLD(at(io.actions_in, eDc + dc));                                                                                               \
-    qp = NTLD(at(io.dof_state, (eDc + dc) * 2)); qv = NTLD(at(io.dof_state, (eDc + dc) * 2 + 1));                                               \
-    kp = NTLD(at(io.kp_scale, eDc + dc)); kd = NTLD(at(io.kd_scale, eDc + dc)); rfs = NTLD(at(io.rfi_lim_scale, eDc + dc)); ras = NTLD(at(io.rao_scale, eDc + dc)); \
-    u_inj = NTLD(at(io.u_rfi ? io.u_rfi : io.actions_in, eDc + dc));                                                                        \
-    pf_last_act = NTLD(at(io.last_actions, eDc + dc)); pf_last_qd = NTLD(at(io.last_dof_vel, eDc + dc));
-#ifdef PBHC_EARLY_OPERANDS
-    LOAD_STEP_OPERANDS()
-#endif
+    // (the operands of the pre-physics step / torques / joint-space sums are requested behind phase D)
     adelayB = io.action_delay_idx[envc];
     const float mlenB = io.motion_len[envc];
     didx = c.randomize_ctrl_delay ? (int)adelayB : 0;
@@ -1321,9 +1121,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     __builtin_amdgcn_sched_barrier(0);
     STAMPB(7);
-#ifndef PBHC_ABL_RNG
     if (c.randomize_torque_rfi) u_rfi = io.u_rfi ? 0.5f : rng_uniform(rt.seed, env, step_ctr, 1, d);     // in-kernel draw: computed while the loads fly
-#endif
     STAMPB(8);
     if (valid) {
       // contact forces and the previous contacts
@@ -1356,11 +1154,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     STAMPB(1);
     // ---- phase D: reference frame: lerp / slerp of the two frame rows (MotionLibBase.get_motion_state motion_lib_base.py:123-259)
-#ifdef PBHC_ABL_PHASED
-    if (false) {
-#else
     if (valid) {
-#endif
       const float a = 1.0f - blend, bb = blend;
       if (lane < D) { rdof[lane] = a * rd0 + bb * rd1; rdofv[lane] = a * rdv0 + bb * rdv1; }
       if (lane < 2) {
@@ -1403,9 +1197,17 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       }
     }
     STAMPB(2);
-#ifndef PBHC_EARLY_OPERANDS
-    LOAD_STEP_OPERANDS()
-#endif
+    // operands of the pre-physics step / torques / joint-space sums: consumed after bar1 — requested here, behind phase D, where the reference
+    // rows' 32 registers are free again, not with the prologue's other loads: 13 registers off the prologue's peak (92 -> 76 VGPRs; 18.0 / 95.0
+    // -> 18.0 / 92.0 us at 4096 / 32 768 envs, profiles/round4_k_env_step_variants.txt (i)).  A sixth workgroup per CU, which 76 registers
+    // admit, measured no further gain.
+#pragma unroll
+    for (int k = 0; k < PBHC_MAX_QUEUE; ++k) qold[k] = at(io.action_queue, qoff + (u32)(min(k, Q - 1) * D));
+    a_in = at(io.actions_in, eDc + dc);
+    qp = at(io.dof_state, (eDc + dc) * 2); qv = at(io.dof_state, (eDc + dc) * 2 + 1);
+    kp = at(io.kp_scale, eDc + dc); kd = at(io.kd_scale, eDc + dc); rfs = at(io.rfi_lim_scale, eDc + dc); ras = at(io.rao_scale, eDc + dc);
+    u_inj = at(io.u_rfi ? io.u_rfi : io.actions_in, eDc + dc);
+    pf_last_act = at(io.last_actions, eDc + dc); pf_last_qd = at(io.last_dof_vel, eDc + dc);
     // ---- the history row (40 % of this role's loaded bytes, read by nobody before bar2) is REQUESTED here, behind the loads that bar1 waits
     // for — issued with them it sat in the same in-order queue and the burst of all workgroups' prologues landed ~2 k cycles later —
     // and copied to the feature row after bar1
@@ -1413,7 +1215,6 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const u32 hbase = (u32)envc * (u32)(io.hist_pitch ? io.hist_pitch : c.hist_dim);
       const int hlast = c.hist_dim - 1;
 #pragma unroll
-#ifndef PBHC_ABL_HIST
       for (int u = 0; u < PBHC_HREG; ++u)
         if (!hist_b) hreg[u] = at(io.hist, hbase + (u32)min(lane + u * PBHC_G, hlast));
       if (hist_b) {
@@ -1423,14 +1224,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
 #pragma unroll
         for (int u = 0; u < PBHC_HREG4; ++u)
           if (u * PBHC_G < nq) {
-            const pbhc_f32x4 hv = NTLD(*reinterpret_cast<const pbhc_f32x4*>(&at(io.hist, hbase + 4u * (u32)min(lane + u * PBHC_G, nq - 1))));
+            const pbhc_f32x4 hv = *reinterpret_cast<const pbhc_f32x4*>(&at(io.hist, hbase + 4u * (u32)min(lane + u * PBHC_G, nq - 1)));
             hreg4[u] = make_float4(hv[0], hv[1], hv[2], hv[3]);
           }
       }
-#else
-      for (int u = 0; u < PBHC_HREG; ++u) hreg[u] = 0.0f;
-      for (int u = 0; u < PBHC_HREG4; ++u) hreg4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
     }
     // per-dof constants of the config: one batch of loads at the head of the interval
     k_tl = c.torque_limits[dc]; k_dp = io.default_dof_pos ? at(io.default_dof_pos, eDc + dc) : c.default_dof_pos[dc];
@@ -1524,11 +1321,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         sincos_cw(feat[c.feat_off[PBHC_F_RELYAW]] * 0.5f, &sn, &cs);
         ryq = mk4(0.0f, 0.0f, -sn, cs);
       }
-#ifdef PBHC_ABL_EBODY
-      for (int b = lane; b < 0; b += PBHC_G) {
-#else
       for (int b = lane; b < Bx; b += PBHC_G) {
-#endif
         f3 rpos = ld3(rp + 3 * b);
         f3 dp = sub3(rpos, ld3(bp + 3 * b));
         float n2 = dp.x * dp.x + dp.y * dp.y + dp.z * dp.z;
@@ -1656,20 +1449,13 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const bool dof_far = c.terminate_when_dof_far && pf_dof_far;
       misc[M_RESET] = (grav != 0.0f || far != 0.0f || tout != 0.0f || refz != 0.0f || refori != 0.0f || bodyz != 0.0f || tcontact != 0.0f || tlowh != 0.0f
                        || dof_far) ? 1.0f : 0.0f;
-#ifdef PBHC_ABL_NORESET
-      misc[M_RESET] = 0.0f;
-#endif
     }
     WAVE_LDS_FENCE();
     STAMP(4);
   } else {
     // =============== role B, interval 2a: pre-physics step + torques, joint-space differences + reductions, foot norms, the
     // post-reset features of a NON-terminated env (what phase H of role A computes after a reset), the observation maps -> LDS ========
-#ifdef PBHC_ABL_HIST
-    if (false) {
-#else
     if (valid && !hist_b) {                                      // the history row -> feature row (hist_b: it stays in registers until bar2)
-#endif
 #pragma unroll
       for (int u = 0; u < PBHC_HREG; ++u) { const int i = lane + u * PBHC_G; if (i < c.hist_dim) feat[hoff + i] = hreg[u]; }
       if (c.hist_dim > PBHC_HREG * PBHC_G)
@@ -1703,11 +1489,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       const float soft_pos = (float)glob[PBHC_G_SOFT_POS_VAL], soft_vel = (float)glob[PBHC_G_SOFT_VEL_VAL], soft_tau = (float)glob[PBHC_G_SOFT_TAU_VAL];
       const float inv_dt = 1.0f / dt;
       const int o_dja = c.feat_off[PBHC_F_DIF_JOINT_ANGLES], o_djv = c.feat_off[PBHC_F_DIF_JOINT_VELOCITIES];
-#ifdef PBHC_ABL_JOINT
-      if (false) {
-#else
       if (d < D) {
-#endif
         const int dd = d;
         float dj = rdof[dd] - q[dd], djv = rdofv[dd] - qd[dd];
         feat[o_dja + dd] = dj; feat[o_djv + dd] = djv;
@@ -1943,29 +1725,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
       obs_write_list_unaligned(mg, n_early, nlist, lane, PBHC_G, feat, outg, ob, c.groups[g].dim, c.groups[g].clip, clipobs);       \
     obs_write_noisy(mg, nn_early, nn, lane, PBHC_G, feat, outg, ob, c.groups[g].clip, clipobs, noise_cur, 16 + g, nzb); \
   }
-#ifdef PBHC_ABL_OBSX4
-// timing experiment: the same rows, the same bytes, stored 16 bytes per lane straight from the feature row (contents meaningless)
-#define OBS_GROUPS(ROLE, LATE_TOO) do {                                                                                             \
-  _Pragma("unroll") for (int g = 0; g < PBHC_MAX_GROUPS; ++g) {                                                                     \
-    if (g >= c.num_groups || c.groups[g].role != (ROLE)) continue;                                                                  \
-    const int pitch_g = io.obs_pitch[g] ? io.obs_pitch[g] : c.groups[g].pitch;                                                      \
-    float* __restrict__ const outg = io.obs[g];                                                                                     \
-    const u32 ob = (u32)env * (u32)pitch_g;                                                                                         \
-    _Pragma("unroll") for (int q0 = 0; q0 < (c.groups[g].dim + 3) / 4; q0 += PBHC_G) {                                             \
-      const int q = min(q0 + lane, (c.groups[g].dim + 3) / 4 - 1);                                                                  \
-      float4 v = *reinterpret_cast<const float4*>(feat + 4 * (q & 127));                                                            \
-      v.x *= clipobs;                                                                                                               \
-      *reinterpret_cast<float4*>(&at(outg, ob + (unsigned int)(4 * q))) = v;                                                        \
-    }                                                                                                                               \
-  } } while (0)
-#define OBS_GROUPS_LATE(ROLE) do { } while (0)
-#elif !defined(PBHC_ABL_OBS)
 #define OBS_GROUPS(ROLE, LATE_TOO) do { if (use_runs) { OBS_GROUPS_RUNS(ROLE, LATE_TOO) } else { OBS_GROUPS_MAP(ROLE, LATE_TOO) } } while (0)
 #define OBS_GROUPS_LATE(ROLE) do { if (use_runs) { OBS_GROUPS_LATE_RUNS(ROLE) } else { OBS_GROUPS_LATE_MAP(ROLE) } } while (0)
-#else
-#define OBS_GROUPS(ROLE, LATE_TOO) do { } while (0)
-#define OBS_GROUPS_LATE(ROLE) do { } while (0)
-#endif
   float rew_total = 0.0f, etr_val = 0.0f;
 
   if (!roleB) {
@@ -1973,14 +1734,10 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     // (a) lane k < 10: e_k = exp(-err_k / sigma_k).  (b) lane i <-> term i: cheap selects.
     if (valid && lane < PBHC_NUM_SIGMA) {
       const float e = red[R_ERR0 + lane];
-#ifndef PBHC_ABL_F
       // exp(-err / sigma) (motion_tracking.py:1154-1290) as 2^(-err log2(e) / sigma) with the hardware reciprocal and 2^x (1 ulp each; the
       // library's expf + a correctly rounded division are ~35 instructions of the reward chain): relative error <= ~(2 + |x|) 6e-8, i.e.
       // < 2e-6 for the arguments the tracking terms see — inside the 3e-5 / 1e-4 the reward columns are held to
       red[R_EXP0 + lane] = __builtin_amdgcn_exp2f((-e * __builtin_amdgcn_rcpf(pf_sigma)) * 1.44269504088896341f);
-#else
-      red[R_EXP0 + lane] = e * pf_sigma;
-#endif
     }
     WAVE_LDS_FENCE();
     STAMP(25);
@@ -1993,9 +1750,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         // reads (one round trip), every value computed by every lane, each lane keeping the one its term id names — instead of a switch per
         // lane, whose cases ran one after the other, each behind its own LDS reads (1.7 k cycles of the chain).  The specialised build drops
         // the terms its config does not have (TERM folds to a literal there).
-#ifdef PBHC_ABL_F
-#define TERM(name) false
-#elif defined(PBHC_STATIC_CFG)
+#ifdef PBHC_STATIC_CFG
 #define TERM(name) cfg_has_term(kStaticCfg, PBHC_R_##name)
 #else
 #define TERM(name) true
@@ -2322,10 +2077,8 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     }
     WAVE_LDS_FENCE();
     STAMP(8);
-#ifndef PBHC_ABL_WB
     if (hist_b && valid) { STATE_WRITEBACK(); }                  // phase J on THIS role (see interval 3)
-#endif
-#if defined(PBHC_STATIC_CFG) && !defined(PBHC_ABL_OBS) && !defined(PBHC_ABL_OBSX4)
+#ifdef PBHC_STATIC_CFG
     // ... and its share of the reference waves' rows: every source is final for this role (its own phase H included), history excluded
     if (row_help && valid && obs_by_role) { OBS_GROUPS_HELP_RUNS() }
 #endif
@@ -2399,14 +2152,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
     if (valid && obs_by_role) {
       // a surviving env: every pair; a terminated env: all but the pairs that read post-reset features (after bar3)
       const bool rs = misc[M_RESET] != 0.0f || gateB || io.redraw_all != 0;
-      if (wide) {
-        // (a wave holds two envs: the one-block form when neither resets — wave-uniform, ~98 % of the waves)
-#ifdef PBHC_WIDE_ONEBUF       // (measurement aid)
-        { OBS_GROUPS_WIDE(0, rs) }
-#else
-        if (__builtin_amdgcn_ballot_w64(rs) == 0) { OBS_GROUPS_WIDE_ALL() } else { OBS_GROUPS_WIDE(0, rs) }
-#endif
-      } else if (rs) { OBS_GROUPS(1, false); } else { OBS_GROUPS(1, true); }
+      if (rs) { OBS_GROUPS(1, false); } else { OBS_GROUPS(1, true); }
     }
     STAMPB(5);
   }
@@ -2415,9 +2161,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
   // a terminated env (~1 % of them): the pairs of role B's rows that read post-reset features, by role B itself — it is idle from here to bar4
   // while role A, the chain that sets the kernel's duration, writes the state back (round 2: role A wrote them before bar3, +2.8 k cycles on
   // exactly the workgroups that finish last)
-  if (roleB && valid && obs_by_role && (misc[M_RESET] != 0.0f || io.redraw_all != 0)) {
-    if (wide) { OBS_GROUPS_WIDE(1, true) } else { OBS_GROUPS_LATE(1); }
-  }
+  if (roleB && valid && obs_by_role && (misc[M_RESET] != 0.0f || io.redraw_all != 0)) OBS_GROUPS_LATE(1);
 
   // =============== interval 3: state write-back (role A) ================================================================================
   if (valid) {
@@ -2455,11 +2199,7 @@ __global__ __launch_bounds__(PBHC_TPB, PBHC_MIN_WAVES) __attribute__((amdgpu_wav
         }
       }
     }
-#ifdef PBHC_ABL_WB
-    if (false) {
-#else
     if (roleB && !hist_b) {
-#endif
       // ---------------- phase J: state write-back (_post_compute_observations_callback :398-405), by the reference waves: everything it
       // stores is final in LDS since bar3 (a reset's new state included), these waves have nothing else left, and the arrays are the ones
       // they loaded in their prologue — while the dynamics waves go straight on to the partial sums (1.3 k cycles off the chain).

@@ -1068,12 +1068,6 @@ int pbhc_env_step_launch(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
       return PBHC_EINVAL;
     }
   }
-  PbhcStepIO a_io = *io;
-  a_io.obs_wide = 1;
-  for (int g = 0; g < e->cfg.num_groups; ++g) {
-    const int pitch = io->obs_pitch[g] ? io->obs_pitch[g] : e->cfg.groups[g].pitch;
-    if (((uintptr_t)io->obs[g] & 15) != 0 || (pitch & 3) != 0 || pitch < ((e->cfg.groups[g].dim + 3) & ~3)) a_io.obs_wide = 0;
-  }
   int a_stride = e->spec_fn ? e->spec_lds_stride : e->lds_stride;
   const size_t a_lds = e->spec_fn ? e->spec_lds_bytes : e->lds_bytes;
   const long long* a_ep = (const long long*)io->episode_length_buf;
@@ -1081,7 +1075,7 @@ int pbhc_env_step_launch(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
   const float *a_fr = io->frame_root, *a_fq = io->frame_dof_pos, *a_fqd = io->frame_dof_vel;
   const int32_t* a_cur = io->frame_cursor;
   int a_fi = io->frame_index, a_n = e->cfg.num_envs;
-  void* args[] = {(void*)&a_ep, (void*)&a_st, (void*)&a_fr, (void*)&a_fq, (void*)&a_fqd, (void*)&a_cur, (void*)&a_fi, (void*)&a_n, (void*)&a_cfg, (void*)&e->tbl, (void*)&a_io, (void*)&a_glob, (void*)&e->d_partials, (void*)&a_stride, (void*)&a_skc, (void*)&a_map, (void*)&a_skj};
+  void* args[] = {(void*)&a_ep, (void*)&a_st, (void*)&a_fr, (void*)&a_fq, (void*)&a_fqd, (void*)&a_cur, (void*)&a_fi, (void*)&a_n, (void*)&a_cfg, (void*)&e->tbl, (void*)io, (void*)&a_glob, (void*)&e->d_partials, (void*)&a_stride, (void*)&a_skc, (void*)&a_map, (void*)&a_skj};
   const void* fn = e->spec_fn ? e->spec_fn : (e->cfg.tracking_mode ? (const void*)k_env_step<1> : (const void*)k_env_step<0>);
   if (e->cfg.terminate_when_dof_far)          // the batch-global dof-far decision, ahead of the step's reset path (k_dof_far_any)
     hipLaunchKernelGGL(k_dof_far_any, dim3((a_n + DOF_FAR_EPB - 1) / DOF_FAR_EPB), dim3(PBHC_G * DOF_FAR_EPB), 0, st, a_ep, a_st, a_fq, a_cur, a_fi,

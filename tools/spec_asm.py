@@ -1,10 +1,14 @@
 """Diagnostic (CPU only, no GPU needed): build the config-specialised k_env_step for one of the fixture configs exactly as an env would
 (env_config.build -> pbhc_env_config_finalize -> generated header -> hipcc) and write its gfx950 assembly + a static instruction census.
 
-    python tools/spec_asm.py [v1_g1_23dof_walk.yaml] [--general] [--out /tmp/spec] [--defs "-DX -DY"]
+    python tools/spec_asm.py [v1_g1_23dof_walk.yaml] [--general] [--contact-mask] [--out /tmp/spec] [--defs="-DX -DY"]
+`generic` in place of a config: the generic kernels of pbhc_kernels.hip.  --sha256 prints the hash of the assembly with what differs
+between two compilations of the same source taken out (the __hip_cuid_ symbol, the checkout and output paths): two trees that print the
+same hash build the same machine code.
 Not part of the product or the tests."""
 import argparse
 import collections
+import hashlib
 import os
 import re
 import subprocess
@@ -23,31 +27,42 @@ ap.add_argument("--general", action="store_true")
 ap.add_argument("--out", default="/tmp/spec")
 ap.add_argument("--defs", default="")
 ap.add_argument("--noise-off", action="store_true")
+ap.add_argument("--contact-mask", action="store_true")      # the motion file has one (a config with the teleop_contact_mask reward needs it)
+ap.add_argument("--sha256", action="store_true")
 a = ap.parse_args()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cfg = load_config(os.path.join(ROOT, "tests", "golden", "configs", a.cfg), {"num_envs": 4096, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"}, now="t")
-if a.noise_off:
-    for k in list(cfg.obs.noise_scales.keys()):
-        cfg.obs.noise_scales[k] = 0.0
-skel = Skeleton.from_motion_config(cfg.robot.motion)
-
-
-class _ML:
-    has_contact_mask = False
-
-
-nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
-c, L = env_config.build(_TopView(cfg.env.config), skel, _ML(), 4096, "cpu", nl, seed=1, mode=1 if a.general else 0)
-cf = S.finalised(c)
-text = S.emit_header(cf)
 os.makedirs(a.out, exist_ok=True)
-hdr = os.path.join(a.out, "cfg.h")
-open(hdr, "w").write(text)
 asm = os.path.join(a.out, "k.s")
-cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + S.KERNEL_FLAGS + a.defs.split() + [f'-DPBHC_STATIC_CFG="{hdr}"', f"-DPBHC_SPEC_MODE={int(cf.tracking_mode)}",
-      "--cuda-device-only", "-S", "-o", asm, os.path.join(S.CSRC, "pbhc_env_step_spec.hip")]
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def spec_cmd():
+    """the config as an env would finalise it -> generated header; the defines and the translation unit of its specialised build"""
+    cfg = load_config(os.path.join(ROOT, "tests", "golden", "configs", a.cfg), {"num_envs": 4096, "simulator._target_": "pbhc_amd.simulator.replay_stub.ReplaySimStub"}, now="t")
+    if a.noise_off:
+        for k in list(cfg.obs.noise_scales.keys()):
+            cfg.obs.noise_scales[k] = 0.0
+    skel = Skeleton.from_motion_config(cfg.robot.motion)
+
+    class _ML:
+        has_contact_mask = a.contact_mask
+
+    nl = len(cfg.domain_rand.get("randomize_link_body_names", []))
+    c, L = env_config.build(_TopView(cfg.env.config), skel, _ML(), 4096, "cpu", nl, seed=1, mode=1 if a.general else 0)
+    cf = S.finalised(c)
+    text = S.emit_header(cf)
+    hdr = os.path.join(a.out, "cfg.h")
+    open(hdr, "w").write(text)
+    return [f'-DPBHC_STATIC_CFG="{hdr}"', f"-DPBHC_SPEC_MODE={int(cf.tracking_mode)}", os.path.join(S.CSRC, "pbhc_env_step_spec.hip")]
+
+
+cmd = [HIPCC] + S.KERNEL_FLAGS + a.defs.split() + ([os.path.join(S.CSRC, "pbhc_kernels.hip")] if a.cfg == "generic" else spec_cmd()) + \
+      ["--cuda-device-only", "-S", "-o", asm]
 subprocess.run(cmd, check=True)
 src = open(asm).read()
+if a.sha256:
+    norm = "".join(l for l in src.splitlines(True) if "__hip_cuid_" not in l).replace(os.path.abspath(a.out), "<out>").replace(ROOT, "<root>")
+    print("sha256:", hashlib.sha256(norm.encode()).hexdigest())
 body = src[src.index("_Z10k_env_step"):]
 census = collections.Counter()
 n = 0
