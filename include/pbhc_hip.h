@@ -548,6 +548,24 @@ int pbhc_env_step_finish(PbhcEnv* env, const PbhcStepIO* io, void* stream);
  * episode_length_buf, motion_start_times and the observation row obs[rec->obs_group]).  A plain launch with no host-side state: a stream
  * capture may record it, the frame index lives in rec->counter. */
 int pbhc_record_motion(PbhcEnv* env, const PbhcStepIO* io, const PbhcRecordIO* rec, void* stream);
+/* Per-clip episode statistics and failure-weighted clip sampling (env.config.clip_statistics / clip_sampling; pbhc_clip_stats.hip).  Raw
+ * device pointers, no PbhcEnv: the step kernel does not know about them.  NULL or sizes < 1 return PBHC_EINVAL without touching the GPU.
+ * pbhc_clip_stats: k_clip_stats on `stream`, to follow the step that left reset_buf, time_out_buf (u8), end_time_ratio_buf and
+ *   last_episode_length_buf [N].  For every env with reset_buf != 0 and slot_clip[env] in [0, M): window[slot_clip[env]] += (1, time_out == 0,
+ *   llrintf(end_time_ratio * 2^24), last_episode_length); window [M,4] int64.  Integer atomics only: the table does not depend on arrival
+ *   order.  A plain launch with no host-side state: a stream capture may record it.
+ * pbhc_clip_sampling_update: one workgroup.  Per clip, in double, with the window's episodes e and failures f:
+ *   E <- f32(decay E + e) (sampling_history), F <- f32(decay F + f) (termination_history), r = (F + prior) / (E + prior),
+ *   success_rate = E > 0 ? 1 - F / E : 0, sampling_prob = f32((1 - floor) r / sum(r) + floor / M); cdf [M] double = the inclusive prefix sum
+ *   of double(sampling_prob); the window is cleared.  decay and uniform_floor in [0, 1], prior_episodes > 0, else PBHC_EINVAL.
+ * pbhc_clip_sample_slots: slot j of slot_clip [N] <- the first i with cdf[i] > u * cdf[M-1] (clamped to M-1),
+ *   u = u01(philox4x32(seed; j, draw_index, 20, 0)[0]): a multinomial draw with replacement that never returns a clip of probability 0.
+ *   cdf [M] double: as pbhc_clip_sampling_update left it (any non-decreasing prefix sum of non-negative weights). */
+int pbhc_clip_stats(const int64_t* reset_buf, const uint8_t* time_out_buf, const float* end_time_ratio_buf, const int64_t* last_episode_length_buf,
+                    const int64_t* slot_clip, int N, int M, int64_t* window, void* stream);
+int pbhc_clip_sampling_update(int64_t* window, float* sampling_history, float* termination_history, float* success_rate, float* sampling_prob,
+                              double* cdf, int M, double decay, double prior_episodes, double uniform_floor, void* stream);
+int pbhc_clip_sample_slots(const double* cdf, int M, uint64_t seed, uint32_t draw_index, int64_t* slot_clip, int N, void* stream);
 /* Second half of a step launched with io->totals_out: `totals` = the element-wise sum over ranks of every shard's totals_out,
  * `num_envs_total` = the number of envs of all ranks.  Must run before the next pbhc_env_step of this env. */
 #define PBHC_NUM_TOTALS 64

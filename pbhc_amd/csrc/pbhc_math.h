@@ -302,6 +302,8 @@ __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0
 // step unchanged: 1 torque RFI, 2 episodic DR (kp, kd, rfi limit, rao), 6 reset start phase + control delay, 9 default joint angles,
 // 11 termination gates (env word 0xFFFFFFFF), 12 / 13 reset-state noise (root / dofs), 14 / 15 obs.noise_process (OU step / stationary
 // redraw), 16 observation noise base, 17 parallel_serial_pd ratios, 18 / 19 parallel_serial_tau (episodic rao / per-step torque).
+// Outside the step: 20 the slot -> clip draw of clip_sampling (k_clip_sample_slots; counter words (slot, draw index, 20, 0)).
+#define PBHC_RNG_STREAM_CLIP_SAMPLING 20u
 // four uniforms of one Philox call, keyed (env, step, stream, idx): for draws that are consumed together
 __device__ __forceinline__ void rng_uniform4(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, uint32_t idx, float u[4]) {
   uint32_t o[4];

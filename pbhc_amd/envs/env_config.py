@@ -562,3 +562,35 @@ def record_layout(ec, L, D, Bx, mode):
                 root_lin_vel=(3,), root_ang_vel=(3,), dof_vel=(D,), contact_mask=(2,), motion_times=())
     return dict(total_steps=T, obs_group=L.group_names.index("actor_obs"), rows=rows, save_note=ec.get("save_note", None),
                 eval_timestamp=ec.get("eval_timestamp", None), ckpt_dir=ec.get("ckpt_dir", None))
+
+
+CLIP_SAMPLING_DEFAULTS = dict(decay=0.5, prior_episodes=1.0, uniform_floor=0.1)       # a maintainer's choice, untrained
+
+
+def clip_options(ec):
+    """env.config.clip_statistics / env.config.clip_sampling -> plain dict(statistics, sampling, decay, prior_episodes, uniform_floor); both
+    keys absent: everything off.  clip_sampling.enable implies clip_statistics.  Like the recorder this stays out of PbhcEnvConfig and of
+    the layout: the step kernel and its specialised builds do not change with it."""
+    out = dict(statistics=bool(ec.get("clip_statistics", False)), sampling=False, **CLIP_SAMPLING_DEFAULTS)
+    cs = ec.get("clip_sampling", None)
+    if cs is None:
+        return out
+    if not hasattr(cs, "get"):
+        raise _lib.PbhcError(f"env.config.clip_sampling must be a mapping (enable, decay, prior_episodes, uniform_floor), got {cs!r}")
+    unknown = sorted(set(cs.keys()) - {"enable", *CLIP_SAMPLING_DEFAULTS})
+    if unknown:
+        raise _lib.PbhcError(f"env.config.clip_sampling: unknown keys {unknown}")
+    for k in CLIP_SAMPLING_DEFAULTS:
+        try:
+            out[k] = float(cs.get(k, CLIP_SAMPLING_DEFAULTS[k]))
+        except (TypeError, ValueError):
+            raise _lib.PbhcError(f"env.config.clip_sampling.{k} must be a number, got {cs.get(k)!r}") from None
+    if not 0.0 <= out["decay"] <= 1.0:                     # (a NaN fails every one of these comparisons)
+        raise _lib.PbhcError(f"env.config.clip_sampling.decay must lie in [0, 1], got {out['decay']}")
+    if not (out["prior_episodes"] > 0.0 and out["prior_episodes"] < float("inf")):
+        raise _lib.PbhcError(f"env.config.clip_sampling.prior_episodes must be > 0 and finite, got {out['prior_episodes']}")
+    if not 0.0 <= out["uniform_floor"] <= 1.0:
+        raise _lib.PbhcError(f"env.config.clip_sampling.uniform_floor must lie in [0, 1], got {out['uniform_floor']}")
+    out["sampling"] = bool(cs.get("enable", False))
+    out["statistics"] = out["statistics"] or out["sampling"]
+    return out

@@ -39,6 +39,8 @@ class LeggedRobotGeneralTracking(LeggedRobotMotionTracking):
         self.motion_start_idx += self.num_envs
         if self.motion_start_idx >= self.num_motions:
             self.motion_start_idx = 0
+        if self._clip_window is not None:
+            self.wait_finalize()                     # the collector of the last step reads the old slot -> clip table
         self._motion_lib.load_motions(random_sample=False, start_idx=self.motion_start_idx, max_len=self.max_len)
         self.curr_motion_ids = self._motion_lib.slot_clip
         self.reset_all()

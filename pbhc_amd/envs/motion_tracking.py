@@ -225,6 +225,7 @@ class LeggedRobotMotionTracking:
         if self._c.noise_process:                   # OUProcess.reset at construction (legged_robot_base.py:124-127): the stationary law
             self._ou_state.copy_(self._ou_stationary(N))
         self._init_save_motion()
+        self._init_clip_statistics()
         self.init_done = True
 
     def specialise(self, mode="jit", verbose=False):
@@ -581,9 +582,18 @@ class LeggedRobotMotionTracking:
 
     def resample_motion(self, keep_reset_buf=False):
         """motion_tracking.py:385-389 / general_tracking.py:291-297"""
+        if self._clip_window is not None:
+            self.wait_finalize()                     # the collector of the last step, on the finalize stream, reads the OLD slot -> clip table
         if self.common_step_counter > 0:
             self._reference_bodies()                 # the last step's lazy reference bodies belong to the OLD slot -> clip table: freeze them
-        self._motion_lib.load_motions(random_sample=True, max_len=self.max_len)
+        if self._clip["sampling"]:
+            # all-reduce (data parallel) -> update kernel -> device slot draw -> crop rebuild; the reset below cuts episodes short that are
+            # not counted: only step() launches the collector
+            self.update_clip_sampling()
+            self._motion_lib.sample_slots_device(self._seed, self._clip_draws)
+            self._clip_draws += 1
+        else:
+            self._motion_lib.load_motions(random_sample=True, max_len=self.max_len)
         self.curr_motion_ids = self._motion_lib.slot_clip
         self._reset_all_state(keep_reset_buf=keep_reset_buf)
 
@@ -755,6 +765,8 @@ class LeggedRobotMotionTracking:
             _lib.check(self._lib.pbhc_env_step(self._env, C.byref(io), _lib.current_stream()), "pbhc_env_step")
             if self._rec is not None:
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), _lib.current_stream()), "pbhc_record_motion")
+            if self._clip_window is not None:
+                self._launch_clip_stats(_lib.current_stream())
         else:
             # the fused launch here, its one-workgroup reduction on the side stream (set_finalize_stream): this stream goes straight on to
             # the policy forward of the new observations; the reduction is joined again before the next launch (wait_finalize)
@@ -766,6 +778,8 @@ class LeggedRobotMotionTracking:
             self._step_done.record(cur)
             fs.wait_event(self._step_done)
             _lib.check(self._lib.pbhc_env_step_finish(self._env, C.byref(io), fs.cuda_stream), "pbhc_env_step_finish")
+            if self._clip_window is not None:        # off the step -> policy -> step chain; wait_finalize() orders it before the next step
+                self._launch_clip_stats(fs.cuda_stream)
             self._fin_done.record(fs)
             self._fin_pending = True
         if self._totals is not None:
@@ -887,6 +901,55 @@ class LeggedRobotMotionTracking:
         self.saved_motion_path = save_path
         print(f"Saved motion data to {save_path}")
 
+    # ---- per-clip episode statistics / failure-weighted clip sampling (env.config.clip_statistics, clip_sampling) ----
+    def _init_clip_statistics(self):
+        """`_clip_window [M,4]` int64 (episodes, failures, sum of end_time_ratio * 2^24, sum of episode lengths) per unique clip, filled by
+        k_clip_stats after every fused step: nothing of it touches the host.  None when the keys are absent — then no launch is added."""
+        self._clip = env_config.clip_options(self.config)
+        self._clip_window, self._clip_draws = None, 0
+        if self._clip["statistics"]:
+            self._clip_window = torch.zeros(self._motion_lib._num_unique_motions, 4, dtype=torch.int64, device=self.device)
+
+    def _launch_clip_stats(self, stream):
+        ml = self._motion_lib
+        _lib.check(self._lib.pbhc_clip_stats(self.reset_buf.data_ptr(), self.time_out_buf.data_ptr(), self.end_time_ratio_buf.data_ptr(),
+                                             self.last_episode_length_buf.data_ptr(), ml.slot_clip.data_ptr(), self.num_envs,
+                                             ml._num_unique_motions, self._clip_window.data_ptr(), stream), "pbhc_clip_stats")
+
+    def _require_clip_statistics(self, what):
+        if self._clip_window is None:
+            raise _lib.PbhcError(f"{what}: env.config.clip_statistics (or clip_sampling.enable) is not set")
+
+    def clip_statistics(self):
+        """The episodes that ended in step() since the window was last cleared, per unique clip, as device tensors [M]: `episodes`,
+        `failures` (int64; an episode that ended without a time-out), `end_time_ratio_mean`, `episode_length_mean` (float64, 0 where a
+        clip has no episode).  No host synchronisation."""
+        self._require_clip_statistics("clip_statistics")
+        self.wait_finalize()
+        w = self._clip_window
+        e = w[:, 0].clone()
+        n = e.clamp(min=1).double()
+        return dict(episodes=e, failures=w[:, 1].clone(), end_time_ratio_mean=w[:, 2].double() / 16777216.0 / n,
+                    episode_length_mean=w[:, 3].double() / n)
+
+    def clear_clip_statistics(self):
+        self._require_clip_statistics("clear_clip_statistics")
+        self.wait_finalize()
+        self._clip_window.zero_()
+
+    def update_clip_sampling(self):
+        """Fold the window into the motion library's sampling hooks (`_sampling_history`, `_termination_history`, `_success_rate`,
+        `_sampling_prob`) with the configured decay / prior_episodes / uniform_floor, and clear it.  Data parallel: the window is first
+        summed over the ranks (one exact int64 all-reduce), so every rank holds the same probabilities.  resample_motion() calls it when
+        clip_sampling is enabled; public, so that a user can fold at their own cadence."""
+        self._require_clip_statistics("update_clip_sampling")
+        self.wait_finalize()
+        group = getattr(self, "_stat_group", None)
+        if pdist.active(group):
+            pdist.all_reduce(self._clip_window, group=group)
+        c = self._clip
+        self._motion_lib.update_sampling_device(self._clip_window, c["decay"], c["prior_episodes"], c["uniform_floor"])
+
     # ---- logging: device-side means, read back on demand (no per-step sync) ----------------
     def read_log(self):
         self.wait_finalize()
@@ -922,6 +985,12 @@ class LeggedRobotMotionTracking:
         for i, k in enumerate(env_config.SIGMA_KEYS):
             out["adp_sigma_" + k] = g[K["PBHC_G_SIGMA"] + i]
             out["error_ema_" + k] = g[K["PBHC_G_EMA"] + i]
+        if self._clip_window is not None:                 # one device -> host copy: the window's two count columns and max(_sampling_prob)
+            w = self._clip_window
+            t = torch.stack([w[:, 0].sum().double(), w[:, 1].sum().double(), self._motion_lib._sampling_prob.max().double()]).cpu().numpy()
+            out["clip_episodes"] = t[0]
+            out["clip_success_rate"] = 1.0 - t[1] / t[0] if t[0] > 0 else 0.0
+            out["clip_sampling_concentration"] = w.shape[0] * t[2]
         self.log_dict.update({k: torch.tensor(float(v)) for k, v in out.items()})
         return out
 

@@ -98,6 +98,7 @@ class MotionLib:
         self._termination_history = torch.zeros(len(clips), device=self.device)
         self._success_rate = torch.zeros(len(clips), device=self.device)
         self._sampling_history = torch.zeros(len(clips), device=self.device)
+        self._sampling_cdf = None          # double [M], written by update_sampling_device (clip_sampling only)
         self.slot_clip = torch.zeros(num_envs, dtype=torch.long, device=self.device)
         self.table = _lib.PbhcMotionTable()
         if self.max_len > 0 and any(np.asarray(c["pose_aa"]).shape[0] >= self.max_len for c in clips):
@@ -244,6 +245,35 @@ class MotionLib:
         self._curr_motion_ids = self.slot_clip
         if self.max_len > 0:
             self._build_slot_crops(crop_starts)
+        return self.slot_clip
+
+    # ---- failure-weighted clip sampling on the device (env.config.clip_sampling; csrc/pbhc_clip_stats.hip) ------
+    def _cdf(self):
+        if self._sampling_cdf is None:
+            self._sampling_cdf = torch.zeros(self._num_unique_motions, dtype=torch.float64, device=self.device)
+        return self._sampling_cdf
+
+    def update_sampling_device(self, window, decay, prior_episodes, uniform_floor):
+        """Fold `window` ([M,4] int64: episodes, failures, ...; cleared here) into the four sampling hooks and the CDF of `_sampling_prob`:
+        E <- decay E + e, F <- decay F + f, r = (F + prior) / (E + prior), p = (1 - floor) r / sum(r) + floor / M."""
+        M = self._num_unique_motions
+        _lib.require_gpu_tensor(window, "window", torch.int64, (M, 4))
+        _lib.check(_lib.lib().pbhc_clip_sampling_update(_lib.ptr(window), _lib.ptr(self._sampling_history), _lib.ptr(self._termination_history),
+                                                        _lib.ptr(self._success_rate), _lib.ptr(self._sampling_prob), _lib.ptr(self._cdf()), M,
+                                                        float(decay), float(prior_episodes), float(uniform_floor), _lib.current_stream()),
+                   "pbhc_clip_sampling_update")
+
+    def sample_slots_device(self, seed, draw_index):
+        """The random slot -> clip assignment of load_motions drawn on the device from the CDF update_sampling_device left, restatable bit
+        for bit: slot j takes the first clip whose CDF exceeds u_j * total, u_j = u01(philox4x32(seed; j, draw_index, 20, 0)[0]).  In place
+        (the step kernel holds the pointer); crops are re-drawn as in load_motions."""
+        if self._sampling_cdf is None:
+            raise _lib.PbhcError("sample_slots_device before update_sampling_device")
+        _lib.check(_lib.lib().pbhc_clip_sample_slots(_lib.ptr(self._sampling_cdf), self._num_unique_motions, int(seed), int(draw_index) & 0xFFFFFFFF,
+                                                     _lib.ptr(self.slot_clip), self.num_envs, _lib.current_stream()), "pbhc_clip_sample_slots")
+        self._curr_motion_ids = self.slot_clip
+        if self.max_len > 0:
+            self._build_slot_crops()
         return self.slot_clip
 
     def get_motion_length(self, slot_ids=None):
