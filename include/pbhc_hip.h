@@ -566,6 +566,21 @@ int pbhc_clip_stats(const int64_t* reset_buf, const uint8_t* time_out_buf, const
 int pbhc_clip_sampling_update(int64_t* window, float* sampling_history, float* termination_history, float* success_rate, float* sampling_prob,
                               double* cdf, int M, double decay, double prior_episodes, double uniform_floor, void* stream);
 int pbhc_clip_sample_slots(const double* cdf, int M, uint64_t seed, uint32_t draw_index, int64_t* slot_clip, int N, void* stream);
+/* Per-clip tracking error of the library sweep (env.library_sweep; pbhc_clip_track.hip).  Raw device pointers, no PbhcEnv: the step kernel
+ * does not know about it.  k_clip_track on `stream`, to follow the step (and pbhc_clip_stats) that left root_states [N,13], dof_state
+ * [N,D,2], ref_time [N] (PbhcStepIO.ref_time_out) and reset_buf [N]; motion_ids [N] and `tbl`: the table entries and the table that step
+ * used, env_origins [N,3].  For every env with slot_clip[env] in [0, M):
+ *   reset_buf != 0: no frame (the post-step state is the new episode's: the terminal frame is not scored); retire[env] = -1 unless retire is
+ *     NULL.  retire may alias slot_clip: the env is then scored on its first episode only.
+ *   otherwise: track_window[slot_clip[env]] += (1, llrintf(e_g 2^20), llrintf(e_l 2^20), llrintf(e_j 2^20)); track_window [M,4] int64, e_g =
+ *     mean_b |p_b - r_b|, e_l = mean_b |(p_b - p_0) - (r_b - r_0)| over the B real bodies (p: the FK pbhc_sim_fk runs, r: the lookup
+ *     pbhc_motion_state runs at ref_time, offset by the origin), e_j = |q - q_ref|_2 — the per-frame E_gmpbpe, E_mpbpe, E_mpjpe of
+ *     measure_traj.py:147-222.  A frame with a non-finite error is not counted.  motion_ids outside the table: skipped.
+ * Integer atomics only: the table does not depend on arrival order.  NULL (retire excepted), N < 1, M < 1, a skeleton beyond the kernel
+ * maxima or a table row that does not fit it return PBHC_EINVAL without touching the GPU. */
+int pbhc_clip_track(const PbhcSkeleton* skel, const PbhcMotionTable* tbl, const float* root_states, const float* dof_state, const float* ref_time,
+                    const float* env_origins, const int64_t* motion_ids, const int64_t* reset_buf, const int64_t* slot_clip, int64_t* retire,
+                    int N, int M, int64_t* track_window, void* stream);
 /* Second half of a step launched with io->totals_out: `totals` = the element-wise sum over ranks of every shard's totals_out,
  * `num_envs_total` = the number of envs of all ranks.  Must run before the next pbhc_env_step of this env. */
 #define PBHC_NUM_TOTALS 64

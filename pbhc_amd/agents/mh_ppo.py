@@ -360,6 +360,14 @@ class MHPPO(OnDeviceAgent):
             obs, _, _, _ = self.env.step({"actions": self.actor.act_inference(obs["actor_obs"])})
         return obs
 
+    @torch.no_grad()
+    def evaluate_library(self, **kw):
+        """Score every unique clip of the motion library once under the current policy (env.library_sweep; **kw: its max_steps, sync_every,
+        before_wave).  Leaves and returns `self.library_metrics`."""
+        self._eval_mode()
+        self.library_metrics = self.env.library_sweep(lambda obs: self.actor.act_inference(obs["actor_obs"]), **kw)
+        return self.library_metrics
+
     def evaluate_policy(self):
         if getattr(self.env, "save_motion", False):
             return self._evaluate_and_record()

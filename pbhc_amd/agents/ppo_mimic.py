@@ -467,6 +467,14 @@ class PPO(OnDeviceAgent):
             obs, _, _, _ = self.env.step({"actions": self.alg.act_inference(obs, hist_encoding=True)})
         return obs
 
+    @torch.no_grad()
+    def evaluate_library(self, **kw):
+        """Score every unique clip of the motion library once under the current policy (env.library_sweep; **kw: its max_steps, sync_every,
+        before_wave).  Leaves and returns `self.library_metrics`."""
+        self._eval_mode()
+        self.library_metrics = self.env.library_sweep(lambda obs: self.alg.act_inference(obs, hist_encoding=True), **kw)
+        return self.library_metrics
+
     def evaluate_policy(self):
         if getattr(self.env, "save_motion", False):
             # the reference's recorder lives in LeggedRobotMotionTracking, which this agent's general-tracking env does not derive from

@@ -653,7 +653,8 @@ int pbhc_sizeof_env_config(void) { return (int)sizeof(PbhcEnvConfig); }
 int pbhc_sizeof_step_io(void) { return (int)sizeof(PbhcStepIO); }
 int pbhc_sizeof_record_io(void) { return (int)sizeof(PbhcRecordIO); }
 
-static int check_skel(const PbhcSkeleton* sk) {
+// (not in the header: shared with pbhc_clip_track.hip, whose kernel indexes LDS with the same chain tables)
+int pbhc_check_skel(const PbhcSkeleton* sk) {
   ARG_CHECK(sk != nullptr);
   ARG_CHECK(sk->num_bodies >= 1 && sk->num_bodies <= sk->num_bodies_ext && sk->num_bodies_ext <= PBHC_MAX_BODIES);
   ARG_CHECK(sk->num_dof == sk->num_bodies - 1 && sk->num_dof <= PBHC_MAX_DOF);
@@ -672,7 +673,7 @@ static int check_skel(const PbhcSkeleton* sk) {
 
 int pbhc_motion_build(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, const float* contact, int F, float dt,
                       float* out_rows, float* scratch, void* stream) {
-  int rc = check_skel(skel);
+  int rc = pbhc_check_skel(skel);
   if (rc) return rc;
   ARG_CHECK(pose_aa && trans && out_rows && scratch && F >= 1 && dt > 0.0f);
   hipStream_t st = (hipStream_t)stream;
@@ -693,7 +694,7 @@ int pbhc_motion_build(const PbhcSkeleton* skel, const float* pose_aa, const floa
 
 int pbhc_motion_build_batch(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, const float* contact, int total_frames, int num_clips,
                             const int32_t* frame_clip, const int32_t* clip_start, const float* clip_dt, float* out_rows, float* scratch, void* stream) {
-  int rc = check_skel(skel);
+  int rc = pbhc_check_skel(skel);
   if (rc) return rc;
   ARG_CHECK(pose_aa && trans && out_rows && scratch && frame_clip && clip_start && clip_dt && total_frames >= 1 && num_clips >= 1 && num_clips <= total_frames);
   hipStream_t st = (hipStream_t)stream;
@@ -722,7 +723,7 @@ int pbhc_motion_state(const PbhcMotionTable* tbl, int Bx, int D, const int64_t* 
 
 int pbhc_sim_fk(const PbhcSkeleton* skel, const float* root_states, const float* dof_pos, const float* dof_vel, int dof_stride, int n,
                 float* out, void* stream) {
-  int rc = check_skel(skel);
+  int rc = pbhc_check_skel(skel);
   if (rc) return rc;
   ARG_CHECK(root_states && dof_pos && dof_vel && out && n >= 0 && dof_stride >= 1);
   if (n == 0) return PBHC_OK;
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(PBHC_G* PBHC_EPB) void k_debug_fk(PbhcSkeleton sk, 
 }
 extern "C" int pbhc_debug_fk(const PbhcSkeleton* skel, const float* root_states, const float* dof_pos, const float* dof_vel, int n, int method, float* out, void* stream) {
   ARG_CHECK(skel);
-  int rc = check_skel(skel);
+  int rc = pbhc_check_skel(skel);
   if (rc) return rc;
   ARG_CHECK(root_states && dof_pos && dof_vel && out && n >= 0 && (method == 0 || method == 1));
   if (method == 1 && !skel_fk_jump(skel->num_bodies_ext, skel->max_depth)) {
@@ -786,7 +787,7 @@ extern "C" int pbhc_debug_fk(const PbhcSkeleton* skel, const float* root_states,
 static int finalize_config(const PbhcEnvConfig* cfg, PbhcEnvConfig* fin, int* lds_stride, size_t* lds_bytes) {
   ARG_CHECK(cfg && fin && lds_stride && lds_bytes);
   ARG_CHECK(cfg->abi_version == PBHC_ABI_VERSION);
-  int rc = check_skel(&cfg->skel);
+  int rc = pbhc_check_skel(&cfg->skel);
   if (rc) return rc;
   const int Bx = cfg->skel.num_bodies_ext;
   ARG_CHECK(cfg->num_envs >= 1);

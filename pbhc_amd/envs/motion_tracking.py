@@ -950,6 +950,102 @@ class LeggedRobotMotionTracking:
         c = self._clip
         self._motion_lib.update_sampling_device(self._clip_window, c["decay"], c["prior_episodes"], c["uniform_floor"])
 
+    # ---- library evaluation: every unique clip once from motion time 0, scored on the device (csrc/pbhc_clip_track.hip) ----
+    def _library_sweep_refusal(self):
+        """why library_sweep() cannot run now, or None — host-side state only, checked before anything is launched"""
+        if getattr(self, "_stat_mode", None) is not None:
+            return "a data-parallel statistics group is active (every rank would sweep the whole library)"
+        if getattr(self, "_rec", None) is not None:
+            return "the evaluation recorder is on (env.config.save_motion): it records env 0's clip, not a library"
+        if self.config.get("enforce_randomize_motion_start_eval", False):
+            return "env.config.enforce_randomize_motion_start_eval is set: the sweep plays every clip from motion time 0"
+        if torch.cuda.is_current_stream_capturing():
+            return "called inside a stream capture (the sweep reads the device once per sync_every steps)"
+        return None
+
+    def library_sweep(self, act, max_steps=None, sync_every=32, before_wave=None):
+        """Play every unique clip of the motion library once from motion time 0 under `act` (obs_dict -> actions [N,D]) and score it on its
+        FIRST episode: ceil(M / N) waves of N clips, wave w = clips w N .. w N + N - 1 on envs 0 .. N - 1 (`load_motions(random_sample=False,
+        start_idx=w N)`; the idle envs of the last wave wrap around to a valid clip and are not scored).  Per wave: `before_wave(w, clip_ids)`
+        (clip_ids [N] int64 on the device, -1 = idle; a ReplaySimStub user installs the wave's replay window there), a reset of every env,
+        one step with zero actions (as reset_all(), counted), then act -> step until every clip's episode has ended — looked at once per
+        `sync_every` steps, the only host reads — or `max_steps` (default: ceil(longest clip of the wave / dt) + 8) have run.  After every
+        step two launches on the stepping stream: k_clip_stats into the sweep's OWN [M,4] episode window and k_clip_track, which scores the
+        frame of every clip still in its first episode and retires the clips whose episode just ended.  The frame that ends an episode
+        is not scored (its post-step state is the next episode's).  Eager, one stream: the finalize stream is detached for the duration,
+        the periodic motion resample of step() is suspended, the training window (`_clip_window`) and the sampling hooks are not touched;
+        afterwards the slot -> clip table is what it was and every env is reset.  Calls set_is_evaluating().
+        -> dict of device tensors [M]: episodes (0/1), failures, success (bool: the episode ended by a time-out), end_time_ratio,
+        episode_length, frames, E_gmpbpe, E_mpbpe (m), E_mpjpe (rad) (float64 means over the scored frames as pbhc_amd.eval.metrics
+        eval_accuracy defines them per frame, NaN without a frame), and host scalars from ONE copy at the end: success_rate (of all M
+        clips), the three errors averaged over the clips with frames, unfinished (clip ids still running at the cap), waves, steps."""
+        why = self._library_sweep_refusal()
+        if why is not None:
+            raise _lib.PbhcError("library_sweep: " + why)
+        ml, N, dev = self._motion_lib, self.num_envs, self.device
+        M = ml._num_unique_motions
+        sync_every = max(1, int(sync_every))
+        fs = self._finalize_stream
+        self.set_finalize_stream(None)                       # (waits for the last step's reduction first)
+        interval = getattr(self, "resample_time_interval", None)
+        if interval is not None:
+            self.resample_time_interval = float("inf")       # step(): counter % inf is never 0
+        window, self._clip_window = self._clip_window, None   # step() does not collect the sweep's episodes into the training window
+        slot_before = ml.slot_clip.clone()
+        crops_before = ml.crop_starts.clone() if ml.max_len > 0 else None
+        self.set_is_evaluating()
+        episodes = torch.zeros(M, 4, dtype=torch.int64, device=dev)
+        track = torch.zeros(M, 4, dtype=torch.int64, device=dev)
+        eval_clip = torch.empty(N, dtype=torch.int64, device=dev)
+        zero_act = torch.zeros(N, self.dim_actions, device=dev)
+        waves, steps, unfinished = -(-M // N), 0, []
+        s, lib = self.simulator, self._lib
+        try:
+            for w in range(waves):
+                ml.load_motions(random_sample=False, start_idx=w * N, max_len=self.max_len)
+                ids = torch.arange(N, device=dev) + w * N
+                eval_clip.copy_(torch.where(ids < M, ids, torch.full_like(ids, -1)))
+                if before_wave is not None:
+                    before_wave(w, eval_clip.clone())
+                self._reset_all_state()
+                cap = int(max_steps) if max_steps is not None else int(np.ceil(float(self.motion_len[:min(N, M - w * N)].max()) / self.dt)) + 8
+                obs = None
+                for k in range(cap):
+                    obs = self.step({"actions": zero_act if k == 0 else act(obs)})[0]
+                    steps += 1
+                    st = _lib.current_stream()
+                    _lib.check(lib.pbhc_clip_stats(self.reset_buf.data_ptr(), self.time_out_buf.data_ptr(), self.end_time_ratio_buf.data_ptr(),
+                                                   self.last_episode_length_buf.data_ptr(), eval_clip.data_ptr(), N, M, episodes.data_ptr(), st),
+                               "pbhc_clip_stats")
+                    _lib.check(lib.pbhc_clip_track(C.byref(s._csk), C.byref(ml.table), s.robot_root_states.data_ptr(), s.dof_state.data_ptr(),
+                                                   self._ref_time.data_ptr(), self.env_origins.data_ptr(), self._slot_clip.data_ptr(),
+                                                   self.reset_buf.data_ptr(), eval_clip.data_ptr(), eval_clip.data_ptr(), N, M, track.data_ptr(), st),
+                               "pbhc_clip_track")
+                    if (k + 1) % sync_every == 0 and not bool((eval_clip >= 0).any()):
+                        break
+                else:
+                    unfinished += eval_clip[eval_clip >= 0].tolist()
+        finally:
+            ml.slot_clip.copy_(slot_before)
+            if crops_before is not None:
+                ml._build_slot_crops(crops_before)
+            self._reset_all_state()
+            self._clip_window = window
+            if interval is not None:
+                self.resample_time_interval = interval
+            self.set_finalize_stream(fs)
+        e = episodes[:, 0]
+        n = e.clamp(min=1).double()
+        frames = track[:, 0]
+        nan = torch.full((M,), float("nan"), dtype=torch.float64, device=dev)
+        err = [torch.where(frames > 0, track[:, k].double() / 1048576.0 / frames.clamp(min=1).double(), nan) for k in (1, 2, 3)]
+        out = dict(episodes=e, failures=episodes[:, 1], success=(e > 0) & (episodes[:, 1] == 0), end_time_ratio=episodes[:, 2].double() / 16777216.0 / n,
+                   episode_length=episodes[:, 3].double() / n, frames=frames, E_gmpbpe=err[0], E_mpbpe=err[1], E_mpjpe=err[2])
+        scored = (frames > 0).double()
+        host = torch.stack([out["success"].double().sum() / M] + [torch.nan_to_num(x).sum() / scored.sum() for x in err]).cpu().tolist()
+        out.update(success_rate=host[0], E_gmpbpe_mean=host[1], E_mpbpe_mean=host[2], E_mpjpe_mean=host[3], unfinished=unfinished, waves=waves, steps=steps)
+        return out
+
     # ---- logging: device-side means, read back on demand (no per-step sync) ----------------
     def read_log(self):
         self.wait_finalize()
