@@ -566,6 +566,34 @@ int pbhc_clip_stats(const int64_t* reset_buf, const uint8_t* time_out_buf, const
 int pbhc_clip_sampling_update(int64_t* window, float* sampling_history, float* termination_history, float* success_rate, float* sampling_prob,
                               double* cdf, int M, double decay, double prior_episodes, double uniform_floor, void* stream);
 int pbhc_clip_sample_slots(const double* cdf, int M, uint64_t seed, uint32_t draw_index, int64_t* slot_clip, int N, void* stream);
+/* Failure-weighted start-time sampling (env.config.start_statistics / start_sampling; pbhc_start_sampling.hip): K phase bins of equal width
+ * per clip.  Raw device pointers, no PbhcEnv: the step kernel does not know about them, it reads start_time through
+ * PbhcStepIO.ovr_start_time.  NULL (where not allowed below), N < 1, M < 1, K outside [1, PBHC_START_MAX_BINS] or a bad rule parameter
+ * return PBHC_EINVAL without touching the GPU.
+ * pbhc_start_stats: k_start_stats on `stream`, to follow the step that left reset_buf, time_out_buf (u8), end_time_ratio_buf and
+ *   last_episode_length_buf [N]; clip_len [M]: the table's motion_len; dt > 0: the control step.  For every env with reset_buf != 0 and
+ *   c = slot_clip[env] in [0, M), in double: pe = end_time_ratio, ps = pe - (last_episode_length * dt) / clip_len[c],
+ *   e = clamp(floor(pe K), 0, K-1), s = clamp(floor(ps K), 0, e); a non-finite phase adds nothing.  window[c][s][0] += 1,
+ *   window[c][e+1][0] -= 1 if e+1 < K (the prefix sum over the bins = episodes that visited each bin), window[c][e][1] += (time_out == 0).
+ *   window [M,K,2] int64.  Integer atomics only: the table does not depend on arrival order.  A plain launch with no host-side state.
+ * pbhc_start_sampling_update: one workgroup per clip.  Per bin b, in double, v_b = the prefix sum of column 0, f_b = column 1:
+ *   V_b <- f32(decay V_b + v_b), F_b <- f32(decay F_b + f_b) (hist_V, hist_F [M,K] float32), r_b = (F_b + prior) / (V_b + prior),
+ *   w_b = sum_{u=0}^{H-1} lambda^u r_{b+u} over b+u <= K-1 (H = lookahead_bins, lambda = lookahead_decay; no wrap-around),
+ *   prob[c][b] = f32((1 - floor) w_b / sum_b w_b + floor / K); cdf [M,K] double = per clip the inclusive prefix sum of double(prob); the
+ *   window is cleared.  decay, uniform_floor, lookahead_decay in [0, 1], prior_episodes > 0, 1 <= lookahead_bins <= K.
+ * pbhc_start_draw: k_start_draw on `stream`; env j if reset_buf is NULL or reset_buf[j] != 0, with c = slot_clip[j] in [0, M):
+ *   (u1, u2) = u01 of words 0 and 1 of philox4x32(seed; j, (uint32)counter[0], 21, salt) (counter: a device double, read not advanced — the
+ *   env globals' step counter; salt: 0 for the per-step launch, the count of redraw-all calls otherwise), or ovr_u[j][0..1] when ovr_u
+ *   [N,2] is not NULL (tests); bin = the first b with cdf[c][b] > u1 cdf[c][K-1], clamped to K-1 — never a bin of probability 0;
+ *   start_time[j] = min(f32(((bin + u2) / K) clip_len[c]) formed in double, the largest float below clip_len[c]).  Other entries of
+ *   start_time are not written.  A plain launch with no host-side state: a replayed graph draws afresh, the counter having moved. */
+#define PBHC_START_MAX_BINS 128
+int pbhc_start_stats(const int64_t* reset_buf, const uint8_t* time_out_buf, const float* end_time_ratio_buf, const int64_t* last_episode_length_buf,
+                     const int64_t* slot_clip, const float* clip_len, double dt, int N, int M, int K, int64_t* window, void* stream);
+int pbhc_start_sampling_update(int64_t* window, float* hist_V, float* hist_F, float* prob, double* cdf, int M, int K, double decay,
+                               double prior_episodes, double uniform_floor, int lookahead_bins, double lookahead_decay, void* stream);
+int pbhc_start_draw(const double* cdf, const float* clip_len, const int64_t* slot_clip, const int64_t* reset_buf, const float* ovr_u, int N, int M,
+                    int K, uint64_t seed, const double* counter, uint32_t salt, float* start_time, void* stream);
 /* Per-clip tracking error of the library sweep (env.library_sweep; pbhc_clip_track.hip).  Raw device pointers, no PbhcEnv: the step kernel
  * does not know about it.  k_clip_track on `stream`, to follow the step (and pbhc_clip_stats) that left root_states [N,13], dof_state
  * [N,D,2], ref_time [N] (PbhcStepIO.ref_time_out) and reset_buf [N]; motion_ids [N] and `tbl`: the table entries and the table that step

@@ -95,7 +95,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_env_step_launch", "pbhc_env_step_finish", "pbhc_mlp_fwd", "pbhc_mlp_fwd_lds_bytes", "pbhc_mlp_pack", "pbhc_mlp_packed_floats", "pbhc_rollout_post2", "pbhc_mlp_fwd_sample", "pbhc_linear_out_bwd",
            "pbhc_env_get_config", "pbhc_env_attach_specialised", "pbhc_env_is_specialised", "pbhc_env_config_finalize", "pbhc_kl_lr_rule", "pbhc_debug_fk", "pbhc_mlp_fwd_cat", "pbhc_conv_encoder_fwd", "pbhc_conv_encoder_lds_bytes",
            "pbhc_record_motion", "pbhc_sizeof_record_io", "pbhc_debug_rotvec_host",
-           "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track"]
+           "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
+           "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw"]
 
 
 class PbhcError(RuntimeError):
@@ -139,6 +140,9 @@ def _load():
     lib.pbhc_clip_sampling_update.argtypes = [vp, vp, vp, vp, vp, vp, i, C.c_double, C.c_double, C.c_double, vp]
     lib.pbhc_clip_sample_slots.argtypes = [vp, i, C.c_uint64, C.c_uint32, vp, i, vp]
     lib.pbhc_clip_track.argtypes = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcMotionTable)] + [vp] * 8 + [i, i, vp, vp]
+    lib.pbhc_start_stats.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, i, i, i, vp, vp]
+    lib.pbhc_start_sampling_update.argtypes = [vp, vp, vp, vp, vp, i, i, C.c_double, C.c_double, C.c_double, i, C.c_double, vp]
+    lib.pbhc_start_draw.argtypes = [vp, vp, vp, vp, vp, i, i, i, C.c_uint64, vp, C.c_uint32, vp, vp]
     lib.pbhc_env_profile.argtypes = [vp, i]
     lib.pbhc_env_profile_read.argtypes = [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]
     lib.pbhc_env_profile_overhead.argtypes = [vp, vp, C.POINTER(C.c_float)]

@@ -242,6 +242,9 @@ def collect(agent, d, obs_dict):
         agent._rollouts_done = agent.__dict__.get("_rollouts_done", 0) + 1
         if agent._dp and agent._stat_mode == "rollout":
             env.sync_globals()                     # sigma / curricula / log means: the mean over the ranks, once per rollout
+        so = getattr(env, "_start", None)          # start_sampling: the fold (outside the graph: an all-reduce under data parallelism)
+        if so is not None and so["sampling"] and agent._rollouts_done % so["update_every_rollouts"] == 0:
+            env.update_start_sampling()
         agent._timer.split()
         agent._compute_returns(agent._last_obs, last_values=last_values)
     return agent._last_obs

@@ -304,6 +304,9 @@ __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0
 // redraw), 16 observation noise base, 17 parallel_serial_pd ratios, 18 / 19 parallel_serial_tau (episodic rao / per-step torque).
 // Outside the step: 20 the slot -> clip draw of clip_sampling (k_clip_sample_slots; counter words (slot, draw index, 20, 0)).
 #define PBHC_RNG_STREAM_CLIP_SAMPLING 20u
+// 21 the start-time draw of start_sampling (k_start_draw; counter words (env, step counter, 21, salt): salt 0 for the per-step launch,
+// the count of redraw-all calls otherwise).
+#define PBHC_RNG_STREAM_START_SAMPLING 21u
 // four uniforms of one Philox call, keyed (env, step, stream, idx): for draws that are consumed together
 __device__ __forceinline__ void rng_uniform4(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, uint32_t idx, float u[4]) {
   uint32_t o[4];

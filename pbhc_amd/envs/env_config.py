@@ -594,3 +594,53 @@ def clip_options(ec):
     out["sampling"] = bool(cs.get("enable", False))
     out["statistics"] = out["statistics"] or out["sampling"]
     return out
+
+
+START_SAMPLING_DEFAULTS = dict(bins=32, decay=0.9, prior_episodes=1.0, uniform_floor=0.1, lookahead_bins=4, lookahead_decay=0.8,
+                               update_every_rollouts=1)                                # a maintainer's choice, untrained
+_START_INT_KEYS = ("bins", "lookahead_bins", "update_every_rollouts")
+
+
+def start_options(ec):
+    """env.config.start_statistics / env.config.start_sampling -> plain dict(statistics, sampling, bins, decay, prior_episodes, uniform_floor,
+    lookahead_bins, lookahead_decay, update_every_rollouts); both keys absent: everything off.  start_sampling.enable implies
+    start_statistics.  lookahead_bins is clamped to bins only where it was NOT given (the default 4 with fewer than 4 bins); a given value
+    above bins is refused.  Like clip_options this stays out of PbhcEnvConfig and of the layout."""
+    out = dict(statistics=bool(ec.get("start_statistics", False)), sampling=False, **START_SAMPLING_DEFAULTS)
+    cs = ec.get("start_sampling", None)
+    if cs is None:
+        return out
+    if not hasattr(cs, "get"):
+        raise _lib.PbhcError(f"env.config.start_sampling must be a mapping (enable, {', '.join(START_SAMPLING_DEFAULTS)}), got {cs!r}")
+    unknown = sorted(set(cs.keys()) - {"enable", *START_SAMPLING_DEFAULTS})
+    if unknown:
+        raise _lib.PbhcError(f"env.config.start_sampling: unknown keys {unknown}")
+    for k in START_SAMPLING_DEFAULTS:
+        v = cs.get(k, START_SAMPLING_DEFAULTS[k])
+        try:
+            if isinstance(v, (bool, str)):
+                raise TypeError
+            out[k] = float(v)
+        except (TypeError, ValueError):
+            raise _lib.PbhcError(f"env.config.start_sampling.{k} must be a number, got {v!r}") from None
+    for k in _START_INT_KEYS:
+        if not abs(out[k]) < float("inf") or out[k] != int(out[k]):                        # (a NaN fails the first comparison)
+            raise _lib.PbhcError(f"env.config.start_sampling.{k} must be a whole number, got {out[k]}")
+        out[k] = int(out[k])
+    max_bins = _lib.K["PBHC_START_MAX_BINS"]
+    if not 1 <= out["bins"] <= max_bins:
+        raise _lib.PbhcError(f"env.config.start_sampling.bins must lie in [1, {max_bins}], got {out['bins']}")
+    if "lookahead_bins" not in cs:
+        out["lookahead_bins"] = min(out["lookahead_bins"], out["bins"])
+    if not 1 <= out["lookahead_bins"] <= out["bins"]:
+        raise _lib.PbhcError(f"env.config.start_sampling.lookahead_bins must lie in [1, bins = {out['bins']}], got {out['lookahead_bins']}")
+    if out["update_every_rollouts"] < 1:
+        raise _lib.PbhcError(f"env.config.start_sampling.update_every_rollouts must be >= 1, got {out['update_every_rollouts']}")
+    for k in ("decay", "uniform_floor", "lookahead_decay"):
+        if not 0.0 <= out[k] <= 1.0:                       # (a NaN fails every one of these comparisons)
+            raise _lib.PbhcError(f"env.config.start_sampling.{k} must lie in [0, 1], got {out[k]}")
+    if not (out["prior_episodes"] > 0.0 and out["prior_episodes"] < float("inf")):
+        raise _lib.PbhcError(f"env.config.start_sampling.prior_episodes must be > 0 and finite, got {out['prior_episodes']}")
+    out["sampling"] = bool(cs.get("enable", False))
+    out["statistics"] = out["statistics"] or out["sampling"]
+    return out

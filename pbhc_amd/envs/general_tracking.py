@@ -39,10 +39,11 @@ class LeggedRobotGeneralTracking(LeggedRobotMotionTracking):
         self.motion_start_idx += self.num_envs
         if self.motion_start_idx >= self.num_motions:
             self.motion_start_idx = 0
-        if self._clip_window is not None:
-            self.wait_finalize()                     # the collector of the last step reads the old slot -> clip table
+        if self._clip_window is not None or self._start_window is not None:
+            self.wait_finalize()                     # the collectors of the last step read the old slot -> clip table
         self._motion_lib.load_motions(random_sample=False, start_idx=self.motion_start_idx, max_len=self.max_len)
         self.curr_motion_ids = self._motion_lib.slot_clip
+        self._redraw_start_times()                   # start_sampling: the buffered start times belong to the old table's clip lengths
         self.reset_all()
 
     def read_log(self):

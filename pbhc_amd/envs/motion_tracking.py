@@ -141,7 +141,7 @@ class LeggedRobotMotionTracking:
         self.init_done = False
         self.config = config
         self._lib = _lib.lib()
-        self.is_evaluating = False
+        self._is_evaluating = False
         # ---- BaseTask.__init__ (base_task.py:20-64)
         self.simulator = get_class(config.simulator._target_)(config=config, device=device)
         self.headless = config.headless
@@ -209,6 +209,7 @@ class LeggedRobotMotionTracking:
         self.specialise(os.environ.get("PBHC_SPECIALISE", "jit"))
         self._totals, self._stat_pending, self._stat_group, self._num_envs_total = None, None, None, float(N)     # enable_global_statistics()
         self._finalize_stream, self._step_done, self._fin_done, self._fin_pending = None, None, None, False        # set_finalize_stream()
+        self._init_start_sampling()                 # before _build_io: the step's io names the start-time buffer
         self._init_buffers()
         self._init_obs_buffers()
         self._build_io()
@@ -389,6 +390,8 @@ class LeggedRobotMotionTracking:
         self._io_epoch = getattr(self, "_io_epoch", 0) + 1        # captured graphs of the step hold these addresses: a new epoch invalidates them
         self._overrides = {}
         self._replay_version = -1
+        if self._start_time is not None and self._start_sampling_live():
+            io.ovr_start_time = p(self._start_time)             # the reset path's start time: k_start_draw's buffer (start_sampling)
 
     def set_profiling(self, on=True):
         """per-launch HIP event pairs on k_env_step (bench.py's roofline meter; read with pbhc_env_profile_read).  While it is on the step
@@ -479,6 +482,7 @@ class LeggedRobotMotionTracking:
         self._io_epoch += 1
         for k, v in self._overrides.items():
             setattr(self._io, k, None if v is None else v.data_ptr())
+        self._point_start_time()                     # start_sampling: injected start times win while set, clearing them re-points the buffer
 
     # ---- data-parallel runs: batch statistics over ALL ranks' envs ---------------------------
     def enable_global_statistics(self, group=None, mode="rollout"):
@@ -554,6 +558,19 @@ class LeggedRobotMotionTracking:
     def set_is_evaluating(self):
         self.is_evaluating = True
 
+    @property
+    def is_evaluating(self):
+        return self._is_evaluating
+
+    @is_evaluating.setter
+    def is_evaluating(self, v):
+        """(a property since start_sampling: evaluation suspends it — the step's start-time pointer and the collector follow the flag)"""
+        changed = bool(v) != self._is_evaluating
+        self._is_evaluating = bool(v)
+        if changed and getattr(self, "_start_window", None) is not None:
+            self._io_epoch += 1                      # a captured graph of steps holds, or does not hold, the collector's launches
+            self._point_start_time()
+
     def _resample_motion_times(self, env_ids):
         # motion_tracking.py:369-378
         if len(env_ids) == 0:
@@ -561,6 +578,9 @@ class LeggedRobotMotionTracking:
         self.motion_len[env_ids] = self._motion_lib.get_motion_length(self.motion_ids[env_ids])
         if self.is_evaluating and not self.config.enforce_randomize_motion_start_eval:
             self.motion_start_times[env_ids] = 0.0
+        elif self._start_time is not None and self._start_sampling_live():
+            self.motion_start_times[env_ids] = self._start_time[env_ids]
+            self._redraw_start_times()               # a draw is used once
         else:
             self.motion_start_times[env_ids] = self._motion_lib.sample_time(self.motion_ids[env_ids])
 
@@ -582,8 +602,8 @@ class LeggedRobotMotionTracking:
 
     def resample_motion(self, keep_reset_buf=False):
         """motion_tracking.py:385-389 / general_tracking.py:291-297"""
-        if self._clip_window is not None:
-            self.wait_finalize()                     # the collector of the last step, on the finalize stream, reads the OLD slot -> clip table
+        if self._clip_window is not None or self._start_window is not None:
+            self.wait_finalize()                     # the collectors of the last step, on the finalize stream, read the OLD slot -> clip table
         if self.common_step_counter > 0:
             self._reference_bodies()                 # the last step's lazy reference bodies belong to the OLD slot -> clip table: freeze them
         if self._clip["sampling"]:
@@ -595,6 +615,7 @@ class LeggedRobotMotionTracking:
         else:
             self._motion_lib.load_motions(random_sample=True, max_len=self.max_len)
         self.curr_motion_ids = self._motion_lib.slot_clip
+        self._redraw_start_times()                   # start_sampling: the buffered start times belong to the OLD table's clip lengths
         self._reset_all_state(keep_reset_buf=keep_reset_buf)
 
     def reset_all(self):
@@ -767,6 +788,8 @@ class LeggedRobotMotionTracking:
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), _lib.current_stream()), "pbhc_record_motion")
             if self._clip_window is not None:
                 self._launch_clip_stats(_lib.current_stream())
+            if self._start_window is not None:
+                self._launch_start_sampling(_lib.current_stream())
         else:
             # the fused launch here, its one-workgroup reduction on the side stream (set_finalize_stream): this stream goes straight on to
             # the policy forward of the new observations; the reduction is joined again before the next launch (wait_finalize)
@@ -780,6 +803,8 @@ class LeggedRobotMotionTracking:
             _lib.check(self._lib.pbhc_env_step_finish(self._env, C.byref(io), fs.cuda_stream), "pbhc_env_step_finish")
             if self._clip_window is not None:        # off the step -> policy -> step chain; wait_finalize() orders it before the next step
                 self._launch_clip_stats(fs.cuda_stream)
+            if self._start_window is not None:       # behind the reduction: the step counter k_start_draw keys its draw with is settled
+                self._launch_start_sampling(fs.cuda_stream)
             self._fin_done.record(fs)
             self._fin_pending = True
         if self._totals is not None:
@@ -950,6 +975,103 @@ class LeggedRobotMotionTracking:
         c = self._clip
         self._motion_lib.update_sampling_device(self._clip_window, c["decay"], c["prior_episodes"], c["uniform_floor"])
 
+    # ---- failure-weighted start-time sampling (env.config.start_statistics, start_sampling; csrc/pbhc_start_sampling.hip) ----
+    def _init_start_sampling(self):
+        """`_start_window [M,K,2]` int64 (visit differences, failures per phase bin of every unique clip), filled by k_start_stats after
+        every fused step, and — start_sampling.enable — `_start_time [N]`: the start time every env takes at its NEXT reset, which the step
+        reads through PbhcStepIO.ovr_start_time and k_start_draw refreshes for the envs that just reset.  Both None when the keys are
+        absent: no buffer, no launch, the pointer stays NULL."""
+        self._start = env_config.start_options(self.config)
+        self._start_window, self._start_time, self._start_redraws, self._start_suspended = None, None, 0, False
+        if not self._start["statistics"]:
+            return
+        ml = self._motion_lib
+        if ml.max_len > 0:
+            raise _lib.PbhcError("env.config.start_sampling / start_statistics cannot be combined with robot.motion.motion_max_len crops: slot "
+                                 "times are crop-relative there, a phase bin of the clip means nothing")
+        ml.init_start_sampling(self._start["bins"])
+        self._start_window = torch.zeros(ml._num_unique_motions, self._start["bins"], 2, dtype=torch.int64, device=self.device)
+        if self._start["sampling"]:
+            self._start_time = torch.zeros(self.num_envs, device=self.device)
+            self._redraw_start_times()
+
+    def _start_collecting(self):
+        """suspended, not refused: evaluation and library_sweep() collect nothing and leave the tables alone"""
+        return not self._is_evaluating and not self._start_suspended
+
+    def _start_sampling_live(self):
+        return self._start["sampling"] and self._start_collecting()
+
+    def _point_start_time(self):
+        """io.ovr_start_time: the buffer while start sampling is live, NULL while it is suspended; injected start times (set_injected_draws) win"""
+        if self._start_time is None or self._overrides.get("ovr_start_time") is not None:
+            return
+        p = self._start_time.data_ptr() if self._start_sampling_live() else None
+        if self._io.ovr_start_time != p:
+            self._io.ovr_start_time = p
+            self._io_epoch += 1
+
+    def _step_counter_ptr(self):
+        return self.globals[K["PBHC_G_STEP_COUNTER"]:].data_ptr()
+
+    def _redraw_start_times(self):
+        """a fresh start time for EVERY env from the current tables; salt = the count of these calls (>= 1: the per-step launch uses 0, so a
+        redraw between two steps never repeats a per-step key)"""
+        if self._start_time is None or not self._start_sampling_live():
+            return
+        self._start_redraws += 1
+        self._motion_lib.draw_start_times_device(self._start_time, self._seed, self._step_counter_ptr(), self._start_redraws)
+
+    def _launch_start_sampling(self, stream):
+        if not self._start_collecting():
+            return
+        ml = self._motion_lib
+        M, Kb = ml._num_unique_motions, self._start["bins"]
+        _lib.check(self._lib.pbhc_start_stats(self.reset_buf.data_ptr(), self.time_out_buf.data_ptr(), self.end_time_ratio_buf.data_ptr(),
+                                              self.last_episode_length_buf.data_ptr(), ml.slot_clip.data_ptr(), ml._motion_lengths.data_ptr(),
+                                              float(self.dt), self.num_envs, M, Kb, self._start_window.data_ptr(), stream), "pbhc_start_stats")
+        if self._start_time is not None:             # the envs that just reset used their draw: the next one (salt 0, keyed by the new counter)
+            ml.draw_start_times_device(self._start_time, self._seed, self._step_counter_ptr(), 0, reset_buf=self.reset_buf, stream=stream)
+
+    def _require_start_statistics(self, what):
+        if self._start_window is None:
+            raise _lib.PbhcError(f"{what}: env.config.start_statistics (or start_sampling.enable) is not set")
+
+    def start_statistics(self):
+        """The episodes that ended in step() since the window was last cleared or folded, per unique clip and phase bin, as device tensors
+        [M,K]: `visits` (int64: episodes that passed through the bin), `failures` (int64: episodes that ended in it without a time-out),
+        `visits_history`, `failures_history` (float32: the decayed sums of the folds) and `prob` (float32: the start-bin law in force).
+        No host synchronisation."""
+        self._require_start_statistics("start_statistics")
+        self.wait_finalize()
+        w, ml = self._start_window, self._motion_lib
+        return dict(visits=torch.cumsum(w[:, :, 0], dim=1), failures=w[:, :, 1].clone(), visits_history=ml._start_visits.clone(),
+                    failures_history=ml._start_failures.clone(), prob=ml._start_prob.clone())
+
+    def clear_start_statistics(self):
+        self._require_start_statistics("clear_start_statistics")
+        self.wait_finalize()
+        self._start_window.zero_()
+
+    def update_start_sampling(self):
+        """The fold: the window into the motion library's start-sampling tables (`_start_visits`, `_start_failures`, `_start_prob`,
+        `_start_cdf`) with the configured decay / prior_episodes / uniform_floor / look-ahead, the window cleared, then — start_sampling.enable —
+        a fresh start time for every env.  Data parallel: the window is first summed over the ranks (one exact int64 all-reduce), so every
+        rank holds the same law.  The rollout driver calls it every update_every_rollouts rollouts; public, so that a user can fold at
+        their own cadence.  Suspended (evaluation, library_sweep): nothing happens, -> False."""
+        self._require_start_statistics("update_start_sampling")
+        if not self._start_collecting():
+            return False
+        self.wait_finalize()
+        group = getattr(self, "_stat_group", None)
+        if pdist.active(group):
+            pdist.all_reduce(self._start_window, group=group)
+        c = self._start
+        self._motion_lib.update_start_sampling_device(self._start_window, c["decay"], c["prior_episodes"], c["uniform_floor"], c["lookahead_bins"],
+                                                      c["lookahead_decay"])
+        self._redraw_start_times()
+        return True
+
     # ---- library evaluation: every unique clip once from motion time 0, scored on the device (csrc/pbhc_clip_track.hip) ----
     def _library_sweep_refusal(self):
         """why library_sweep() cannot run now, or None — host-side state only, checked before anything is launched"""
@@ -991,6 +1113,8 @@ class LeggedRobotMotionTracking:
         if interval is not None:
             self.resample_time_interval = float("inf")       # step(): counter % inf is never 0
         window, self._clip_window = self._clip_window, None   # step() does not collect the sweep's episodes into the training window
+        self._start_suspended = True                         # nor into the start-time window; the step draws its own start times
+        self._point_start_time()
         slot_before = ml.slot_clip.clone()
         crops_before = ml.crop_starts.clone() if ml.max_len > 0 else None
         self.set_is_evaluating()
@@ -1031,6 +1155,8 @@ class LeggedRobotMotionTracking:
                 ml._build_slot_crops(crops_before)
             self._reset_all_state()
             self._clip_window = window
+            self._start_suspended = False
+            self._point_start_time()                         # (back only if the env is no longer evaluating)
             if interval is not None:
                 self.resample_time_interval = interval
             self.set_finalize_stream(fs)
@@ -1081,6 +1207,12 @@ class LeggedRobotMotionTracking:
         for i, k in enumerate(env_config.SIGMA_KEYS):
             out["adp_sigma_" + k] = g[K["PBHC_G_SIGMA"] + i]
             out["error_ema_" + k] = g[K["PBHC_G_EMA"] + i]
+        if self._start_window is not None:                # one device -> host copy: the window's failures per bin and max(_start_prob)
+            f = self._start_window[:, :, 1].sum(dim=0).double()
+            bins = torch.arange(f.shape[0], dtype=torch.float64, device=self.device)
+            t = torch.stack([f.sum(), (f * bins).sum(), self._motion_lib._start_prob.max().double()]).cpu().numpy()
+            out["start_sampling_concentration"] = f.shape[0] * t[2]
+            out["start_failure_bin_mean"] = t[1] / t[0] if t[0] > 0 else 0.0
         if self._clip_window is not None:                 # one device -> host copy: the window's two count columns and max(_sampling_prob)
             w = self._clip_window
             t = torch.stack([w[:, 0].sum().double(), w[:, 1].sum().double(), self._motion_lib._sampling_prob.max().double()]).cpu().numpy()

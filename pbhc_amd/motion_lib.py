@@ -99,6 +99,8 @@ class MotionLib:
         self._success_rate = torch.zeros(len(clips), device=self.device)
         self._sampling_history = torch.zeros(len(clips), device=self.device)
         self._sampling_cdf = None          # double [M], written by update_sampling_device (clip_sampling only)
+        # start_sampling only (init_start_sampling): per clip and phase bin, the decayed visit / failure histories, the start-bin law, its CDF
+        self._start_visits = self._start_failures = self._start_prob = self._start_cdf = None
         self.slot_clip = torch.zeros(num_envs, dtype=torch.long, device=self.device)
         self.table = _lib.PbhcMotionTable()
         if self.max_len > 0 and any(np.asarray(c["pose_aa"]).shape[0] >= self.max_len for c in clips):
@@ -275,6 +277,40 @@ class MotionLib:
         if self.max_len > 0:
             self._build_slot_crops()
         return self.slot_clip
+
+    # ---- failure-weighted start-time sampling on the device (env.config.start_sampling; csrc/pbhc_start_sampling.hip) ------
+    def init_start_sampling(self, bins):
+        """`_start_visits`, `_start_failures`, `_start_prob` [M,K] float32 and `_start_cdf` [M,K] double for K = `bins` phase bins per unique
+        clip: empty histories, the uniform law.  Refused for a library of max_len crops: a slot's times are relative to ITS crop there."""
+        if self.max_len > 0:
+            raise _lib.PbhcError("env.config.start_sampling / start_statistics with robot.motion.motion_max_len crops: slot times are "
+                                 "crop-relative, a phase bin of the clip means nothing there")
+        M, K, dev = self._num_unique_motions, int(bins), self.device
+        self._start_visits = torch.zeros(M, K, device=dev)
+        self._start_failures = torch.zeros(M, K, device=dev)
+        self._start_prob = torch.full((M, K), 1.0 / K, device=dev)
+        self._start_cdf = torch.cumsum(self._start_prob.double(), dim=1).contiguous()
+
+    def update_start_sampling_device(self, window, decay, prior_episodes, uniform_floor, lookahead_bins, lookahead_decay):
+        """Fold `window` ([M,K,2] int64: visit differences, failures; cleared here) into the start-sampling tables: V <- decay V + visits,
+        F <- decay F + failures, r = (F + prior) / (V + prior), w_b = sum_{u < H} lambda^u r_{b+u}, p = (1 - floor) w / sum(w) + floor / K."""
+        if self._start_cdf is None:
+            raise _lib.PbhcError("update_start_sampling_device before init_start_sampling")
+        M, K = self._start_prob.shape
+        _lib.require_gpu_tensor(window, "window", torch.int64, (M, K, 2))
+        _lib.check(_lib.lib().pbhc_start_sampling_update(_lib.ptr(window), _lib.ptr(self._start_visits), _lib.ptr(self._start_failures),
+                                                         _lib.ptr(self._start_prob), _lib.ptr(self._start_cdf), M, K, float(decay),
+                                                         float(prior_episodes), float(uniform_floor), int(lookahead_bins), float(lookahead_decay),
+                                                         _lib.current_stream()), "pbhc_start_sampling_update")
+
+    def draw_start_times_device(self, start_time, seed, counter_ptr, salt, reset_buf=None, stream=None):
+        """start_time[j] <- (bin + u2) / K * clip length of slot j, bin from `_start_cdf` (k_start_draw, Philox stream 21 keyed by the device
+        step counter at `counter_ptr` and `salt`), for every slot, or for those with reset_buf != 0.  In place; capturable."""
+        M, K = self._start_prob.shape
+        _lib.check(_lib.lib().pbhc_start_draw(_lib.ptr(self._start_cdf), _lib.ptr(self._motion_lengths), _lib.ptr(self.slot_clip),
+                                              None if reset_buf is None else _lib.ptr(reset_buf), None, self.num_envs, M, K, int(seed), counter_ptr,
+                                              int(salt) & 0xFFFFFFFF, _lib.ptr(start_time), _lib.current_stream() if stream is None else stream),
+                   "pbhc_start_draw")
 
     def get_motion_length(self, slot_ids=None):
         if slot_ids is None:
