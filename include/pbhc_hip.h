@@ -665,6 +665,13 @@ int pbhc_ppo_loss(const float* mu, const float* std, const float* value, const f
                   float value_coef, float entropy_coef, int use_clipped_value_loss, float desired_kl, int adapt_lr, float* grad_mu, float* grad_value,
                   float* grad_std, float* scalars, float* scalars_acc, float* lr, float* scratch, void* stream);
 int pbhc_ppo_loss_scratch_floats(int B);
+/* pbhc_ppo_loss's first stage alone: grad_mu, grad_value and *num_partials partial rows of the loss sums in `scratch`; its second stage
+ * (grad_std, scalars, the learning rates) then runs inside the backward's finishing launch, pbhc_colsum_final_ppo_reduce below.
+ * kl_form2: pbhc_ppo_loss's adapt_lr bit 1. */
+int pbhc_ppo_loss_partials(const float* mu, const float* std, const float* value, const float* actions, const float* old_logp, const float* old_mu,
+                           const float* old_sigma, const float* adv, const float* returns, const float* old_values, int B, int A, int R, float clip,
+                           float value_coef, int use_clipped_value_loss, int kl_form2, float* grad_mu, float* grad_value, float* scratch,
+                           int* num_partials, void* stream);
 /* The same learning-rate rule on a KL mean already on the device (data-parallel update: the mean over all ranks, after the all-reduce):
  * lr[i] <- rule(lr[i], *kl_mean) for i < n.  Reference: mh_ppo.py:455-466. */
 int pbhc_kl_lr_rule(float* lr, int n, const float* kl_mean, float desired_kl, void* stream);
@@ -699,6 +706,19 @@ int pbhc_linear_out_bwd(const float* dy, const float* h, const float* saved, con
  * cores); bits 8-15: 32-row tiles per workgroup of the matrix-core form (0 / 1: one — measured in the update: 28.85 / 28.84 / 29.1 ms per update
  * at 1 / 2 / 3, i.e. fewer partial rows buy nothing) */
 void pbhc_debug_out_bwd_variant(int mfma);
+/* pbhc_colsum_final with pbhc_ppo_loss's second stage as one more workgroup of the same launch (same sums in the same order as there): nothing
+ * needs grad_std, scalars[4], scalars_acc or lr before the optimiser pass that follows the backward's finishing launch.  num_jobs may be 0. */
+typedef struct PbhcPpoReduce {
+  const float* scratch;        /* as left by pbhc_ppo_loss_partials; 16-byte aligned */
+  const float* std;
+  float* grad_std;
+  float* scalars;
+  float* scalars_acc;          /* may be NULL */
+  float* lr;
+  int32_t num_partials, B, A, adapt_lr;      /* num_partials from pbhc_ppo_loss_partials; adapt_lr bit 0 as pbhc_ppo_loss */
+  float entropy_coef, desired_kl;
+} PbhcPpoReduce;
+int pbhc_colsum_final_ppo_reduce(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, void* stream);
 
 
 /* One Linear of a training-time Linear / activation stack on the fp32 matrix cores with its activation folded into the GEMM epilogue

@@ -86,6 +86,7 @@ PbhcRecordIO = _S["PbhcRecordIO"]
 PbhcMlpSample = _S["PbhcMlpSample"]
 PbhcMlpInput = _S["PbhcMlpInput"]
 PbhcConvEncoder = _S["PbhcConvEncoder"]
+PbhcPpoReduce = _S["PbhcPpoReduce"]
 
 EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
            "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
@@ -96,7 +97,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_env_get_config", "pbhc_env_attach_specialised", "pbhc_env_is_specialised", "pbhc_env_config_finalize", "pbhc_kl_lr_rule", "pbhc_debug_fk", "pbhc_mlp_fwd_cat", "pbhc_conv_encoder_fwd", "pbhc_conv_encoder_lds_bytes",
            "pbhc_record_motion", "pbhc_sizeof_record_io", "pbhc_debug_rotvec_host",
            "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
-           "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw"]
+           "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
+           "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce"]
 
 
 class PbhcError(RuntimeError):
@@ -153,6 +155,8 @@ def _load():
     lib.pbhc_act_bwd_partials.argtypes = [vp, vp, i, i, i, vp, vp, C.POINTER(C.c_int), vp]
     lib.pbhc_colsum_final.argtypes = [vp, i, vp]
     lib.pbhc_linear_out_bwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
+    lib.pbhc_ppo_loss_partials.argtypes = [vp] * 10 + [i, i, i, f, f, i, i, vp, vp, vp, C.POINTER(C.c_int), vp]
+    lib.pbhc_colsum_final_ppo_reduce.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), vp]
     lib.pbhc_linear_act_fwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
     lib.pbhc_linear_act_fwd_out.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp, vp]
     lib.pbhc_linear_dgrad_act.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i, vp]

@@ -13,7 +13,12 @@ MI355X:
   OVERWRITES, so it is opt-in: only a stack whose owner declared `grad_direct(seq)` — "I zero the gradient buffer before every backward"
   (the agents do) — takes it, and only while the stack has ONE live application; a stack applied twice in outstanding graphs, and
   every stack of user code, hands its gradients back to autograd, which accumulates as usual;
-* ELU runs in place and its derivative is taken from the output (`y > 0 ? 1 : y + 1`), so pre-activations are not kept.
+* ELU runs in place and its derivative is taken from the output (`y > 0 ? 1 : y + 1`), so pre-activations are not kept;
+* every fused backward ends in ONE finishing launch (`pbhc_colsum_final`: bias gradients, the output layer's weight gradient, split-K partials);
+  an owner that brackets several stacks' backwards with begin_deferred_finish() / finish_deferred() gets one for all of them, and may hand
+  finish_deferred() the second stage of its loss (`pbhc_colsum_final_ppo_reduce`: one more workgroup of that launch, not a launch of its own).
+  MHPPO's optimiser step is then 22 launches: 6 forward (the two 128-column ones with their output layers), the loss's first stage, per stack
+  the output layer's one-pass backward + 2 input-gradient and 3 weight-gradient GEMMs, the finishing launch, gradient norm, Adam.
 Same arithmetic as autograd's (the column sums are two-stage fp32 in a fixed order); pinned by the update-parity tests.
 """
 from __future__ import annotations
@@ -119,24 +124,30 @@ def begin_deferred_finish():
     _DEFER["on"] = True
 
 
-def _launch_jobs(job_list, st):
+def _launch_jobs(job_list, st, reduce=None):
+    """`reduce` (a PbhcPpoReduce): the loss's second stage rides in the last launch as one more workgroup (pbhc_colsum_final_ppo_reduce)"""
     MAXJ = _lib.K["PBHC_MAX_COLSUM_JOBS"]
     lib = _lib.lib()
-    for k in range(0, len(job_list), MAXJ):
+    for k in range(0, max(len(job_list), 1), MAXJ):
         chunk = job_list[k:k + MAXJ]
         jobs = (_lib._S["PbhcColsumJob"] * MAXJ)()
         for j, (part, out, nrb, n) in zip(jobs, chunk):
             j.part, j.out, j.num_row_blocks, j.n = part, out, nrb, n
-        _lib.check(lib.pbhc_colsum_final(jobs, len(chunk), st), "pbhc_colsum_final")
+        if reduce is not None and k + MAXJ >= len(job_list):
+            _lib.check(lib.pbhc_colsum_final_ppo_reduce(jobs, len(chunk), C.byref(reduce), st), "pbhc_colsum_final_ppo_reduce")
+        elif chunk:
+            _lib.check(lib.pbhc_colsum_final(jobs, len(chunk), st), "pbhc_colsum_final")
 
 
-def finish_deferred():
-    """launch what the backwards since begin_deferred_finish() left pending (current stream = the stream those backwards ran on)"""
+def finish_deferred(reduce=None):
+    """launch what the backwards since begin_deferred_finish() left pending (current stream = the stream those backwards ran on).
+    reduce: the owner's PbhcPpoReduce — the loss's second stage, whose results nothing reads before the optimiser pass, as one more
+    workgroup of this launch instead of a one-workgroup launch of its own between the loss and the backward"""
     _DEFER["on"] = False
     job_list, keep = _DEFER["jobs"], _DEFER["keep"]
     _DEFER["jobs"], _DEFER["keep"] = [], []
-    if job_list:
-        _launch_jobs(job_list, _lib.current_stream())
+    if job_list or reduce is not None:
+        _launch_jobs(job_list, _lib.current_stream(), reduce)
     del keep
 
 

@@ -20,6 +20,8 @@ What it shares with ppo_mimic.PPO is agents/base.py; the rollout is agents/rollo
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from .. import _lib
@@ -267,37 +269,43 @@ class MHPPO(OnDeviceAgent):
         adapt = int(self.desired_kl is not None and self.schedule == "adaptive")
         on_device_lr = adapt if not self._dp else 0
         st = _lib.current_stream()
-        _lib.check(lib.pbhc_ppo_loss(mu.data_ptr(), self.actor.std.data_ptr(), value.data_ptr(), b["actions"].data_ptr(), b["actions_log_prob"].data_ptr(),
-                                     b["action_mean"].data_ptr(), b["action_sigma"].data_ptr(), b["advantages"].data_ptr(), b["returns"].data_ptr(),
-                                     b["values"].data_ptr(), B, self.num_act, self.num_rew_fn, float(self.clip_param), float(self.value_loss_coef),
-                                     float(self.entropy_coef), int(self.use_clipped_value_loss), float(self.desired_kl or 0.0), on_device_lr,
-                                     self._grad_mu.data_ptr(), self._grad_value.data_ptr(), self._gflat[so:so + sn].data_ptr(), self._loss_scalars.data_ptr(),
-                                     loss["_acc"].data_ptr() if "_acc" in loss else None, self._lr.data_ptr(), self._loss_scratch.data_ptr(), st), "pbhc_ppo_loss")
+        # The loss's first stage here; its one-workgroup second stage (d(loss)/d(std), the loss scalars, the learning-rate rule) rides in the
+        # backward's finishing launch: nothing reads its results before the all-reduce / the optimiser pass.
+        npart = C.c_int(0)
+        _lib.check(lib.pbhc_ppo_loss_partials(mu.data_ptr(), self.actor.std.data_ptr(), value.data_ptr(), b["actions"].data_ptr(), b["actions_log_prob"].data_ptr(),
+                                              b["action_mean"].data_ptr(), b["action_sigma"].data_ptr(), b["advantages"].data_ptr(), b["returns"].data_ptr(),
+                                              b["values"].data_ptr(), B, self.num_act, self.num_rew_fn, float(self.clip_param), float(self.value_loss_coef),
+                                              int(self.use_clipped_value_loss), 0, self._grad_mu.data_ptr(), self._grad_value.data_ptr(),
+                                              self._loss_scratch.data_ptr(), C.byref(npart), st), "pbhc_ppo_loss_partials")
+        red = _lib.PbhcPpoReduce()
+        red.scratch, red.std, red.grad_std = self._loss_scratch.data_ptr(), self.actor.std.data_ptr(), self._gflat[so:so + sn].data_ptr()
+        red.scalars, red.scalars_acc, red.lr = self._loss_scalars.data_ptr(), loss["_acc"].data_ptr() if "_acc" in loss else None, self._lr.data_ptr()
+        red.num_partials, red.B, red.A, red.adapt_lr = npart.value, B, self.num_act, on_device_lr
+        red.entropy_coef, red.desired_kl = float(self.entropy_coef), float(self.desired_kl or 0.0)
+        self._backward_both(mu, value, red)
         na, nc = self._n_actor, self._n_critic
         if self._dp:
             # ONE all-reduce per optimiser step (north_star: "a single RCCL all-reduce of policy gradients per PPO update"): actor + critic
             # segments and, in the slot behind them, the minibatch KL mean (the adaptive learning-rate rule, mh_ppo.py:455-466, needs the
             # mean over ALL ranks' samples) — averaged by the collective itself (ReduceOp.AVG), 5.2 MB, latency-bound on xGMI.
-            self._gflat[na + nc:na + nc + 1].copy_(self._loss_scalars[3:4])
-            self._backward_both(mu, value)
+            self._gflat[na + nc:na + nc + 1].copy_(self._loss_scalars[3:4])      # (behind the backward: its finishing launch leaves the KL mean)
             pdist.allreduce_mean_(self._gflat[:na + nc + 1])
             if adapt:                                    # the rule on the all-rank KL mean: one launch (pdist.kl_lr_rule_ is its host-tensor form)
                 _lib.check(lib.pbhc_kl_lr_rule(self._lr.data_ptr(), 2, self._gflat[na + nc:].data_ptr(), float(self.desired_kl), st), "pbhc_kl_lr_rule")
-        else:
-            self._backward_both(mu, value)
         self._adam2(zero_grad=1)
         self._gflat_clean = True
-        if "_acc" not in loss:                            # ("_acc": summed by the loss kernel's finishing block)
+        if "_acc" not in loss:                            # ("_acc": summed by the loss's second stage)
             loss["Value"] += self._loss_scalars[1]; loss["Surrogate"] += self._loss_scalars[0]; loss["Entropy"] += self._loss_scalars[2]
         return loss
 
-    def _backward_both(self, mu, value):
-        """both networks' backward on this stream, their finishing column-sum launches merged into one (fused_mlp.finish_deferred)"""
+    def _backward_both(self, mu, value, reduce):
+        """both networks' backward on this stream, their finishing column-sum launches merged into one (fused_mlp.finish_deferred) that also
+        carries the loss's second stage (`reduce`, a PbhcPpoReduce)"""
         fused_mlp.begin_deferred_finish()
         try:
             torch.autograd.backward([mu, value], [self._grad_mu, self._grad_value])
         finally:
-            fused_mlp.finish_deferred()
+            fused_mlp.finish_deferred(reduce)
 
     def _update_ppo_eager(self, b, loss):
         """Eager PyTorch form of the update (used only for the optional L2C2 regulariser, mh_ppo.py:488-507)."""

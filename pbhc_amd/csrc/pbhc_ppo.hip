@@ -40,7 +40,8 @@ __device__ __forceinline__ float gsum32(float v) {
 //   partial[blk][0..2] = sum over the block's rows of (max(s1,s2), sum_r max(l1,l2), kl)
 //   gstd_part[blk][a]  = sum over the block's rows of d(surrogate)/d(sigma_a) (before the 1/B).
 // (A "last block finishes the job" ticket was tried instead of the second launch: the device-scope release / acquire it needs is an L2
-// write-back + invalidate per block on this 8-XCD part — 73 us for the pair against 25 us as two launches.)
+// write-back + invalidate per block on this 8-XCD part — 73 us for the pair against 25 us as two launches.  MHPPO's update runs the second
+// stage as one workgroup of its backward's finishing launch instead: pbhc_ppo_loss_partials + pbhc_colsum_final_ppo_reduce.)
 __global__ __launch_bounds__(256) void k_ppo_loss(const float* __restrict__ mu, const float* __restrict__ stdp, const float* __restrict__ value,
                                                   const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ old_mu,
                                                   const float* __restrict__ old_sigma, const float* __restrict__ adv, const float* __restrict__ returns,
@@ -163,66 +164,100 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float* __restrict__ mu, 
 // before the first add, and sums them in block order.
 #define RED_T 1024
 #define RED_CH (RED_T / 32)
-__global__ __launch_bounds__(RED_T) void k_ppo_reduce(const float* __restrict__ partial, const float* __restrict__ gstd_part, const float* __restrict__ stdp,
-                                                      int nblocks, int B, int A, float entropy_coef, float desired_kl, int adapt_lr,
-                                                      float* __restrict__ grad_std, float* __restrict__ scalars, float* __restrict__ lr,
-                                                      float* __restrict__ scalars_acc) {
+struct ReduceArgs {
+  const float *partial, *gstd_part, *stdp;
+  int nblocks, B, A;
+  float entropy_coef, desired_kl;
+  int adapt_lr;
+  float *grad_std, *scalars, *lr, *scalars_acc;
+};
+// NT threads: 1024 in a launch of its own (k_ppo_reduce), 256 as one workgroup of the step's finishing launch (k_colsum_final_reduce), where a
+// thread takes four neighbouring columns of its chunk with 16-byte loads (every load of up to 512 partial rows in flight at once, as with
+// 1024 threads).  Chunk ch sums blocks ch, ch + 32, ... in that order and the chunks are added in order 0..31, whichever thread summed them:
+// the result does not depend on NT.
+template <int NT>
+__device__ __forceinline__ void ppo_reduce_body(const ReduceArgs& P) {
   __shared__ double sh_g[RED_CH][33];
   __shared__ double sh_s[RED_CH][4];
   __shared__ float sh_e[32];
   __shared__ float sh_m[4];
-  const int col = threadIdx.x & 31, chunk = threadIdx.x >> 5;
-  const float lr0 = threadIdx.x < 2 ? lr[threadIdx.x] : 0.0f;       // in flight with the partials
-  const float sig = col < A ? stdp[col] : 1.0f;
-  float gq[16], sq[16];
+  constexpr int V = RED_T / NT;                                     // columns per thread (1, or 4: one 16-byte load per partial row)
+  static_assert(V == 1 || V == 4, "ppo_reduce_body: 1024 or 256 threads");
+  constexpr int TPC = 32 / V;                                       // threads per chunk
+  const int col = threadIdx.x & 31;
+  const int chunk = threadIdx.x / TPC, c0 = (threadIdx.x % TPC) * V;
+  const int A = P.A, nblocks = P.nblocks;
+  const float* __restrict__ partial = P.partial;
+  const float* __restrict__ gstd_part = P.gstd_part;
+  const float lr0 = threadIdx.x < 2 ? P.lr[threadIdx.x] : 0.0f;       // in flight with the partials
+  const float sig = col < A ? P.stdp[col] : 1.0f;
+  double sg[V], ss[V];
 #pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int b = chunk + u * RED_CH;
-    gq[u] = b < nblocks ? gstd_part[(size_t)b * 32 + col] : 0.0f;
-    sq[u] = (b < nblocks && col < 3) ? partial[(size_t)b * LOSS_NP + col] : 0.0f;
-  }
-  double sg = 0.0, ss = 0.0;
+  for (int v = 0; v < V; ++v) { sg[v] = 0.0; ss[v] = 0.0; }
+  for (int b0 = chunk; b0 < nblocks; b0 += 16 * RED_CH) {            // (one trip up to 512 partial rows, two up to 1024)
+    float gq[16][V], sq[16][V];
 #pragma unroll
-  for (int u = 0; u < 16; ++u) { sg += (double)gq[u]; ss += (double)sq[u]; }
-  for (int b = chunk + 16 * RED_CH; b < nblocks; b += RED_CH) {            // (not reached with the entry's 512-block cap)
-    sg += (double)gstd_part[(size_t)b * 32 + col];
-    if (col < 3) ss += (double)partial[(size_t)b * LOSS_NP + col];
+    for (int u = 0; u < 16; ++u) {
+      const int b = b0 + u * RED_CH;
+      const bool in = b < nblocks;
+      const size_t bc = in ? b : nblocks - 1;                       // (clamped and unconditional: a load under a branch of its own waits for the one before it)
+      if constexpr (V == 4) {
+        const float4 g = *reinterpret_cast<const float4*>(gstd_part + bc * 32 + c0);
+        const float4 q = *reinterpret_cast<const float4*>(partial + bc * LOSS_NP);
+        gq[u][0] = in ? g.x : 0.0f; gq[u][1] = in ? g.y : 0.0f; gq[u][2] = in ? g.z : 0.0f; gq[u][3] = in ? g.w : 0.0f;
+        const bool ins = in && c0 == 0;
+        sq[u][0] = ins ? q.x : 0.0f; sq[u][1] = ins ? q.y : 0.0f; sq[u][2] = ins ? q.z : 0.0f; sq[u][3] = 0.0f;
+      } else {
+        const float g = gstd_part[bc * 32 + c0], q = partial[bc * LOSS_NP + min(c0, 2)];
+        gq[u][0] = in ? g : 0.0f;
+        sq[u][0] = (in && c0 < 3) ? q : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) { sg[v] += (double)gq[u][v]; ss[v] += (double)sq[u][v]; }
+    }
   }
-  sh_g[chunk][col] = sg;
-  if (col < 3) sh_s[chunk][col] = ss;
-  if (chunk == 0) sh_e[col] = col < A ? 0.5f + 0.9189385332046727f + logf(sig) : 0.0f;   // entropy terms (mean over rows of identical values)
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    sh_g[chunk][c0 + v] = sg[v];
+    if (c0 + v < 3) sh_s[chunk][c0 + v] = ss[v];
+  }
+  if (threadIdx.x < 32) sh_e[col] = col < A ? 0.5f + 0.9189385332046727f + logf(sig) : 0.0f;   // entropy terms (mean over rows of identical values)
   __syncthreads();
   if (threadIdx.x < A) {
     double t = 0.0;
     for (int ch = 0; ch < RED_CH; ++ch) t += sh_g[ch][threadIdx.x];
     // actor_loss = surrogate - entropy_coef * entropy ; entropy = sum_a (0.5 + 0.5 log(2 pi) + log sigma_a)
-    grad_std[threadIdx.x] = (float)t - entropy_coef / sig;
+    P.grad_std[threadIdx.x] = (float)t - P.entropy_coef / sig;
   }
   if (threadIdx.x >= 32 && threadIdx.x < 35) {              // wave 0's upper half: the three scalar columns, each its own lane
     const int k = threadIdx.x - 32;
     double t = 0.0;
     for (int ch = 0; ch < RED_CH; ++ch) t += sh_s[ch][k];
-    const float mean = (float)(t / (double)B);
+    const float mean = (float)(t / (double)P.B);
     const int slot = k == 2 ? 3 : k;                        // surrogate loss, value loss, (entropy), kl
-    scalars[slot] = mean;
-    if (scalars_acc) scalars_acc[slot] += mean;
+    P.scalars[slot] = mean;
+    if (P.scalars_acc) P.scalars_acc[slot] += mean;
     sh_m[k] = mean;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     float ent = 0.0f;
     for (int a = 0; a < A; ++a) ent += sh_e[a];
-    scalars[2] = ent;
-    if (scalars_acc) scalars_acc[2] += ent;
+    P.scalars[2] = ent;
+    if (P.scalars_acc) P.scalars_acc[2] += ent;
   }
-  if (threadIdx.x < 2 && adapt_lr) {
+  if (threadIdx.x < 2 && P.adapt_lr) {
     const float kl_mean = sh_m[2];
     float l = lr0;
-    if (kl_mean > desired_kl * 2.0f) l = fmaxf(1e-5f, l / 1.5f);
-    else if (kl_mean < desired_kl / 2.0f && kl_mean > 0.0f) l = fminf(1e-2f, l * 1.5f);
-    lr[threadIdx.x] = l;
+    if (kl_mean > P.desired_kl * 2.0f) l = fmaxf(1e-5f, l / 1.5f);
+    else if (kl_mean < P.desired_kl / 2.0f && kl_mean > 0.0f) l = fminf(1e-2f, l * 1.5f);
+    P.lr[threadIdx.x] = l;
   }
 }
+__global__ __launch_bounds__(RED_T) void k_ppo_reduce(ReduceArgs P) { ppo_reduce_body<RED_T>(P); }
 
 // ---- activation backward fused with the bias gradient ------------------------------------------------
 // dz = dy * act'(saved) (written in place over dy when dz == dy) and grad_bias[c] = sum_rows dz[r][c], one pass over the [B,n] slab:
@@ -319,11 +354,11 @@ __device__ __forceinline__ void colsum_wide_block(const float* __restrict__ part
   }
 }
 // the second stage of several layers in one launch (the bias gradients of a whole MLP backward)
-__global__ __launch_bounds__(ACT_T) void k_colsum_final_multi(ColsumJobs J, int num_jobs) {
+__device__ __forceinline__ void colsum_multi_block(const ColsumJobs& J, int num_jobs, int blk) {
   int j = 0;
-  while (j + 1 < num_jobs && (int)blockIdx.x >= J.first_block[j + 1]) ++j;
+  while (j + 1 < num_jobs && blk >= J.first_block[j + 1]) ++j;
   const PbhcColsumJob job = J.job[j];
-  const int block = (int)blockIdx.x - J.first_block[j];
+  const int block = blk - J.first_block[j];
   if (colsum_wide(job.num_row_blocks, job.n) && ((uintptr_t)job.part & 15) == 0) {
     colsum_wide_block(job.part, job.num_row_blocks, job.n, job.out, block);
   } else if (colsum_wide(job.num_row_blocks, job.n)) {             // (unaligned partial images: the tall form over this block's 1024 columns)
@@ -332,6 +367,14 @@ __global__ __launch_bounds__(ACT_T) void k_colsum_final_multi(ColsumJobs J, int 
   } else {
     colsum_final_block(job.part, job.num_row_blocks, job.n, job.out, block);
   }
+}
+__global__ __launch_bounds__(ACT_T) void k_colsum_final_multi(ColsumJobs J, int num_jobs) { colsum_multi_block(J, num_jobs, (int)blockIdx.x); }
+// The same launch with the loss's second stage (k_ppo_reduce's body) as workgroup 0: nothing reads the loss scalars, d(loss)/d(std) or the
+// learning rates before the optimiser pass that follows this launch, so the one-workgroup reduce need not be a launch of its own between the
+// loss and the backward.  It is the first workgroup because it is the longest (four dependent trips to memory).
+__global__ __launch_bounds__(ACT_T) void k_colsum_final_reduce(ColsumJobs J, int num_jobs, ReduceArgs Q) {
+  if (blockIdx.x == 0) ppo_reduce_body<ACT_T>(Q);
+  else colsum_multi_block(J, num_jobs, (int)blockIdx.x - 1);
 }
 __device__ __forceinline__ void colsum_final_block(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out, int block) {
   // 32 columns x 8 row slices per block (a slice reads rows slice, slice + 8, ...: eight independent loads in flight per thread), then the
@@ -782,6 +825,18 @@ int pbhc_rollout_post(const float* rew, const float* values, const int64_t* rese
   return pbhc_rollout_post2(rew, values, reset_buf, time_outs, N, R, gamma, rewards_out, dones_out, cur_reward_sum, cur_episode_length, ep_stats, nullptr, stream);
 }
 
+static int ppo_loss_first_stage(const float* mu, const float* std, const float* value, const float* actions, const float* old_logp, const float* old_mu,
+                                const float* old_sigma, const float* adv, const float* returns, const float* old_values, int B, int A, int R, float clip,
+                                float value_coef, int use_clipped_value_loss, int kl_v2, float* grad_mu, float* grad_value, float* scratch, hipStream_t st) {       // -> partial rows
+  int nb = (B + LOSS_ROWS - 1) / LOSS_ROWS;
+  if (nb > 512) nb = 512;                         // grid-stride over row tiles: the second stage sums <= 512 partials per column in one trip
+  float* partial = scratch;                       // [nb][LOSS_NP]
+  float* gstd_part = scratch + (size_t)nb * LOSS_NP;   // [nb][32]
+  hipLaunchKernelGGL(k_ppo_loss, dim3(nb), dim3(256), 0, st, mu, std, value, actions, old_logp, old_mu, old_sigma, adv, returns, old_values, B, A, R,
+                     clip, value_coef, use_clipped_value_loss, kl_v2, grad_mu, grad_value, partial, gstd_part);
+  return nb;
+}
+
 int pbhc_ppo_loss(const float* mu, const float* std, const float* value, const float* actions, const float* old_logp, const float* old_mu,
                   const float* old_sigma, const float* adv, const float* returns, const float* old_values, int B, int A, int R, float clip,
                   float value_coef, float entropy_coef, int use_clipped_value_loss, float desired_kl, int adapt_lr, float* grad_mu, float* grad_value,
@@ -790,13 +845,23 @@ int pbhc_ppo_loss(const float* mu, const float* std, const float* value, const f
   ARG_CHECK(grad_mu && grad_value && grad_std && scalars && lr && scratch);
   ARG_CHECK(B >= 1 && A >= 1 && A <= 32 && R >= 1 && R <= 32);
   hipStream_t st = (hipStream_t)stream;
-  int nb = (B + LOSS_ROWS - 1) / LOSS_ROWS;
-  if (nb > 512) nb = 512;                         // grid-stride over row tiles: the 1-block second stage sums <= 512 partials per column
-  float* partial = scratch;                       // [nb][LOSS_NP]
-  float* gstd_part = scratch + (size_t)nb * LOSS_NP;   // [nb][32]
-  hipLaunchKernelGGL(k_ppo_loss, dim3(nb), dim3(256), 0, st, mu, std, value, actions, old_logp, old_mu, old_sigma, adv, returns, old_values, B, A, R,
-                     clip, value_coef, use_clipped_value_loss, (adapt_lr >> 1) & 1, grad_mu, grad_value, partial, gstd_part);
-  hipLaunchKernelGGL(k_ppo_reduce, dim3(1), dim3(RED_T), 0, st, partial, gstd_part, std, nb, B, A, entropy_coef, desired_kl, adapt_lr & 1, grad_std, scalars, lr, scalars_acc);
+  const int nb = ppo_loss_first_stage(mu, std, value, actions, old_logp, old_mu, old_sigma, adv, returns, old_values, B, A, R, clip, value_coef,
+                                      use_clipped_value_loss, (adapt_lr >> 1) & 1, grad_mu, grad_value, scratch, st);
+  const ReduceArgs Q{scratch, scratch + (size_t)nb * LOSS_NP, std, nb, B, A, entropy_coef, desired_kl, adapt_lr & 1, grad_std, scalars, lr, scalars_acc};
+  hipLaunchKernelGGL(k_ppo_reduce, dim3(1), dim3(RED_T), 0, st, Q);
+  HIP_CHECK(hipGetLastError());
+  return PBHC_OK;
+}
+
+int pbhc_ppo_loss_partials(const float* mu, const float* std, const float* value, const float* actions, const float* old_logp, const float* old_mu,
+                           const float* old_sigma, const float* adv, const float* returns, const float* old_values, int B, int A, int R, float clip,
+                           float value_coef, int use_clipped_value_loss, int kl_form2, float* grad_mu, float* grad_value, float* scratch,
+                           int* num_partials, void* stream) {
+  ARG_CHECK(mu && std && value && actions && old_logp && old_mu && old_sigma && adv && returns && old_values);
+  ARG_CHECK(grad_mu && grad_value && scratch && num_partials);
+  ARG_CHECK(B >= 1 && A >= 1 && A <= 32 && R >= 1 && R <= 32);
+  *num_partials = ppo_loss_first_stage(mu, std, value, actions, old_logp, old_mu, old_sigma, adv, returns, old_values, B, A, R, clip, value_coef,
+                                       use_clipped_value_loss, kl_form2 & 1, grad_mu, grad_value, scratch, (hipStream_t)stream);
   HIP_CHECK(hipGetLastError());
   return PBHC_OK;
 }
@@ -884,22 +949,33 @@ int pbhc_linear_out_bwd(const float* dy, const float* h, const float* saved, con
   return PBHC_OK;
 }
 
-int pbhc_colsum_final(const PbhcColsumJob* jobs, int num_jobs, void* stream) {
-  ARG_CHECK(jobs && num_jobs >= 1 && num_jobs <= PBHC_MAX_COLSUM_JOBS);
-  ColsumJobs J;
-  int blocks = 0;
-  for (int j = 0; j < PBHC_MAX_COLSUM_JOBS; ++j) {
-    if (j < num_jobs) {
-      ARG_CHECK(jobs[j].part && jobs[j].out && jobs[j].num_row_blocks >= 1 && jobs[j].n >= 1);
-      J.job[j] = jobs[j];
-      blocks += colsum_blocks(jobs[j].num_row_blocks, jobs[j].n);
-    } else {
-      J.job[j] = PbhcColsumJob{nullptr, nullptr, 0, 0};
-    }
-  }
+static int colsum_fill(const PbhcColsumJob* jobs, int num_jobs, ColsumJobs& J) {       // -> workgroups
+  for (int j = 0; j < PBHC_MAX_COLSUM_JOBS; ++j) J.job[j] = j < num_jobs ? jobs[j] : PbhcColsumJob{nullptr, nullptr, 0, 0};
   int acc = 0;
   for (int j = 0; j < PBHC_MAX_COLSUM_JOBS; ++j) { J.first_block[j] = acc; acc += colsum_blocks(J.job[j].num_row_blocks, J.job[j].n); }
+  return acc;
+}
+
+int pbhc_colsum_final(const PbhcColsumJob* jobs, int num_jobs, void* stream) {
+  ARG_CHECK(jobs && num_jobs >= 1 && num_jobs <= PBHC_MAX_COLSUM_JOBS);
+  for (int j = 0; j < num_jobs; ++j) ARG_CHECK(jobs[j].part && jobs[j].out && jobs[j].num_row_blocks >= 1 && jobs[j].n >= 1);
+  ColsumJobs J;
+  const int blocks = colsum_fill(jobs, num_jobs, J);
   hipLaunchKernelGGL(k_colsum_final_multi, dim3(blocks), dim3(ACT_T), 0, (hipStream_t)stream, J, num_jobs);
+  HIP_CHECK(hipGetLastError());
+  return PBHC_OK;
+}
+
+int pbhc_colsum_final_ppo_reduce(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, void* stream) {
+  ARG_CHECK(red && num_jobs >= 0 && num_jobs <= PBHC_MAX_COLSUM_JOBS && (jobs || num_jobs == 0));
+  for (int j = 0; j < num_jobs; ++j) ARG_CHECK(jobs[j].part && jobs[j].out && jobs[j].num_row_blocks >= 1 && jobs[j].n >= 1);
+  ARG_CHECK(((uintptr_t)red->scratch & 15) == 0);                        // (the 256-thread reduce reads its partial rows 16 bytes at a time)
+  ARG_CHECK(red->scratch && red->std && red->grad_std && red->scalars && red->lr && red->num_partials >= 1 && red->B >= 1 && red->A >= 1 && red->A <= 32);
+  ColsumJobs J;
+  const int blocks = colsum_fill(jobs, num_jobs, J);
+  const ReduceArgs Q{red->scratch, red->scratch + (size_t)red->num_partials * LOSS_NP, red->std, red->num_partials, red->B, red->A, red->entropy_coef,
+                     red->desired_kl, red->adapt_lr & 1, red->grad_std, red->scalars, red->lr, red->scalars_acc};
+  hipLaunchKernelGGL(k_colsum_final_reduce, dim3(blocks + 1), dim3(ACT_T), 0, (hipStream_t)stream, J, num_jobs, Q);
   HIP_CHECK(hipGetLastError());
   return PBHC_OK;
 }
