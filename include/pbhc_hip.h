@@ -497,6 +497,26 @@ int pbhc_motion_build(const PbhcSkeleton* skel, const float* pose_aa, const floa
 int pbhc_motion_build_batch(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, const float* contact, int total_frames, int num_clips,
                             const int32_t* frame_clip, const int32_t* clip_start, const float* clip_dt, float* out_rows, float* scratch, void* stream);
 
+/* Lead-in / lead-out frames between a default pose and every clip of a library, BEFORE the build (reference: the offline step
+ * robot_motion_process/motion_interpolation_pkl.py, one clip and 23 joints at a time; here any joint count, the whole library in ONE launch,
+ * k_motion_extend).  default_dof: device float [D]. */
+typedef struct PbhcMotionExtend {
+  int32_t start_frames, end_frames;   /* frames added in front of / behind every clip; 0: nothing at that end */
+  int32_t knee_modify;                /* the legs (dofs 0..5, 6..11) move one after the other, the knees (dofs 3, 9) through 1.0 rad */
+  float default_height;               /* root z of the default pose */
+  float default_quat_xyzw[4];         /* its root rotation: pitch and roll are used, the yaw is the clip's */
+  const float* default_dof;
+  float contact_fill;                 /* contact mask of a synthetic frame without knee_modify */
+} PbhcMotionExtend;
+/* The clips' raw arrays concatenated as for pbhc_motion_build_batch — pose_aa [total_in,Bx,3], trans [total_in,3], contact [total_in,2] or NULL
+ * (then out_contact is NULL too and is not touched) — with in_start / out_start [num_clips+1] device int32: first frame of every clip in the
+ * input / output (+ the totals), out_start[c+1] - out_start[c] = in_start[c+1] - in_start[c] + start_frames + end_frames, so
+ * total_out = total_in + num_clips * (start_frames + end_frames).  Output frames inside a clip are copied bit for bit; the synthetic ones
+ * are computed as csrc/pbhc_motion_extend.hip states.  With knee_modify: D >= 12 and frame counts N of 0 or 2 (N / 2 / 2) + 1 == N / 2. */
+int pbhc_motion_extend_batch(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, const float* contact, int total_in, int num_clips,
+                             const int32_t* in_start, const int32_t* out_start, int total_out, PbhcMotionExtend params, float* out_pose_aa,
+                             float* out_trans, float* out_contact, void* stream);
+
 /* Phase lookup + lerp/slerp.  Replaces MotionLibBase.get_motion_state (motion_lib_base.py:123-259).
  * ids [N] int64, times [N], offset [N,3] or NULL -> out [N,row] packed like a frame row
  * (positions include the offset). */

@@ -172,7 +172,7 @@ class LeggedRobotMotionTracking:
         self.skeleton = self.simulator.skeleton
         rc.motion.step_dt = self.dt
         self.max_len = int(getattr(rc.motion, "motion_max_len", -1)) if self.TRACKING_MODE == 1 else -1     # general_tracking.py:60
-        self._motion_lib = MotionLib.from_config(rc.motion, self.skeleton, N, dev, max_len=self.max_len)
+        self._motion_lib = MotionLib.from_config(rc.motion, self.skeleton, N, dev, max_len=self.max_len, robot=rc)
         # host-side draws (slot -> clip sampling, start phases and episodic DR of reset_all): the torch global generator on rank 0 — as the
         # reference — and a rank-keyed generator on the other ranks of a data-parallel run, so that equal seeds do not replicate envs
         self._gen = pdist.host_generator(dev)

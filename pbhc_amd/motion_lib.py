@@ -78,10 +78,19 @@ def rebase_heading(clip, target_heading):
 
 
 class MotionLib:
-    def __init__(self, skeleton, clips, num_envs, device, max_len=-1):
+    def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None):
         """clips: list of clip dicts (see load_motion_file).  max_len > 0: `load_motions` gives every env slot its own random crop of at most
         `max_len` frames of its clip (motion_lib_base.py:420-428) — the tables are then per SLOT (num_envs entries of max_len rows, allocated
-        once so that the step kernel's pointers stay valid) instead of per unique clip."""
+        once so that the step kernel's pointers stay valid) instead of per unique clip.
+        interpolation (motion_interp.Interpolation or None): every clip is cut to [clip_start:clip_end] on the host and gets start_frames /
+        end_frames lead-in / lead-out frames from / to a default pose on the device (`pbhc_motion_extend_batch`) before the build: lengths,
+        tables and crops describe the extended clips.  None, or both frame counts 0: no launch."""
+        if interpolation is not None:
+            if interpolation.num_dof != skeleton.num_dof:
+                raise _lib.PbhcError(f"interpolation was set up for {interpolation.num_dof} dofs, the skeleton has {skeleton.num_dof}")
+            clips = [interpolation.trim(c) for c in clips]
+        self.interpolation = interpolation if interpolation is not None and interpolation.active else None
+        added = self.interpolation.added if self.interpolation is not None else 0
         self.skeleton = skeleton
         self.device = torch.device(device)
         self.num_envs = num_envs
@@ -103,38 +112,89 @@ class MotionLib:
         self._start_visits = self._start_failures = self._start_prob = self._start_cdf = None
         self.slot_clip = torch.zeros(num_envs, dtype=torch.long, device=self.device)
         self.table = _lib.PbhcMotionTable()
-        if self.max_len > 0 and any(np.asarray(c["pose_aa"]).shape[0] >= self.max_len for c in clips):
+        self._clips = clips                              # kept for load_motions(target_heading=...) and extended_clips() (host arrays)
+        if self.max_len > 0 and any(np.asarray(c["pose_aa"]).shape[0] + added >= self.max_len for c in clips):
             self._init_slot_tables(clips)
             return
         self.max_len = -1
         self._raw = None
         self.slot_table = self.slot_clip                 # the kernel's motion ids: unique-clip tables, slot -> clip
-        self._clips = clips                              # kept for load_motions(target_heading=...) (host arrays)
         self._build_unique_tables(clips)
+
+    def _extend_device(self, d_pose, d_trans, d_contact, nframes):
+        """The lead-in / lead-out frames of every clip in ONE launch (`pbhc_motion_extend_batch`), on the concatenated raw arrays as
+        `_build_unique_tables` uploads them -> (pose_aa, trans, contact or None, frames per clip) of the extended clips."""
+        ip, dev = self.interpolation, self.device
+        Bx = self.skeleton.num_bodies_ext
+        out_n = [int(F) + ip.added for F in nframes]
+        in_start = np.concatenate([[0], np.cumsum(nframes)]).astype(np.int32)
+        out_start = np.concatenate([[0], np.cumsum(out_n)]).astype(np.int32)
+        total_in, total_out = int(in_start[-1]), int(out_start[-1])
+        d_in, d_out = torch.from_numpy(in_start).to(dev), torch.from_numpy(out_start).to(dev)
+        o_pose = torch.empty(total_out, Bx, 3, device=dev)
+        o_trans = torch.empty(total_out, 3, device=dev)
+        o_contact = torch.empty(total_out, 2, device=dev) if d_contact is not None else None
+        params, d_dof = ip.to_c(dev)
+        _lib.check(_lib.lib().pbhc_motion_extend_batch(C.byref(self._csk), _lib.ptr(d_pose), _lib.ptr(d_trans), _lib.ptr(d_contact), total_in, len(nframes),
+                                                       _lib.ptr(d_in), _lib.ptr(d_out), total_out, params, _lib.ptr(o_pose), _lib.ptr(o_trans),
+                                                       _lib.ptr(o_contact), _lib.current_stream()), "pbhc_motion_extend_batch")
+        # no synchronisation: the inputs, the start arrays and the default joints die with this scope, and the caching allocator hands their
+        # memory out again on this same stream only, behind the launch
+        return o_pose, o_trans, o_contact, out_n
+
+    def _upload_raw(self, clips):
+        """-> (pose_aa [total,Bx,3], trans [total,3], contact [total,2] or None on the device, frames per clip) of the clips concatenated"""
+        Bx, dev = self.skeleton.num_bodies_ext, self.device
+        nframes = [np.asarray(c["pose_aa"]).shape[0] for c in clips]
+        d_pose = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx] for c in clips], axis=0))).to(dev)
+        d_trans = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["root_trans_offset"], dtype=np.float32) for c in clips], axis=0))).to(dev)
+        d_contact = None
+        if self.has_contact_mask:
+            d_contact = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["contact_mask"], dtype=np.float32) for c in clips], axis=0))).to(dev)
+        return d_pose, d_trans, d_contact, nframes
+
+    def extended_clips(self):
+        """The library's clips as the tables were built from them — trimmed, with the lead-in / lead-out frames — as host clip dicts
+        (root_trans_offset, pose_aa, fps, contact_mask if the library has one): what `save_motion_npz` or the deploy side needs."""
+        clips = self._clips
+        if self.interpolation is None:
+            return [dict(c) for c in clips]
+        for c in clips:
+            self._check_clip(c)
+        pose, trans, contact, nf = self._extend_device(*self._upload_raw(clips))
+        pose, trans = pose.cpu().numpy(), trans.cpu().numpy()
+        contact = None if contact is None else contact.cpu().numpy()
+        out, a = [], 0
+        for c, F in zip(clips, nf):
+            e = dict(root_trans_offset=trans[a:a + F].copy(), pose_aa=pose[a:a + F].copy(), fps=int(c["fps"]))
+            if contact is not None:
+                e["contact_mask"] = contact[a:a + F].copy()
+            out.append(e)
+            a += F
+        return out
+
+    def _check_clip(self, c):
+        Bx = self.skeleton.num_bodies_ext
+        if np.asarray(c["pose_aa"]).shape[1] < Bx:
+            raise _lib.PbhcError(f"pose_aa has {np.asarray(c['pose_aa']).shape[1]} bodies, skeleton needs {Bx}")
+        F = np.asarray(c["pose_aa"]).shape[0]
+        if self.has_contact_mask and tuple(np.asarray(c["contact_mask"]).shape) != (F, 2):
+            raise _lib.PbhcError(f"contact mask shape {tuple(np.asarray(c['contact_mask']).shape)} is not supported")
 
     def _build_unique_tables(self, clips, into=None):
         """FK + filtered velocities of EVERY unique clip in one launch set (`pbhc_motion_build_batch`): the clips' frames are concatenated on the
         host, uploaded once, and the kernels stop velocities / the Gaussian filter at clip boundaries — no per-clip launch, copy or
         synchronisation (the reference runs a Python FK per env slot).  `into`: rebuild in place (same row count)."""
         Bx = self.skeleton.num_bodies_ext
-        nframes, dts = [], []
         for c in clips:
-            if np.asarray(c["pose_aa"]).shape[1] < Bx:
-                raise _lib.PbhcError(f"pose_aa has {np.asarray(c['pose_aa']).shape[1]} bodies, skeleton needs {Bx}")
-            F = np.asarray(c["pose_aa"]).shape[0]
-            if self.has_contact_mask and tuple(np.asarray(c["contact_mask"]).shape) != (F, 2):
-                raise _lib.PbhcError(f"contact mask shape {tuple(np.asarray(c['contact_mask']).shape)} is not supported")
-            nframes.append(F); dts.append(1.0 / int(c["fps"]))
+            self._check_clip(c)
+        dts = [1.0 / int(c["fps"]) for c in clips]
+        dev = self.device
+        d_pose, d_trans, d_contact, nframes = self._upload_raw(clips)
+        if self.interpolation is not None:                 # lead-in / lead-out frames: the build below sees the extended clips
+            d_pose, d_trans, d_contact, nframes = self._extend_device(d_pose, d_trans, d_contact, nframes)
         starts = np.concatenate([[0], np.cumsum(nframes)]).astype(np.int32)
         total = int(starts[-1])
-        pose = np.concatenate([np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx] for c in clips], axis=0)
-        trans = np.concatenate([np.asarray(c["root_trans_offset"], dtype=np.float32) for c in clips], axis=0)
-        dev = self.device
-        d_pose = torch.from_numpy(np.ascontiguousarray(pose)).to(dev)
-        d_trans = torch.from_numpy(np.ascontiguousarray(trans)).to(dev)
-        d_contact = None
-        if self.has_contact_mask:
-            d_contact = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["contact_mask"], dtype=np.float32) for c in clips], axis=0))).to(dev)
         d_fc = torch.from_numpy(np.repeat(np.arange(len(clips), dtype=np.int32), nframes)).to(dev)
         d_start = torch.from_numpy(starts).to(dev)
         d_dt = torch.tensor(dts, dtype=torch.float32, device=dev)
@@ -178,6 +238,14 @@ class MotionLib:
             trans = torch.as_tensor(np.asarray(c["root_trans_offset"], dtype=np.float32)).contiguous().to(dev)
             contact = torch.as_tensor(np.asarray(c["contact_mask"], dtype=np.float32)).contiguous().to(dev) if self.has_contact_mask else None
             self._raw.append((pose, trans, contact, int(c["fps"])))
+        if self.interpolation is not None:
+            # once, with the same launch as the unique tables: crops are drawn from the extended clips, as from the reference's processed pickle
+            nf = [r[0].shape[0] for r in self._raw]
+            pose, trans, contact, nf = self._extend_device(torch.cat([r[0] for r in self._raw]), torch.cat([r[1] for r in self._raw]),
+                                                           torch.cat([r[2] for r in self._raw]) if self.has_contact_mask else None, nf)
+            starts = np.concatenate([[0], np.cumsum(nf)])
+            self._raw = [(pose[a:b], trans[a:b], contact[a:b] if contact is not None else None, r[3])
+                         for a, b, r in zip(starts[:-1].tolist(), starts[1:].tolist(), self._raw)]
         self.frames = torch.zeros(N * K, self.row, device=dev)
         self.length_starts = (torch.arange(N, dtype=torch.int32, device=dev) * K).contiguous()
         self.num_frames = torch.ones(N, dtype=torch.int32, device=dev)
@@ -216,15 +284,21 @@ class MotionLib:
         self._motion_lengths.copy_(torch.tensor(lens, dtype=torch.float32))
 
     @classmethod
-    def from_config(cls, mcfg, skeleton, num_envs, device, max_len=-1):
-        """mcfg = config.robot.motion (motion_file = .pkl / .npz / directory); max_len: see __init__."""
+    def from_config(cls, mcfg, skeleton, num_envs, device, max_len=-1, robot=None):
+        """mcfg = config.robot.motion (motion_file = .pkl / .npz / directory); max_len: see __init__.  mcfg.interpolation (absent by default):
+        see motion_interp.Interpolation.from_config; robot = config.robot supplies its default joints and the dof names."""
         path = str(mcfg.motion_file)
         if not os.path.isabs(path) and not os.path.exists(path):
             path = os.path.join(_lib.ROOT, path)
         clips = [c for _, c in load_motion_file(path)]
         if mcfg.get("motion_lib_type", "origin") == "WJX" and len(clips) != 1:
             raise _lib.PbhcError("Not Allowed to load more than one motion!")     # motion_lib_robot_WJX.py:202
-        return cls(skeleton, clips, num_envs, device, max_len=max_len)
+        interpolation = None
+        if mcfg.get("interpolation", None) is not None:
+            from .motion_interp import Interpolation
+
+            interpolation = Interpolation.from_config(mcfg.interpolation, skeleton.num_dof, robot=robot)
+        return cls(skeleton, clips, num_envs, device, max_len=max_len, interpolation=interpolation)
 
     # ---- slot -> clip assignment (load_motions, motion_lib_base.py:293-305) -----------------
     def load_motions(self, random_sample=True, start_idx=0, max_len=-1, target_heading=None, sampling_prob=None, crop_starts=None):

@@ -1,0 +1,83 @@
+"""Write the clips of a motion file as the trainer sees them under `robot.motion.interpolation`: cut to [clip_start:clip_end], with the
+lead-in / lead-out frames from / to the default pose (the job of the reference's robot_motion_process/motion_interpolation_pkl.py, for any
+joint count and any number of clips, on the GPU: `pbhc_motion_extend_batch`).  The deploy side gets the same frames the policy was trained on.
+
+    python tools/interpolate_motion.py --config <config.yaml> --out <clips.npz> [--motion-file <.pkl / .npz / dir>]
+        [--start-frames 30 --end-frames 30 --clip-start 0 --clip-end -1 --knee-modify --contact 0.5 --default-pose pose.npy]
+
+The config supplies the skeleton, the default joint angles and — if it has the key — robot.motion.interpolation; options override the key.
+Output: an .npz through `save_motion_npz`, and next to it a joblib .pkl in the reference's layout (root_trans_offset, pose_aa, dof,
+root_rot, smpl_joints, fps, contact_mask) when `joblib` can be imported.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pbhc_amd import _lib  # noqa: E402
+from pbhc_amd.motion_interp import Interpolation  # noqa: E402
+from pbhc_amd.motion_lib import MotionLib, load_motion_file, save_motion_npz  # noqa: E402
+from pbhc_amd.skeleton import Skeleton  # noqa: E402
+from pbhc_amd.utils.config import load_config  # noqa: E402
+
+
+def reference_layout(clip, dof_axis):
+    """one extended clip -> the dict the reference's convert_pkl writes"""
+    from scipy.spatial.transform import Rotation as sRot
+
+    D = dof_axis.shape[0]
+    pose = clip["pose_aa"]
+    out = dict(root_trans_offset=clip["root_trans_offset"], pose_aa=pose, dof=(pose[:, 1:1 + D] * dof_axis[None]).sum(-1).astype(np.float32),
+               root_rot=sRot.from_rotvec(pose[:, 0].astype(np.float64)).as_quat().astype(np.float32), smpl_joints=np.zeros_like(pose), fps=clip["fps"])
+    if "contact_mask" in clip:
+        out["contact_mask"] = clip["contact_mask"]
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--out", required=True, help=".npz to write (a .pkl of the same stem is written beside it when joblib imports)")
+    ap.add_argument("--motion-file", default=None, help="default: robot.motion.motion_file of the config")
+    ap.add_argument("--start-frames", type=int, default=None)
+    ap.add_argument("--end-frames", type=int, default=None)
+    ap.add_argument("--clip-start", type=int, default=None)
+    ap.add_argument("--clip-end", type=int, default=None)
+    ap.add_argument("--knee-modify", action="store_true", default=None)
+    ap.add_argument("--contact", type=float, default=None)
+    ap.add_argument("--default-pose", default=None, help=".npy of 7 + D floats: translation, xyzw quaternion, joints")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+
+    cfg = load_config(args.config, {}, now="tool")
+    rc = cfg.robot
+    icfg = dict(rc.motion.get("interpolation", None) or {})
+    for key in ("start_frames", "end_frames", "clip_start", "clip_end", "knee_modify", "contact"):
+        if getattr(args, key) is not None:
+            icfg[key] = getattr(args, key)
+    if args.default_pose is not None:
+        icfg["default_pose"] = np.load(args.default_pose).tolist()
+    skel = Skeleton.from_motion_config(rc.motion)
+    path = args.motion_file or str(rc.motion.motion_file)
+    if not os.path.isabs(path) and not os.path.exists(path):
+        path = os.path.join(_lib.ROOT, path)
+    named = load_motion_file(path)
+    ml = MotionLib(skel, [c for _, c in named], 1, args.device, interpolation=Interpolation.from_config(icfg, skel.num_dof, robot=rc))
+    clips = [(name, c) for (name, _), c in zip(named, ml.extended_clips())]
+    save_motion_npz(args.out, clips)
+    print(f"wrote {args.out}: {len(clips)} clip(s), frames {[int(c['pose_aa'].shape[0]) for _, c in clips]}")
+    try:
+        import joblib
+    except ImportError:
+        print("joblib is not installed: no .pkl written")
+        return 0
+    pkl = os.path.splitext(args.out)[0] + ".pkl"
+    joblib.dump({name: reference_layout(c, skel.dof_axis) for name, c in clips}, pkl)
+    print(f"wrote {pkl}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
