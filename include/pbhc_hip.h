@@ -517,6 +517,30 @@ int pbhc_motion_extend_batch(const PbhcSkeleton* skel, const float* pose_aa, con
                              const int32_t* in_start, const int32_t* out_start, int total_out, PbhcMotionExtend params, float* out_pose_aa,
                              float* out_trans, float* out_contact, void* stream);
 
+/* Mirrored and time-scaled copies of every clip of a library, BEFORE the extension and the build (no counterpart in the reference, which
+ * ships seven clips; config key robot.motion.augmentation), the whole library in ONE launch, k_motion_augment.  A library of num_clips clips
+ * becomes num_clips * num_variants clips; output clip src * num_variants + v is variant v of source clip src, v = speed index * (mirror ? 2 : 1)
+ * + mirrored, speed index 0 = speed 1.0, index i > 0 = speeds[i - 1]; variant 0 is the source, bit for bit. */
+#define PBHC_MAX_SPEEDS 8
+typedef struct PbhcMotionAugment {
+  int32_t num_variants;               /* V = (1 + num_speeds) * (mirror ? 2 : 1) */
+  int32_t num_speeds;                 /* playback speeds besides 1.0, <= PBHC_MAX_SPEEDS */
+  int32_t mirror;                     /* every speed also reflected across the x-z plane */
+  int32_t pad;
+  double speeds[PBHC_MAX_SPEEDS];     /* each in [0.25, 4]; the clip keeps its fps */
+} PbhcMotionAugment;
+/* Raw arrays as for pbhc_motion_extend_batch, in_start [num_clips+1], out_start [num_clips*V+1] device int32 (first frame of every clip in the
+ * input / output, then the totals).  A variant of speed s of a clip of F frames has F' = floor((F - 1) / s) + 1 frames (formed in double, one
+ * less if (F' - 1) s > F - 1); output frame k samples the source at x = k s: i0 = floor(x), t = x - i0; t == 0 copies frame i0 bit for bit,
+ * otherwise translation and joint rows are a + t (b - a) in double rounded once, the root row is the short-way slerp of the two root rotations
+ * in double, the contact mask is that of the nearer frame (i0 for t < 0.5).  The mirror, applied after the resampling: translation
+ * (x, -y, z), pose_aa row b = (-x, y, -z) of row perm[b], contact columns swapped.  perm: device int32 [Bx], an involution with perm[0] = 0
+ * (NULL without mirror).  total_out must lie in the range the frame-count formula allows for total_in frames in num_clips clips; an output
+ * clip whose out_start entries disagree with the formula is left unwritten by the kernel. */
+int pbhc_motion_augment_batch(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, const float* contact, int total_in, int num_clips,
+                              const int32_t* in_start, const int32_t* out_start, int total_out, PbhcMotionAugment params, const int32_t* perm,
+                              float* out_pose_aa, float* out_trans, float* out_contact, void* stream);
+
 /* Phase lookup + lerp/slerp.  Replaces MotionLibBase.get_motion_state (motion_lib_base.py:123-259).
  * ids [N] int64, times [N], offset [N,3] or NULL -> out [N,row] packed like a frame row
  * (positions include the offset). */

@@ -23,6 +23,7 @@
 #include <stdio.h>
 
 #include "../../include/pbhc_hip.h"
+#include "pbhc_dquat.h"
 #include "pbhc_math.h"
 
 using namespace pbhc;
@@ -55,20 +56,6 @@ __device__ __forceinline__ double ext_joint(double s, double e, int j, int i, in
   return lead_in ? lin_open(s, e, i + 1, N + 1) : lin_closed(s, e, i + 1, N + 1);
 }
 
-struct d4 { double x, y, z, w; };
-
-__device__ __forceinline__ d4 dq_mul(d4 a, d4 b) {
-  return d4{a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-            a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-
-// scipy's Rotation.from_rotvec: (v sin(a/2) / a, cos(a/2)), the series 1/2 - a^2/48 + a^4/3840 for a <= 1e-3
-__device__ __forceinline__ d4 dq_from_rotvec(double x, double y, double z) {
-  const double a = sqrt(x * x + y * y + z * z);
-  const double s = a <= 1e-3 ? 0.5 - a * a / 48.0 + a * a * a * a / 3840.0 : sin(0.5 * a) / a;
-  return d4{s * x, s * y, s * z, cos(0.5 * a)};
-}
-
 // intrinsic Z-Y'-X'' angles of a unit quaternion: R = Rz(yaw) Ry(pitch) Rx(roll)
 __device__ __forceinline__ void dq_to_zyx(d4 q, double& yaw, double& pitch, double& roll) {
   yaw = atan2(2.0 * (q.w * q.z + q.x * q.y), 1.0 - 2.0 * (q.y * q.y + q.z * q.z));
@@ -79,16 +66,6 @@ __device__ __forceinline__ void dq_to_zyx(d4 q, double& yaw, double& pitch, doub
 __device__ __forceinline__ d4 dq_from_zyx(double yaw, double pitch, double roll) {
   const double cy = cos(0.5 * yaw), sy = sin(0.5 * yaw), cp = cos(0.5 * pitch), sp = sin(0.5 * pitch), cr = cos(0.5 * roll), sr = sin(0.5 * roll);
   return d4{sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy};
-}
-
-// scipy's Slerp([0, 1], [A, B])(t): A * exp(t * log(A^-1 B)), the relative rotation taken the short way round
-__device__ __forceinline__ d4 dq_slerp(d4 A, d4 B, double t) {
-  d4 rel = dq_mul(d4{-A.x, -A.y, -A.z, A.w}, B);
-  if (rel.w < 0.0) rel = d4{-rel.x, -rel.y, -rel.z, -rel.w};
-  const double nv = sqrt(rel.x * rel.x + rel.y * rel.y + rel.z * rel.z);
-  if (!(nv > 0.0)) return A;
-  const double half = t * atan2(nv, rel.w), s = sin(half) / nv;
-  return dq_mul(A, d4{s * rel.x, s * rel.y, s * rel.z, cos(half)});
 }
 
 __global__ __launch_bounds__(EXT_THREADS) void k_motion_extend(ExtAxes ax, int Bx, int D, const float* __restrict__ pose_aa,

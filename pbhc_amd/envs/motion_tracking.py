@@ -884,7 +884,7 @@ class LeggedRobotMotionTracking:
 
     def clip_of_env(self, i):
         """the motion clip env `i` tracks (what its recording is scored against)"""
-        return self._motion_lib._clips[int(self._motion_lib.slot_clip[i])]
+        return self._motion_lib.built_clip(int(self._motion_lib.slot_clip[i]))
 
     @property
     def motion_recorded(self):

@@ -78,19 +78,23 @@ def rebase_heading(clip, target_heading):
 
 
 class MotionLib:
-    def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None):
+    def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None, augmentation=None):
         """clips: list of clip dicts (see load_motion_file).  max_len > 0: `load_motions` gives every env slot its own random crop of at most
         `max_len` frames of its clip (motion_lib_base.py:420-428) — the tables are then per SLOT (num_envs entries of max_len rows, allocated
         once so that the step kernel's pointers stay valid) instead of per unique clip.
         interpolation (motion_interp.Interpolation or None): every clip is cut to [clip_start:clip_end] on the host and gets start_frames /
         end_frames lead-in / lead-out frames from / to a default pose on the device (`pbhc_motion_extend_batch`) before the build: lengths,
-        tables and crops describe the extended clips.  None, or both frame counts 0: no launch."""
+        tables and crops describe the extended clips.  None, or both frame counts 0: no launch.
+        augmentation (motion_augment.Augmentation or None): after the cut and before the extension every clip becomes V clips — itself, its
+        mirror image, time-scaled copies — on the device (`pbhc_motion_augment_batch`): clip src * V + v is variant v of source clip src
+        (`variant_source`, `variant_info`), and everything downstream sees M * V ordinary clips.  None, or no mirror and no speed: no launch."""
         if interpolation is not None:
             if interpolation.num_dof != skeleton.num_dof:
                 raise _lib.PbhcError(f"interpolation was set up for {interpolation.num_dof} dofs, the skeleton has {skeleton.num_dof}")
             clips = [interpolation.trim(c) for c in clips]
         self.interpolation = interpolation if interpolation is not None and interpolation.active else None
         added = self.interpolation.added if self.interpolation is not None else 0
+        self.augmentation = augmentation if augmentation is not None and augmentation.active else None
         self.skeleton = skeleton
         self.device = torch.device(device)
         self.num_envs = num_envs
@@ -101,25 +105,85 @@ class MotionLib:
         self._contact_size = 2
         self.max_len = int(max_len)
         self.generator = None              # torch.Generator for the sampling draws (None: the global one, as the reference)
-        self._num_unique_motions = len(clips)
+        self._clips = clips                              # the SOURCE clips (host arrays), kept for load_motions(target_heading=...) and extended_clips()
+        self._built_clips = None
+        self._init_variants(clips)
+        M = self._num_unique_motions                     # clips as the tables hold them: len(clips) * variants
         # sampling hooks of the reference (setup_constants, motion_lib_base.py:109-118): per-unique-clip tensors a curriculum may write
-        self._sampling_prob = torch.ones(len(clips), device=self.device) / len(clips)
-        self._termination_history = torch.zeros(len(clips), device=self.device)
-        self._success_rate = torch.zeros(len(clips), device=self.device)
-        self._sampling_history = torch.zeros(len(clips), device=self.device)
+        self._sampling_prob = torch.ones(M, device=self.device) / M
+        self._termination_history = torch.zeros(M, device=self.device)
+        self._success_rate = torch.zeros(M, device=self.device)
+        self._sampling_history = torch.zeros(M, device=self.device)
         self._sampling_cdf = None          # double [M], written by update_sampling_device (clip_sampling only)
         # start_sampling only (init_start_sampling): per clip and phase bin, the decayed visit / failure histories, the start-bin law, its CDF
         self._start_visits = self._start_failures = self._start_prob = self._start_cdf = None
         self.slot_clip = torch.zeros(num_envs, dtype=torch.long, device=self.device)
         self.table = _lib.PbhcMotionTable()
-        self._clips = clips                              # kept for load_motions(target_heading=...) and extended_clips() (host arrays)
-        if self.max_len > 0 and any(np.asarray(c["pose_aa"]).shape[0] + added >= self.max_len for c in clips):
+        if self.max_len > 0 and any(F + added >= self.max_len for F in self._variant_frames):
             self._init_slot_tables(clips)
             return
         self.max_len = -1
         self._raw = None
         self.slot_table = self.slot_clip                 # the kernel's motion ids: unique-clip tables, slot -> clip
         self._build_unique_tables(clips)
+
+    def _init_variants(self, clips):
+        """`variant_source`, `variant_info`, the mirror tables and the frame count of every variant (before the extension); the skeleton's
+        symmetry is checked here, once, when the mirror is on"""
+        aug, dev = self.augmentation, self.device
+        self.mirror_body_perm = self.mirror_dof_perm = self.mirror_dof_sign = None
+        self.mirror_asymmetry = None
+        self._d_perm = None
+        if aug is None:
+            self.variant_info = [(i, False, 1.0) for i in range(len(clips))]
+            self._variant_frames = [np.asarray(c["pose_aa"]).shape[0] for c in clips]
+        else:
+            self.variant_info = [(i,) + aug.variant(v) for i in range(len(clips)) for v in range(aug.num_variants)]
+            self._variant_frames = [F for i, c in enumerate(clips) for F in aug.variant_frames(np.asarray(c["pose_aa"]).shape[0], f"clip {i}")]
+            if aug.mirror:
+                from .motion_augment import mirror_tables
+
+                mt = mirror_tables(self.skeleton, aug.symmetry_tol)
+                self.mirror_body_perm = torch.from_numpy(mt.body_perm).to(dev)
+                self.mirror_dof_perm = torch.from_numpy(mt.dof_perm).to(dev)
+                self.mirror_dof_sign = torch.from_numpy(mt.dof_sign).to(dev)
+                self.mirror_asymmetry = mt.asymmetry
+                self._d_perm = torch.from_numpy(mt.body_perm.astype(np.int32)).to(dev)
+        self._num_unique_motions = len(self.variant_info)
+        self.variant_source = torch.from_numpy(np.array([v[0] for v in self.variant_info], dtype=np.int64)).to(dev)
+
+    def _augment_device(self, d_pose, d_trans, d_contact, nframes):
+        """Every variant of every clip in ONE launch (`pbhc_motion_augment_batch`), on the concatenated raw arrays as `_upload_raw` leaves them
+        -> (pose_aa, trans, contact or None, frames per clip) of the len(nframes) * V clips."""
+        aug, dev = self.augmentation, self.device
+        Bx = self.skeleton.num_bodies_ext
+        out_n = [Fo for i, F in enumerate(nframes) for Fo in aug.variant_frames(int(F), f"clip {i}")]
+        in_start = np.concatenate([[0], np.cumsum(nframes)]).astype(np.int32)
+        out_start = np.concatenate([[0], np.cumsum(out_n)]).astype(np.int32)
+        total_in, total_out = int(in_start[-1]), int(out_start[-1])
+        d_in, d_out = torch.from_numpy(in_start).to(dev), torch.from_numpy(out_start).to(dev)
+        o_pose = torch.empty(total_out, Bx, 3, device=dev)
+        o_trans = torch.empty(total_out, 3, device=dev)
+        o_contact = torch.empty(total_out, 2, device=dev) if d_contact is not None else None
+        _lib.check(_lib.lib().pbhc_motion_augment_batch(C.byref(self._csk), _lib.ptr(d_pose), _lib.ptr(d_trans), _lib.ptr(d_contact), total_in, len(nframes),
+                                                        _lib.ptr(d_in), _lib.ptr(d_out), total_out, aug.to_c(), _lib.ptr(self._d_perm), _lib.ptr(o_pose),
+                                                        _lib.ptr(o_trans), _lib.ptr(o_contact), _lib.current_stream()), "pbhc_motion_augment_batch")
+        # no synchronisation, for the reason given in _extend_device
+        return o_pose, o_trans, o_contact, out_n
+
+    def _ingest_device(self, clips):
+        """upload -> augment -> extend: the raw arrays the tables are built from, concatenated on the device
+        -> (pose_aa, trans, contact or None, frames per clip, fps per clip) of the clips as the tables hold them"""
+        for c in clips:
+            self._check_clip(c)
+        d_pose, d_trans, d_contact, nframes = self._upload_raw(clips)
+        fps = [int(c["fps"]) for c in clips]
+        if self.augmentation is not None:                  # variants first: the lead-in / lead-out frames are added to each at full length
+            d_pose, d_trans, d_contact, nframes = self._augment_device(d_pose, d_trans, d_contact, nframes)
+            fps = [f for f in fps for _ in range(self.augmentation.num_variants)]
+        if self.interpolation is not None:                 # lead-in / lead-out frames: the build sees the extended clips
+            d_pose, d_trans, d_contact, nframes = self._extend_device(d_pose, d_trans, d_contact, nframes)
+        return d_pose, d_trans, d_contact, nframes, fps
 
     def _extend_device(self, d_pose, d_trans, d_contact, nframes):
         """The lead-in / lead-out frames of every clip in ONE launch (`pbhc_motion_extend_batch`), on the concatenated raw arrays as
@@ -154,19 +218,18 @@ class MotionLib:
         return d_pose, d_trans, d_contact, nframes
 
     def extended_clips(self):
-        """The library's clips as the tables were built from them — trimmed, with the lead-in / lead-out frames — as host clip dicts
-        (root_trans_offset, pose_aa, fps, contact_mask if the library has one): what `save_motion_npz` or the deploy side needs."""
+        """The library's clips as the tables were built from them — trimmed, every variant of `augmentation` (clip src * V + v), with the
+        lead-in / lead-out frames — as host clip dicts (root_trans_offset, pose_aa, fps, contact_mask if the library has one): what
+        `save_motion_npz` or the deploy side needs."""
         clips = self._clips
-        if self.interpolation is None:
+        if self.interpolation is None and self.augmentation is None:
             return [dict(c) for c in clips]
-        for c in clips:
-            self._check_clip(c)
-        pose, trans, contact, nf = self._extend_device(*self._upload_raw(clips))
+        pose, trans, contact, nf, fps = self._ingest_device(clips)
         pose, trans = pose.cpu().numpy(), trans.cpu().numpy()
         contact = None if contact is None else contact.cpu().numpy()
         out, a = [], 0
-        for c, F in zip(clips, nf):
-            e = dict(root_trans_offset=trans[a:a + F].copy(), pose_aa=pose[a:a + F].copy(), fps=int(c["fps"]))
+        for f, F in zip(fps, nf):
+            e = dict(root_trans_offset=trans[a:a + F].copy(), pose_aa=pose[a:a + F].copy(), fps=f)
             if contact is not None:
                 e["contact_mask"] = contact[a:a + F].copy()
             out.append(e)
@@ -186,22 +249,19 @@ class MotionLib:
         host, uploaded once, and the kernels stop velocities / the Gaussian filter at clip boundaries — no per-clip launch, copy or
         synchronisation (the reference runs a Python FK per env slot).  `into`: rebuild in place (same row count)."""
         Bx = self.skeleton.num_bodies_ext
-        for c in clips:
-            self._check_clip(c)
-        dts = [1.0 / int(c["fps"]) for c in clips]
         dev = self.device
-        d_pose, d_trans, d_contact, nframes = self._upload_raw(clips)
-        if self.interpolation is not None:                 # lead-in / lead-out frames: the build below sees the extended clips
-            d_pose, d_trans, d_contact, nframes = self._extend_device(d_pose, d_trans, d_contact, nframes)
+        d_pose, d_trans, d_contact, nframes, fps = self._ingest_device(clips)
+        dts = [1.0 / f for f in fps]
+        num_clips = len(nframes)
         starts = np.concatenate([[0], np.cumsum(nframes)]).astype(np.int32)
         total = int(starts[-1])
-        d_fc = torch.from_numpy(np.repeat(np.arange(len(clips), dtype=np.int32), nframes)).to(dev)
+        d_fc = torch.from_numpy(np.repeat(np.arange(num_clips, dtype=np.int32), nframes)).to(dev)
         d_start = torch.from_numpy(starts).to(dev)
         d_dt = torch.tensor(dts, dtype=torch.float32, device=dev)
         out = torch.empty(total, self.row, device=dev) if into is None else into
         assert out.shape[0] == total
         scratch = torch.empty(total * Bx * 14, device=dev)
-        _lib.check(_lib.lib().pbhc_motion_build_batch(C.byref(self._csk), _lib.ptr(d_pose), _lib.ptr(d_trans), _lib.ptr(d_contact), total, len(clips),
+        _lib.check(_lib.lib().pbhc_motion_build_batch(C.byref(self._csk), _lib.ptr(d_pose), _lib.ptr(d_trans), _lib.ptr(d_contact), total, num_clips,
                                                       _lib.ptr(d_fc), _lib.ptr(d_start), _lib.ptr(d_dt), _lib.ptr(out), _lib.ptr(scratch),
                                                       _lib.current_stream()), "pbhc_motion_build_batch")
         torch.cuda.current_stream().synchronize()          # ONE synchronisation: the staging tensors above die with this scope
@@ -212,7 +272,7 @@ class MotionLib:
         self.num_frames = torch.tensor(nframes, dtype=torch.int32, device=dev)
         self._motion_dt = d_dt
         self._motion_lengths = torch.tensor([dt * (F - 1) for dt, F in zip(dts, nframes)], dtype=torch.float32, device=dev)
-        self._fill_table(len(clips), int(nframes[0]), dts[0], dts[0] * (nframes[0] - 1))
+        self._fill_table(num_clips, int(nframes[0]), dts[0], dts[0] * (nframes[0] - 1))
 
     def _fill_table(self, num_entries, f0, dt0, len0):
         self.table.frames = self.frames.data_ptr()
@@ -231,6 +291,14 @@ class MotionLib:
         N, K, dev = self.num_envs, self.max_len, self.device
         Bx = self.skeleton.num_bodies_ext
         self._raw = []
+        if self.interpolation is not None or self.augmentation is not None:
+            # once, with the same launches as the unique tables: crops are drawn from the variants / the extended clips, as from the
+            # reference's processed pickle
+            pose, trans, contact, nf, fps = self._ingest_device(clips)
+            starts = np.concatenate([[0], np.cumsum(nf)])
+            self._raw = [(pose[a:b], trans[a:b], contact[a:b] if contact is not None else None, f)
+                         for a, b, f in zip(starts[:-1].tolist(), starts[1:].tolist(), fps)]
+            clips = []
         for c in clips:
             pose = torch.as_tensor(np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx]).contiguous().to(dev)
             if pose.shape[1] != Bx:
@@ -238,14 +306,6 @@ class MotionLib:
             trans = torch.as_tensor(np.asarray(c["root_trans_offset"], dtype=np.float32)).contiguous().to(dev)
             contact = torch.as_tensor(np.asarray(c["contact_mask"], dtype=np.float32)).contiguous().to(dev) if self.has_contact_mask else None
             self._raw.append((pose, trans, contact, int(c["fps"])))
-        if self.interpolation is not None:
-            # once, with the same launch as the unique tables: crops are drawn from the extended clips, as from the reference's processed pickle
-            nf = [r[0].shape[0] for r in self._raw]
-            pose, trans, contact, nf = self._extend_device(torch.cat([r[0] for r in self._raw]), torch.cat([r[1] for r in self._raw]),
-                                                           torch.cat([r[2] for r in self._raw]) if self.has_contact_mask else None, nf)
-            starts = np.concatenate([[0], np.cumsum(nf)])
-            self._raw = [(pose[a:b], trans[a:b], contact[a:b] if contact is not None else None, r[3])
-                         for a, b, r in zip(starts[:-1].tolist(), starts[1:].tolist(), self._raw)]
         self.frames = torch.zeros(N * K, self.row, device=dev)
         self.length_starts = (torch.arange(N, dtype=torch.int32, device=dev) * K).contiguous()
         self.num_frames = torch.ones(N, dtype=torch.int32, device=dev)
@@ -286,7 +346,8 @@ class MotionLib:
     @classmethod
     def from_config(cls, mcfg, skeleton, num_envs, device, max_len=-1, robot=None):
         """mcfg = config.robot.motion (motion_file = .pkl / .npz / directory); max_len: see __init__.  mcfg.interpolation (absent by default):
-        see motion_interp.Interpolation.from_config; robot = config.robot supplies its default joints and the dof names."""
+        see motion_interp.Interpolation.from_config; robot = config.robot supplies its default joints and the dof names.  mcfg.augmentation
+        (absent by default): see motion_augment.Augmentation.from_config."""
         path = str(mcfg.motion_file)
         if not os.path.isabs(path) and not os.path.exists(path):
             path = os.path.join(_lib.ROOT, path)
@@ -298,7 +359,15 @@ class MotionLib:
             from .motion_interp import Interpolation
 
             interpolation = Interpolation.from_config(mcfg.interpolation, skeleton.num_dof, robot=robot)
-        return cls(skeleton, clips, num_envs, device, max_len=max_len, interpolation=interpolation)
+        augmentation = None
+        if mcfg.get("augmentation", None) is not None:
+            from .motion_augment import Augmentation
+
+            augmentation = Augmentation.from_config(mcfg.augmentation)
+            if augmentation.active and mcfg.get("motion_lib_type", "origin") == "WJX":
+                raise _lib.PbhcError("robot.motion.augmentation with motion_lib_type WJX: a v1 library is ONE clip, the variants would make it "
+                                     f"{augmentation.num_variants}")
+        return cls(skeleton, clips, num_envs, device, max_len=max_len, interpolation=interpolation, augmentation=augmentation)
 
     # ---- slot -> clip assignment (load_motions, motion_lib_base.py:293-305) -----------------
     def load_motions(self, random_sample=True, start_idx=0, max_len=-1, target_heading=None, sampling_prob=None, crop_starts=None):
@@ -309,6 +378,9 @@ class MotionLib:
         if target_heading is not None:
             if self.max_len > 0:
                 raise NotImplementedError("load_motions(target_heading) with max_len crops")
+            if self.augmentation is not None and self.augmentation.mirror:
+                raise _lib.PbhcError("load_motions(target_heading) with robot.motion.augmentation.mirror: the clips are rebased before the "
+                                     "variants are made, so a mirrored variant would face the mirrored heading, not the target")
             self._build_unique_tables([rebase_heading(c, target_heading) for c in self._clips], into=self.frames)
         if max_len != -1 and max_len != self.max_len and (self.max_len != -1 or any(int(f) >= max_len for f in self.num_frames.tolist())):
             raise _lib.PbhcError(f"load_motions(max_len={max_len}): the library was built with max_len={self.max_len} (pass robot.motion.motion_max_len at construction)")
@@ -385,6 +457,15 @@ class MotionLib:
                                               None if reset_buf is None else _lib.ptr(reset_buf), None, self.num_envs, M, K, int(seed), counter_ptr,
                                               int(salt) & 0xFFFFFFFF, _lib.ptr(start_time), _lib.current_stream() if stream is None else stream),
                    "pbhc_start_draw")
+
+    def built_clip(self, clip_id):
+        """clip `clip_id` of the library as a host clip dict: the source clip itself without `augmentation`, else that variant (with the
+        lead-in / lead-out frames), fetched from the device once"""
+        if self.augmentation is None:
+            return self._clips[int(clip_id)]
+        if self._built_clips is None:
+            self._built_clips = self.extended_clips()
+        return self._built_clips[int(clip_id)]
 
     def get_motion_length(self, slot_ids=None):
         if slot_ids is None:

@@ -6,6 +6,8 @@ joint count and any number of clips, on the GPU: `pbhc_motion_extend_batch`).  T
         [--start-frames 30 --end-frames 30 --clip-start 0 --clip-end -1 --knee-modify --contact 0.5 --default-pose pose.npy]
 
 The config supplies the skeleton, the default joint angles and — if it has the key — robot.motion.interpolation; options override the key.
+If the config has robot.motion.augmentation, every variant is written: the source under its own name, the others as <name>__x<speed> and
+<name>__mirror (both for a mirrored, time-scaled one), each with the lead-in / lead-out frames.
 Output: an .npz through `save_motion_npz`, and next to it a joblib .pkl in the reference's layout (root_trans_offset, pose_aa, dof,
 root_rot, smpl_joints, fps, contact_mask) when `joblib` can be imported.
 """
@@ -17,6 +19,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pbhc_amd import _lib  # noqa: E402
+from pbhc_amd.motion_augment import Augmentation  # noqa: E402
 from pbhc_amd.motion_interp import Interpolation  # noqa: E402
 from pbhc_amd.motion_lib import MotionLib, load_motion_file, save_motion_npz  # noqa: E402
 from pbhc_amd.skeleton import Skeleton  # noqa: E402
@@ -64,8 +67,10 @@ def main(argv=None):
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(_lib.ROOT, path)
     named = load_motion_file(path)
-    ml = MotionLib(skel, [c for _, c in named], 1, args.device, interpolation=Interpolation.from_config(icfg, skel.num_dof, robot=rc))
-    clips = [(name, c) for (name, _), c in zip(named, ml.extended_clips())]
+    ml = MotionLib(skel, [c for _, c in named], 1, args.device, interpolation=Interpolation.from_config(icfg, skel.num_dof, robot=rc),
+                   augmentation=Augmentation.from_config(rc.motion.get("augmentation", None)))
+    variant_name = lambda src, mirrored, speed: named[src][0] + (f"__x{speed:g}" if speed != 1.0 else "") + ("__mirror" if mirrored else "")
+    clips = [(variant_name(*info), c) for info, c in zip(ml.variant_info, ml.extended_clips())]
     save_motion_npz(args.out, clips)
     print(f"wrote {args.out}: {len(clips)} clip(s), frames {[int(c['pose_aa'].shape[0]) for _, c in clips]}")
     try:
