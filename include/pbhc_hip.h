@@ -822,6 +822,45 @@ typedef struct PbhcMlpInput {
 } PbhcMlpInput;
 int pbhc_mlp_fwd_cat(const PbhcMlpInput* in, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, float* y, int ldy,
                      int M, const PbhcMlpSample* sample, void* stream);
+/* Riders: the small per-step kernels of the rollout as EXTRA WORKGROUPS of the policy launch, so that the dependent chain
+ * env step -> policy forward -> env step stays on one queue with no branch beside it (the policy forward of step t reads nothing the previous
+ * step's reduction writes: its sampler is keyed by the counter snapshot, see PbhcMlpSample).  Behind the ceil(M / 16) workgroups of the stack:
+ *   has_finalize: ONE workgroup runs the single-process form of pbhc_env_step_finish's reduction (the same additions in the same order, the
+ *                 same scalar chains: the globals come out equal bit for bit) — fill this half with pbhc_env_finalize_rider, which launches
+ *                 nothing; the launch that carries it must follow the pbhc_env_step_launch it belongs to on its stream, and precede the next;
+ *   has_post:     ceil(N / 16) workgroups run pbhc_rollout_post2's kernel body on 16 envs each (same arguments, same per-env arithmetic;
+ *                 ep_stats is summed per 16 envs before its atomics instead of per 8).
+ * pbhc_mlp_fwd_sample_riders / pbhc_mlp_fwd_cat_riders: pbhc_mlp_fwd_sample / pbhc_mlp_fwd_cat with `riders` (NULL, or both flags 0: exactly
+ * those calls). */
+typedef struct PbhcRider {
+  const PbhcEnvConfig* cfg;          /* finalize half: the env's device-side config, globals and partial-sum rows */
+  double* globals;
+  const float* partials;
+  int32_t* frame_cursor;
+  int32_t num_partial_rows;          /* 2 * workgroups of the env step */
+  int32_t num_frames;
+  const float* rew;                  /* post half: the arguments of pbhc_rollout_post2 */
+  const float* values;               /* may be NULL */
+  const int64_t* reset_buf;
+  const uint8_t* time_outs;
+  float* rewards_out;
+  uint8_t* dones_out;
+  float* cur_reward_sum;
+  float* cur_episode_length;
+  double* ep_stats;
+  uint8_t* time_outs_out;            /* may be NULL */
+  int32_t N, R;
+  float gamma;
+  int32_t has_finalize, has_post;
+  int32_t pad_;
+} PbhcRider;
+int pbhc_env_finalize_rider(PbhcEnv* env, const PbhcStepIO* io, PbhcRider* rider);
+/* test aid: the stand-alone reduction kernel on a rider's finalize half (any partial rows / globals / cursor), to hold the rider workgroup to it */
+int pbhc_debug_env_finalize(const PbhcRider* rider, void* stream);
+int pbhc_mlp_fwd_sample_riders(const float* x, int ldx, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, int M,
+                               const PbhcMlpSample* sample, const PbhcRider* riders, void* stream);
+int pbhc_mlp_fwd_cat_riders(const PbhcMlpInput* in, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, float* y,
+                            int ldy, int M, const PbhcMlpSample* sample, const PbhcRider* riders, void* stream);
 /* pbhc_conv_encoder_fwd: the general-tracking `ConvEncoder` (agents/modules/encoder_modules.py:22-107 of the reference: Linear(d -> H) + ReLU
  * per time step, Conv1d(H -> O1, k1, s1) + act, Conv1d(O1 -> O2, k2, s2) + act, Linear(L2 * O2 -> E)) under no_grad in ONE launch, 16 rows per
  * workgroup through all four layers (the rollout: 4 096 rows per control step).  x [M, T * d] with row pitch ldx >= (T - 1) * d + ceil16(d)

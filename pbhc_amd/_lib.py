@@ -85,6 +85,7 @@ PbhcStepIO = _S["PbhcStepIO"]
 PbhcRecordIO = _S["PbhcRecordIO"]
 PbhcMlpSample = _S["PbhcMlpSample"]
 PbhcMlpInput = _S["PbhcMlpInput"]
+PbhcRider = _S["PbhcRider"]
 PbhcConvEncoder = _S["PbhcConvEncoder"]
 PbhcPpoReduce = _S["PbhcPpoReduce"]
 PbhcMotionExtend = _S["PbhcMotionExtend"]
@@ -101,7 +102,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
            "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
            "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
-           "pbhc_motion_extend_batch", "pbhc_motion_augment_batch"]
+           "pbhc_motion_extend_batch", "pbhc_motion_augment_batch",
+           "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize"]
 
 
 class PbhcError(RuntimeError):
@@ -178,6 +180,11 @@ def _load():
     lib.pbhc_conv_encoder_lds_bytes.restype = C.c_size_t
     lib.pbhc_conv_encoder_fwd.argtypes = [vp, i, C.POINTER(PbhcConvEncoder), vp, i, i, vp]
     lib.pbhc_mlp_fwd_cat.argtypes = [C.POINTER(PbhcMlpInput), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, vp, i, i, C.POINTER(PbhcMlpSample), vp]
+    lib.pbhc_env_finalize_rider.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcRider)]
+    lib.pbhc_debug_env_finalize.argtypes = [C.POINTER(PbhcRider), vp]
+    lib.pbhc_mlp_fwd_sample_riders.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, i, C.POINTER(PbhcMlpSample), C.POINTER(PbhcRider), vp]
+    lib.pbhc_mlp_fwd_cat_riders.argtypes = [C.POINTER(PbhcMlpInput), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, vp, i, i, C.POINTER(PbhcMlpSample),
+                                            C.POINTER(PbhcRider), vp]
     lib.pbhc_mlp_fwd_lds_bytes.argtypes = [C.POINTER(i), i]
     lib.pbhc_mlp_fwd_lds_bytes.restype = C.c_size_t
     lib.pbhc_mlp_pack.argtypes = [vp, i, i, vp, vp]

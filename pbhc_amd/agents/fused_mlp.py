@@ -439,10 +439,11 @@ def forward_inference(seq, x):
     return torch.addmm(lin[-1].bias, h, lin[-1].weight.t())
 
 
-def forward_sample(seq, x, std, seed, counter, counter_offset, actions, action_mean, action_sigma, logp):
+def forward_sample(seq, x, std, seed, counter, counter_offset, actions, action_mean, action_sigma, logp, riders=None):
     """The policy stack AND the rollout's sampling (mh_ppo.py:286-296: act(), log-prob, the buffer writes) as one launch
     (`pbhc_mlp_fwd_sample`); needs pack_stack(seq).  Returns False — nothing launched — where that does not apply (the caller then runs
-    forward_inference + pbhc_policy_sample)."""
+    forward_inference + pbhc_policy_sample).  riders: a `PbhcRider` whose work runs as extra workgroups of the launch
+    (`pbhc_mlp_fwd_sample_riders`: the previous control step's reduction and book-keeping, agents/rollout.py)."""
     c = getattr(seq, "_pbhc_stack", None)
     lin = [m for m in seq if isinstance(m, nn.Linear)]
     B = x.shape[0]
@@ -453,16 +454,21 @@ def forward_sample(seq, x, std, seed, counter, counter_offset, actions, action_m
     smp.std, smp.counter, smp.seed, smp.counter_offset = std.data_ptr(), counter, int(seed), int(counter_offset)
     smp.actions, smp.action_mean, smp.action_sigma, smp.logp = actions.data_ptr(), action_mean.data_ptr(), action_sigma.data_ptr(), logp.data_ptr()
     act = _ACT_ID[type(seq[1])] if len(lin) > 1 else 0
+    if riders is not None:
+        _lib.check(_lib.lib().pbhc_mlp_fwd_sample_riders(x.data_ptr(), x.stride(0), c["w"], c["b"], c["dims"], len(lin), act, B, C.byref(smp), C.byref(riders),
+                                                         _lib.current_stream()), "pbhc_mlp_fwd_sample_riders")
+        return True
     _lib.check(_lib.lib().pbhc_mlp_fwd_sample(x.data_ptr(), x.stride(0), c["w"], c["b"], c["dims"], len(lin), act, B, C.byref(smp), _lib.current_stream()),
                "pbhc_mlp_fwd_sample")
     return True
 
 
-def forward_cat_inference(seq, xs, sample=None):
+def forward_cat_inference(seq, xs, sample=None, riders=None):
     """No-grad forward of a packed stack on `torch.cat(xs, -1)` WITHOUT the concatenation (`pbhc_mlp_fwd_cat`: the stack kernel stages its 16
     input rows from up to three column segments — observation slab | encoder outputs), optionally with the rollout's sampling in the last
     layer's epilogue (`sample`: dict(std, seed, counter, counter_offset, actions, action_mean, action_sigma, logp), as forward_sample).
-    Returns the output [B, out] (None with `sample`: the mean lands in action_mean), or False — nothing launched — where it does not apply."""
+    Returns the output [B, out] (None with `sample`: the mean lands in action_mean), or False — nothing launched — where it does not apply.
+    riders: as forward_sample's (`pbhc_mlp_fwd_cat_riders`)."""
     c = getattr(seq, "_pbhc_stack", None)
     lin = [m for m in seq if isinstance(m, nn.Linear)]
     B = xs[0].shape[0]
@@ -485,6 +491,11 @@ def forward_cat_inference(seq, xs, sample=None):
         smp_ref = C.byref(smp)
     else:
         out = torch.empty(B, lin[-1].out_features, device=xs[0].device)
+    if riders is not None:
+        _lib.check(_lib.lib().pbhc_mlp_fwd_cat_riders(C.byref(inp), c["w"], c["b"], c["dims"], len(lin), act, None if out is None else out.data_ptr(),
+                                                      0 if out is None else out.stride(0), B, smp_ref, C.byref(riders), _lib.current_stream()),
+                   "pbhc_mlp_fwd_cat_riders")
+        return out if sample is None else None
     _lib.check(_lib.lib().pbhc_mlp_fwd_cat(C.byref(inp), c["w"], c["b"], c["dims"], len(lin), act, None if out is None else out.data_ptr(),
                                            0 if out is None else out.stride(0), B, smp_ref, _lib.current_stream()), "pbhc_mlp_fwd_cat")
     return out if sample is None else None

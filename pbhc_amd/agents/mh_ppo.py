@@ -209,7 +209,7 @@ class MHPPO(OnDeviceAgent):
             if not d.fuse_sample:
                 return a_mod(st.actor_obs[t]), None
             if not fused_mlp.forward_sample(a_mod.module, st.actor_obs[t], std, self._sample_seed, self._ctr0.data_ptr(), t, st.actions[t], st.action_mean[t],
-                                            st.action_sigma[t], st.actions_log_prob[t]):
+                                            st.action_sigma[t], st.actions_log_prob[t], riders=d.rider):
                 raise _lib.PbhcError("pbhc_mlp_fwd_sample does not apply to this policy (PBHC_FUSED_SAMPLE=0)")
             return st.action_mean[t], None
 

@@ -338,7 +338,8 @@ class PPO(OnDeviceAgent):
                 if d.fuse_sample:
                     smp = dict(std=sigma, seed=self._sample_seed, counter=self._ctr0.data_ptr(), counter_offset=t, actions=st.actions[t],
                                action_mean=st.action_mean[t], action_sigma=st.action_sigma[t], logp=st.actions_log_prob[t])
-                    if fused_mlp.forward_cat_inference(a_seq, xs, sample=smp) is False:
+                    # (the riders go with the launch that samples; the encoder and privileged-stack launches above carry none)
+                    if fused_mlp.forward_cat_inference(a_seq, xs, sample=smp, riders=d.rider) is False:
                         raise _lib.PbhcError("pbhc_mlp_fwd_cat does not apply to this policy (PBHC_FUSED_SAMPLE=0)")
                     return st.action_mean[t], None
                 mu = fused_mlp.forward_cat_inference(a_seq, xs) if any(q is a_seq for q in d.packed) else False

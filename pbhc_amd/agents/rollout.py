@@ -3,8 +3,16 @@ next observations into the next rollout slab, done / episode-statistics kernel),
 then GAE.  No host synchronisation.
 
 Per control step the dependent chain is env step -> policy forward (+ sampling in its last epilogue) -> env step.  Everything else of a step
-runs on a branch stream NEXT to that chain: the env step's one-workgroup reduction (sigma EMA, curricula, step counter) and the done /
-episode-statistics kernel; the chain waits for the branch once per step, right before the next env step.  The critic's values are consumed only
+— the env step's one-workgroup reduction (sigma EMA, curricula, step counter) and the done / episode-statistics kernel — is 13 us of work that
+only the NEXT env step needs.  Two forms:
+  rider form (default; `rider_form`): both ride in the policy launch of the next step as extra workgroups behind the stack's (PbhcRider,
+    pbhc_mlp_fwd_*_riders: the policy forward reads nothing they write — its sampler is keyed by a snapshot of the step counter), so the chain
+    is step -> policy(+ riders) -> step on ONE queue with no branch, no event and no cross-queue edge; the last step's pair follows the loop
+    as plain launches;
+  branch form (PBHC_ROLLOUT_RIDERS=0, and whenever something else lives behind the reduction: the per-step statistics exchange, the clip /
+    start collectors, a per-step critic, the separate sampling kernel): they run on a branch stream NEXT to the chain, which waits for the
+    branch once per step, right before the next env step — two cross-queue edges per control step.
+`agent._rollout_form` says which one ran.  The critic's values are consumed only
 by the time-out bootstrap and by GAE, both after the rollout: evaluated ONCE over all T + 1 slabs (whole-chip GEMM tiles) they cost 1.5 ms,
 against 24 x 85 us for per-step forwards that share the chip with the step -> actor chain.  The weights are constant over the rollout: the MLP
 stacks an agent names run as ONE launch per step from a packed copy (pbhc_mlp_fwd), with the sampling kernel in that launch's last epilogue,
@@ -17,7 +25,8 @@ checked for the whole window before (`rollout_graph_safe`); a rollout that conta
 run inside a capture) or one that is being timed launch by launch runs the loop step by step with one captured forward per step.
 
 Switches (agents/base.py): PBHC_ROLLOUT_GRAPH=0 the eager loop, PBHC_ROLLOUT_SPLIT=0 one stream, PBHC_CRITIC_BATCHED=0 the critic inside
-every control step, PBHC_FUSED_SAMPLE=0 the separate sampling kernel, PBHC_FWD_GRAPHS=0 eager per-step forwards.
+every control step, PBHC_FUSED_SAMPLE=0 the separate sampling kernel, PBHC_FWD_GRAPHS=0 eager per-step forwards, PBHC_ROLLOUT_RIDERS=0 the
+branch form.
 """
 from __future__ import annotations
 
@@ -93,7 +102,8 @@ class RolloutSpec:
     this form of the forward cannot).  key_extra: what else the captured forward depends on.  critic_step(t) -> values of slab t, run on the
     branch stream ahead of forward(t) (None: no per-step critic outside forward).  after_step(t, nxt): called after env.step of step t.
     early_fwd_graphs: build the per-step forward graphs before deciding on the rollout graph (MHPPO) rather than when the eager loop runs
-    (ppo_mimic)."""
+    (ppo_mimic).  rider: filled in by the driver around forward(t) in the rider form — the `PbhcRider` the launch of forward(t) that SAMPLES
+    has to carry (fused_mlp.forward_sample / forward_cat_inference `riders=`), None otherwise."""
 
     keys: list
     batched: bool
@@ -112,6 +122,7 @@ class RolloutSpec:
     early_fwd_graphs: bool = False
     packed: list = dataclasses.field(default_factory=list, init=False)      # the stacks that did pack   } filled in by collect()
     fuse_sample: bool = dataclasses.field(default=False, init=False)        # sampling in the forward   }
+    rider: typing.Any = dataclasses.field(default=None, init=False)         # riders of forward(t)      }
 
 
 def split_streams(env):
@@ -122,6 +133,14 @@ def critic_batched(env):
     return split_streams(env) and switch_on("PBHC_CRITIC_BATCHED")
 
 
+def rider_form(env, d):
+    """May the reduction and the book-keeping of a control step ride in the next step's policy launch?  Only if that launch does not read the
+    live step counter (the fused sampler) and nothing else lives behind the reduction: no per-step statistics exchange between the ranks, no
+    clip / start collectors (they run behind the reduction on the finalize stream), no per-step critic on the branch."""
+    return (split_streams(env) and hasattr(env, "take_finalize_rider") and d.fuse_sample and env._totals is None and env._clip_window is None
+            and env._start_window is None and d.critic_step is None and switch_on("PBHC_ROLLOUT_RIDERS"))
+
+
 def collect(agent, d, obs_dict):
     """one rollout of `agent` as `d` (a RolloutSpec) describes it, from the observations `obs_dict`, through GAE -> the observations after it"""
     st, env, lib = agent.storage, agent.env, _lib.lib()
@@ -129,6 +148,7 @@ def collect(agent, d, obs_dict):
     keys, batched = d.keys, d.batched
     c = _lib.K["PBHC_G_STEP_COUNTER"]
     counter = env.globals[c:].data_ptr()
+    P = lambda x: x.data_ptr()
     with torch.inference_mode():
         for k in keys:
             getattr(st, k)[0].copy_(obs_dict[k])
@@ -147,18 +167,27 @@ def collect(agent, d, obs_dict):
                 env.wait_finalize()
                 agent._ctr0.copy_(env.globals[c:c + 1])
             fuse_sample = d.fuse_sample
+            riders = rider_form(env, d)
+            agent._rollout_form = "riders" if riders else "branch"
             fwd_key = tuple(d.key_extra) + (bool(d.packed), fuse_sample)
-            fwd = forward_graphs(agent, d.forward, fwd_key) if d.early_fwd_graphs else None
-            critic_fwd = None if d.critic_step is None else forward_graphs(agent, d.critic_step, "critic")
+            if riders:
+                # a captured forward holds the riders' descriptors: the env's addresses and replay window (graph_key, read once the env has
+                # picked up a new window: finalize_rider) belong to its key
+                env.finalize_rider()
+                fwd_key += ("riders", *env.graph_key())
+                stale = [k for k in agent.__dict__.get("_fwd_graph_cache", {}) if isinstance(k, tuple) and "riders" in k and k != fwd_key]
+                for k in stale:
+                    del agent._fwd_graph_cache[k]
             cur, br = torch.cuda.current_stream(), agent._branch_stream
-            use_br = split or critic_fwd is not None
-            if split:
+            use_br = (split and not riders) or d.critic_step is not None
+            if riders:
+                env.set_finalize_deferred(True)
+            elif split:
                 env.set_finalize_stream(br)
             post_done = [agent.__dict__.setdefault("_post_done", torch.cuda.Event())]      # (a cell: a capture swaps the event it used for a fresh one)
             # per-step device addresses, formed once (the host's share of a control step is what bounds the loop once the critic is out of it)
             sc = agent.__dict__.get("_step_ptrs")
             if sc is None or sc[0] is not st or sc[2] != batched:
-                P = lambda x: x.data_ptr()
                 sc = (st, [dict(sample=d.sample_ptrs(t), post=(P(st.rewards[t]), P(st.dones[t])), values=P(st.values[t]),
                                 tout=P(agent._time_outs[t]) if batched else None, act={"actions": st.actions[t]},
                                 obs_out={k: getattr(st, k)[t + 1] for k in keys} if t + 1 < T else agent._last_obs) for t in range(T)], batched)
@@ -167,7 +196,58 @@ def collect(agent, d, obs_dict):
             sigma_p, sum_p, len_p, stat_p = d.sigma.data_ptr(), agent.cur_reward_sum.data_ptr(), agent.cur_episode_length.data_ptr(), agent._ep_stats.data_ptr()
             gamma, seed, br_h = float(agent.gamma), agent._sample_seed, br.cuda_stream
 
+            def rider_of(t, fin=True):
+                """what the sampling launch of forward(t) carries: the reduction (fin) and the book-keeping of step t - 1.  Every address in it
+                is fixed (env-owned step outputs, rollout slabs): a captured forward may hold it."""
+                if t == 0:
+                    return None
+                r, sp = (env.finalize_rider() if fin else _lib.PbhcRider()), steps[t - 1]
+                r.rew, r.values, r.reset_buf, r.time_outs = P(env.rew_buf), None if batched else sp["values"], P(env.reset_buf), P(env.time_out_buf)
+                r.rewards_out, r.dones_out = sp["post"]
+                r.cur_reward_sum, r.cur_episode_length, r.ep_stats, r.time_outs_out = sum_p, len_p, stat_p, sp["tout"]
+                r.N, r.R, r.gamma, r.has_post = N, R, gamma, 1
+                return r
+
+            def forward_riders(t, fin=True):
+                d.rider = rider_of(t, fin)
+                try:
+                    return d.forward(t)
+                finally:
+                    d.rider = None
+
+            def run_loop_riders(cur, forward):
+                """step -> policy(+ riders) -> step on ONE stream: forward(t) carries the reduction and the book-keeping of step t - 1"""
+                stream = cur.cuda_stream
+                for t in range(T):
+                    sp = steps[t]
+                    if t == 0:
+                        forward(t)
+                    elif env.finalize_owed:
+                        env.take_finalize_rider()             # (host-side mark: forward(t), captured or not, holds the descriptor)
+                        forward(t)
+                    else:
+                        # something inside the last env.step (a motion resample resets every env) read the globals and flushed the reduction
+                        # as a plain launch already: the book-keeping rider alone, outside any captured forward
+                        forward_riders(t, fin=False)
+                    env.set_obs_outputs(sp["obs_out"])
+                    # terminate_when_dof_far: env.step launches the pre-pass of step t right here, AFTER forward(t) — behind the reduction of
+                    # step t - 1 (a rider of forward(t)) that clears the flag the pre-pass sets, as in the branch form
+                    nxt, rewards, dones, infos = env.step(sp["act"])
+                    if d.after_step is not None:
+                        d.after_step(t, nxt)
+                # the last step's pair: plain launches on the same stream
+                env.flush_finalize()
+                sp = steps[T - 1]
+                _lib.check(lib.pbhc_rollout_post2(P(env.rew_buf), None if batched else sp["values"], P(env.reset_buf), P(env.time_out_buf), N, R, gamma,
+                                                  *sp["post"], sum_p, len_p, stat_p, sp["tout"], stream), "pbhc_rollout_post2")
+
+            fwd_fn = forward_riders if riders else d.forward
+            fwd = forward_graphs(agent, fwd_fn, fwd_key) if d.early_fwd_graphs else None
+            critic_fwd = None if d.critic_step is None else forward_graphs(agent, d.critic_step, "critic")
+
             def run_loop(cur, forward):
+                if riders:
+                    return run_loop_riders(cur, forward)
                 stream = cur.cuda_stream
                 if use_br:
                     br.wait_stream(cur)
@@ -214,15 +294,17 @@ def collect(agent, d, obs_dict):
                 key = (id(st), *env.graph_key(), T) + fwd_key
                 gc = agent.__dict__.get("_rollout_graph")
                 if gc is None or gc[0] != key:
-                    gc = _capture_rollout(agent, key, lambda: run_loop(torch.cuda.current_stream(), d.forward), post_done)
+                    gc = _capture_rollout(agent, key, lambda: run_loop(torch.cuda.current_stream(), fwd_fn), post_done)
                 if gc is not None:
                     gc[1].replay()
                     env.after_graph_steps(T)
                     ran = True
             agent._rollout_used_graph = ran
             if not ran:
-                run_loop(cur, fwd or forward_graphs(agent, d.forward, fwd_key))
-            if split:
+                run_loop(cur, fwd or forward_graphs(agent, fwd_fn, fwd_key))
+            if riders:
+                env.set_finalize_deferred(False)
+            elif split:
                 env.set_finalize_stream(None)
         finally:
             # (also when a step raises: a stack left marked valid would serve stale weights to every later no-grad forward)

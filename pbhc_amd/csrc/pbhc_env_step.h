@@ -7,7 +7,7 @@
 
 #define PBHC_G 32     // lanes per env
 #define PBHC_EPB 4    // envs per workgroup
-#define PBHC_NP 64   // partial sums per workgroup
+#include "pbhc_partials.h"      // PBHC_NP, the P_* columns of a workgroup's partial-sum rows
 
 #ifdef PBHC_STATIC_CFG
 #include PBHC_STATIC_CFG
@@ -26,19 +26,6 @@ __device__ unsigned long long g_wg_times[2 * 4096];          // [workgroup][entr
 #define STAMPB(i) do { } while (0)
 #define WG_STAMP(k) do { } while (0)
 #endif
-
-// ------------------------------------------------------------------------------------------------
-// partial-sum columns written per workgroup by k_env_step, reduced by k_env_finalize
-enum {
-  P_ERR = 0,            // [PBHC_NUM_SIGMA] tracking errors (adaptive sigma)
-  P_UPPER_NORM = PBHC_NUM_SIGMA, P_LOWER_NORM, P_VR_NORM, P_JOINT_NORM, P_CLIP_CNT, P_RESET_CNT, P_TERM_GRAVITY, P_TERM_FAR,
-  P_TERM_TIMEOUT, P_TERM_END, P_RESET_EPLEN, P_ETR_SUM, P_ETR_SQ, P_REW_SUM,
-  P_KEY_NORM, P_LUP_NORM, P_LLO_NORM, P_LVR_NORM, P_LKEY_NORM, P_TERM_REFZ, P_TERM_REFORI, P_TERM_BODYZ,      // general tracking
-  P_TERM_CONTACT, P_TERM_LOWH, P_TERM_POSLIM, P_TERM_VELLIM, P_TERM_TAULIM,
-  P_NUM
-};
-static_assert(P_NUM <= PBHC_NP, "partials");
-static_assert(PBHC_NP == PBHC_NUM_TOTALS, "totals");
 
 // reduction slots per env (LDS)
 enum {

@@ -25,6 +25,8 @@
 
 #include "../../include/pbhc_hip.h"
 #include "pbhc_math.h"
+#include "pbhc_env_finalize.h"      // env_finalize_body  } the riders of k_mlp_fwd: the rollout's per-step small kernels as extra workgroups
+#include "pbhc_rollout_post.h"      // rollout_post_body  } of the policy launch
 
 extern thread_local char g_pbhc_err[512];
 #define MLP_FAIL(code, ...) do { snprintf(g_pbhc_err, sizeof(g_pbhc_err), __VA_ARGS__); return (code); } while (0)
@@ -59,6 +61,10 @@ struct MlpArgs {
   unsigned long long seed;
   int counter_offset;
   float *actions, *action_mean, *action_sigma, *logp;
+  // riders (pbhc_mlp_fwd_*_riders): workgroups [nmain, gridDim.x) do not run the stack but the env's reduction (one workgroup, if
+  // rd.has_finalize) and the rollout's book-keeping (ceil(rd.N / MLP_ROWS) workgroups, if rd.has_post).  nmain == gridDim.x: none
+  int nmain;
+  PbhcRider rd;
 };
 
 __host__ __device__ __forceinline__ int mlp_pitch(int k) { return ((k + 15) & ~15) + 4; }   // zero-padded to a whole k-step; 4 mod 32 words where it matters
@@ -168,8 +174,31 @@ __device__ __forceinline__ void mlp_run(const MlpArgs& a, int l, int first, int 
   }
 }
 
+// A rider workgroup, `idx` counted from the first one.  They share nothing with the stack's workgroups but the launch: of the dynamic LDS they
+// use PBHC_FIN_LDS_DOUBLES doubles (the reduction) or 3 * MLP_ROWS doubles (book-keeping), which the host makes sure the launch has.
+__device__ __forceinline__ void mlp_rider(const PbhcRider& rd, int idx) {
+  extern __shared__ double mlp_smem_f64[];
+  if (rd.has_finalize) {
+    if (idx == 0) {
+      // one workgroup of dependent loads and double divisions next to eight waves of the stack on the same CU: it goes first at issue
+      __builtin_amdgcn_s_setprio(3);
+      env_finalize_body<MLP_T>(mlp_smem_f64, mlp_smem_f64 + PBHC_FIN_CHUNKS * 64, rd.cfg, rd.globals, rd.partials, rd.num_partial_rows, rd.frame_cursor,
+                               rd.num_frames, nullptr, nullptr, 0.0);
+      return;
+    }
+    --idx;
+  }
+  // 512 threads = MLP_ROWS envs x 32 lanes
+  rollout_post_body<MLP_ROWS>(mlp_smem_f64, idx, rd.rew, rd.values, rd.reset_buf, rd.time_outs, rd.N, rd.R, rd.gamma, rd.rewards_out, rd.dones_out,
+                              rd.cur_reward_sum, rd.cur_episode_length, rd.ep_stats, rd.time_outs_out);
+}
+
 __global__ __launch_bounds__(MLP_T) void k_mlp_fwd(MlpArgs a) {
   extern __shared__ float mlp_smem[];
+  if ((int)blockIdx.x >= a.nmain) {                        // (uniform per workgroup; the stack's workgroups pay this one scalar compare)
+    mlp_rider(a.rd, (int)blockIdx.x - a.nmain);
+    return;
+  }
   float* const img0 = mlp_smem;                            // (offsets into the one shared array, so that every access stays a DS instruction)
   const int off1 = MLP_ROWS * a.pitch0;
   const int row0 = blockIdx.x * MLP_ROWS;
@@ -394,8 +423,10 @@ size_t pbhc_mlp_fwd_lds_bytes(const int* dims, int num_layers) {
   return (size_t)MLP_ROWS * (size_t)(p0 + p1) * sizeof(float);
 }
 
+static_assert(MLP_T == 32 * MLP_ROWS, "the book-keeping riders map 32 lanes to each of a workgroup's MLP_ROWS envs");
+
 static int mlp_launch(const PbhcMlpInput* in, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, float* y, int ldy,
-                      int M, const PbhcMlpSample* smp, void* stream) {
+                      int M, const PbhcMlpSample* smp, void* stream, const PbhcRider* rd = nullptr) {
   MLP_ARG(in && weights && biases && dims && (y || smp) && M >= 1 && num_layers >= 1 && num_layers <= PBHC_MLP_MAX_LAYERS && act >= 0 && act <= 3);
   MLP_ARG(in->nseg >= 1 && in->nseg <= PBHC_MLP_MAX_SEGS && (!y || ldy >= dims[num_layers]));
   MlpArgs a;
@@ -437,8 +468,28 @@ static int mlp_launch(const PbhcMlpInput* in, const float* const* weights, const
     if (l & 1) a.pitch1 = p > a.pitch1 ? p : a.pitch1; else a.pitch0 = p > a.pitch0 ? p : a.pitch0;
   }
   if (a.pitch1 == 0) a.pitch1 = 4;
-  const size_t lds = (size_t)MLP_ROWS * (size_t)(a.pitch0 + a.pitch1) * sizeof(float);
+  size_t lds = (size_t)MLP_ROWS * (size_t)(a.pitch0 + a.pitch1) * sizeof(float);
   MLP_ARG(lds <= 160 * 1024);
+  // riders: extra workgroups behind the stack's
+  a.nmain = (M + MLP_ROWS - 1) / MLP_ROWS;
+  int nriders = 0;
+  a.rd = PbhcRider{};
+  if (rd && rd->has_finalize) {
+    MLP_ARG(rd->cfg && rd->globals && rd->partials && rd->frame_cursor && rd->num_partial_rows >= 1 && rd->num_frames >= 1);
+    a.rd.cfg = rd->cfg; a.rd.globals = rd->globals; a.rd.partials = rd->partials; a.rd.frame_cursor = rd->frame_cursor;
+    a.rd.num_partial_rows = rd->num_partial_rows; a.rd.num_frames = rd->num_frames; a.rd.has_finalize = 1;
+    nriders += 1;
+    if (lds < PBHC_FIN_LDS_DOUBLES * sizeof(double)) lds = PBHC_FIN_LDS_DOUBLES * sizeof(double);
+  }
+  if (rd && rd->has_post) {
+    MLP_ARG(rd->rew && rd->reset_buf && rd->time_outs && rd->rewards_out && rd->dones_out && rd->cur_reward_sum && rd->cur_episode_length && rd->ep_stats &&
+            rd->N >= 1 && rd->R >= 1 && rd->R <= 32);
+    a.rd.rew = rd->rew; a.rd.values = rd->values; a.rd.reset_buf = rd->reset_buf; a.rd.time_outs = rd->time_outs; a.rd.rewards_out = rd->rewards_out;
+    a.rd.dones_out = rd->dones_out; a.rd.cur_reward_sum = rd->cur_reward_sum; a.rd.cur_episode_length = rd->cur_episode_length; a.rd.ep_stats = rd->ep_stats;
+    a.rd.time_outs_out = rd->time_outs_out; a.rd.N = rd->N; a.rd.R = rd->R; a.rd.gamma = rd->gamma; a.rd.has_post = 1;
+    nriders += (rd->N + MLP_ROWS - 1) / MLP_ROWS;
+    if (lds < 3 * MLP_ROWS * sizeof(double)) lds = 3 * MLP_ROWS * sizeof(double);
+  }
   if (lds > 64 * 1024) {
     // the attribute is per DEVICE: raised once on each device that runs a wide stack (the first rollout runs outside any capture)
     static std::atomic<unsigned long long> raised{0};       // bit d: device d has it
@@ -450,7 +501,7 @@ static int mlp_launch(const PbhcMlpInput* in, const float* const* weights, const
       raised.fetch_or(bit, std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL(k_mlp_fwd, dim3((M + MLP_ROWS - 1) / MLP_ROWS), dim3(MLP_T), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_mlp_fwd, dim3(a.nmain + nriders), dim3(MLP_T), lds, (hipStream_t)stream, a);
   MLP_HIP(hipGetLastError());
   return PBHC_OK;
 }
@@ -526,6 +577,18 @@ int pbhc_conv_encoder_fwd(const float* x, int ldx, const PbhcConvEncoder* e, flo
 int pbhc_mlp_fwd_cat(const PbhcMlpInput* in, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, float* y, int ldy,
                      int M, const PbhcMlpSample* sample, void* stream) {
   return mlp_launch(in, weights, biases, dims, num_layers, act, y, ldy, M, sample, stream);
+}
+
+int pbhc_mlp_fwd_sample_riders(const float* x, int ldx, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, int M,
+                               const PbhcMlpSample* sample, const PbhcRider* riders, void* stream) {
+  MLP_ARG(sample && dims);
+  const PbhcMlpInput in = one_segment(x, ldx, dims);
+  return mlp_launch(&in, weights, biases, dims, num_layers, act, nullptr, 0, M, sample, stream, riders);
+}
+
+int pbhc_mlp_fwd_cat_riders(const PbhcMlpInput* in, const float* const* weights, const float* const* biases, const int* dims, int num_layers, int act, float* y,
+                            int ldy, int M, const PbhcMlpSample* sample, const PbhcRider* riders, void* stream) {
+  return mlp_launch(in, weights, biases, dims, num_layers, act, y, ldy, M, sample, stream, riders);
 }
 
 }  // extern "C"

@@ -28,11 +28,7 @@ extern thread_local char g_pbhc_err[512];
 #define LOSS_ROWS 8          // rows (samples) per 256-thread workgroup, 32 lanes per row
 #define LOSS_NP 8            // scalar partial sums per workgroup: surrogate, value, kl, (pad)
 
-__device__ __forceinline__ float gsum32(float v) {
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 32);
-  return v;
-}
+#include "pbhc_rollout_post.h"      // gsum32, rollout_post_body (shared with the rider workgroups of the rollout's policy launch, pbhc_mlp.hip)
 
 // One row per 32-lane group: lane a < A <-> action dim a, lane r < R <-> value head r.
 // Every 32-lane group keeps its own running sums over the tiles it visits (no barrier inside the tile loop: the loads of consecutive tiles
@@ -536,34 +532,8 @@ __global__ __launch_bounds__(256) void k_rollout_post(const float* __restrict__ 
                                                       const uint8_t* __restrict__ time_outs, int N, int R, float gamma, float* __restrict__ rewards_out,
                                                       uint8_t* __restrict__ dones_out, float* __restrict__ cur_rew, float* __restrict__ cur_len,
                                                       double* __restrict__ ep_stats, uint8_t* __restrict__ time_outs_out) {
-  __shared__ double sh[3][8];
-  const int lane = threadIdx.x & 31, lr = threadIdx.x >> 5, row = blockIdx.x * 8 + lr;
-  const bool valid = row < N;
-  float r = 0.0f;
-  const float to = valid ? (time_outs[row] ? 1.0f : 0.0f) : 0.0f;
-  if (valid && lane < R) {
-    const size_t i = (size_t)row * R + lane;
-    r = rew[i];
-    rewards_out[i] = values ? r + gamma * values[i] * to : r;      // values == NULL: the caller adds the time-out bootstrap later (batched critic)
-  }
-  const float rsum = gsum32(r);
-  double a = 0.0, b = 0.0, c = 0.0;
-  if (valid && lane == 0) {
-    const bool done = reset_buf[row] > 0;
-    dones_out[row] = done ? 1 : 0;
-    if (time_outs_out) time_outs_out[row] = time_outs[row];
-    const float cr = cur_rew[row] + rsum, cl = cur_len[row] + 1.0f;
-    if (done) { a = (double)cr; b = (double)cl; c = 1.0; }
-    cur_rew[row] = done ? 0.0f : cr;
-    cur_len[row] = done ? 0.0f : cl;
-  }
-  if (lane == 0) { sh[0][lr] = a; sh[1][lr] = b; sh[2][lr] = c; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double t = 0.0;
-    for (int k = 0; k < 8; ++k) t += sh[threadIdx.x][k];
-    if (t != 0.0) atomicAdd(&ep_stats[threadIdx.x], t);        // logging statistics only
-  }
+  __shared__ double sh[3 * 8];
+  rollout_post_body<8>(sh, blockIdx.x, rew, values, reset_buf, time_outs, N, R, gamma, rewards_out, dones_out, cur_rew, cur_len, ep_stats, time_outs_out);
 }
 
 // ---- backward of a stack's narrow OUTPUT layer in one pass --------------------------------------------------------------------------------

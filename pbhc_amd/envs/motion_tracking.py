@@ -134,6 +134,7 @@ def get_class(path):
 
 class LeggedRobotMotionTracking:
     TRACKING_MODE = 0          # selects the kernel instantiation (see PbhcEnvConfig.tracking_mode)
+    _fin_deferred = _fin_owed = False            # set_finalize_deferred(): per instance once it is used
 
     def __init__(self, config, device):
         """config = cfg.env.config (with .robot/.obs/.rewards/.domain_rand/.terrain/.simulator aliased
@@ -429,6 +430,7 @@ class LeggedRobotMotionTracking:
             yield
         finally:
             self.common_step_counter = counter0
+            self._fin_owed = False                   # (a recorded step owes nothing: what it left owed was recorded too, or the capture failed)
             if renew_events:
                 self._step_done, self._fin_done, self._fin_pending = torch.cuda.Event(), torch.cuda.Event(), False
 
@@ -529,14 +531,69 @@ class LeggedRobotMotionTracking:
         instead of the stepping stream (None: back to one stream).  The env orders it after its fused launch and joins it before the next
         one; a caller that reads the globals on the stepping stream in between (pbhc_policy_sample reads the step counter) calls
         `wait_finalize()` first."""
-        if self._finalize_stream is not None:
-            self.wait_finalize()
+        self.wait_finalize()
+        if stream is not None and self._fin_deferred:
+            raise _lib.PbhcError("set_finalize_stream: the env leaves its reductions to riders (set_finalize_deferred)")
         self._finalize_stream = stream
         if stream is not None and self._step_done is None:
             self._step_done, self._fin_done = torch.cuda.Event(), torch.cuda.Event()
 
+    def set_finalize_deferred(self, on):
+        """on: a step launches its fused kernel only (`pbhc_env_step_launch`) and leaves its one-workgroup reduction OWED — no finish launch,
+        no side stream, no event.  The caller takes the reduction over as a rider of a launch of its own that follows the step on the stepping
+        stream (`take_finalize_rider()`: the rollout's next policy forward, agents/rollout.py); whatever nobody took is launched as the plain
+        `pbhc_env_step_finish` by `flush_finalize()`, which the next step and every reader of the globals call first (through
+        `wait_finalize()`), so that no caller can step on, or read, stale globals by forgetting.  off: back to a reduction per step, after
+        flushing.  Not with a finalize stream, the per-step statistics exchange, or the clip / start collectors (they live behind the
+        reduction)."""
+        if on and (self._finalize_stream is not None or self._totals is not None or self._clip_window is not None or self._start_window is not None):
+            raise _lib.PbhcError("set_finalize_deferred: not with a finalize stream, the per-step statistics exchange or the clip / start collectors")
+        if not on:
+            self.flush_finalize()
+        self._fin_deferred = bool(on)
+
+    def _sync_replay_io(self):
+        """the step's view of the simulator's replay window (frame arrays, cursor, length), picked up lazily after the simulator got a new one"""
+        s, io = self.simulator, self._io
+        if self._replay_version != s.replay_version or s.replay is None:
+            s.ensure_replay()
+            r = s.replay
+            io.frame_root, io.frame_dof_pos = r["root"].data_ptr(), r["dof_pos"].data_ptr()
+            io.frame_dof_vel, io.frame_contact = r["dof_vel"].data_ptr(), r["contact"].data_ptr()
+            io.frame_cursor, io.num_frames = s.frame_cursor.data_ptr(), s.replay_len
+            self._replay_version = s.replay_version
+            self._io_epoch += 1
+
+    def finalize_rider(self):
+        """-> a `PbhcRider` whose finalize half describes this env's reduction (nothing is launched, no state changes): the same for every
+        step while `graph_key()` stays what it is — a captured launch may hold it"""
+        self._sync_replay_io()
+        r = _lib.PbhcRider()
+        _lib.check(self._lib.pbhc_env_finalize_rider(self._env, C.byref(self._io), C.byref(r)), "pbhc_env_finalize_rider")
+        return r
+
+    @property
+    def finalize_owed(self):
+        """a deferred step's reduction is still to be launched or taken (False again once something on the way flushed it)"""
+        return self._fin_owed
+
+    def take_finalize_rider(self):
+        """The caller runs the owed reduction of the last step as a rider of a launch it queues NEXT on the stepping stream, before anything
+        that reads the globals: -> the descriptor (`finalize_rider()`); the reduction counts as handed over."""
+        if not self._fin_owed:
+            raise _lib.PbhcError("take_finalize_rider: no reduction is owed (set_finalize_deferred(True), then step())")
+        self._fin_owed = False
+        return self.finalize_rider()
+
+    def flush_finalize(self):
+        """launch the reduction a deferred step still owes (if any) as the plain `pbhc_env_step_finish` on the current stream"""
+        if self._fin_owed:
+            self._fin_owed = False
+            _lib.check(self._lib.pbhc_env_step_finish(self._env, C.byref(self._io), _lib.current_stream()), "pbhc_env_step_finish")
+
     def wait_finalize(self):
-        """the current stream waits for the last step's reduction (no-op on one stream)"""
+        """the current stream is behind the last step's reduction: waits for the finalize stream's (no-op on one stream), launches an owed one"""
+        self.flush_finalize()
         if self._fin_pending:
             torch.cuda.current_stream().wait_event(self._fin_done)
             self._fin_pending = False
@@ -760,14 +817,8 @@ class LeggedRobotMotionTracking:
         s = self.simulator
         io = self._io
         io.actions_in = actions.data_ptr()
-        if self._replay_version != s.replay_version or s.replay is None:
-            s.ensure_replay()
-            r = s.replay
-            io.frame_root, io.frame_dof_pos = r["root"].data_ptr(), r["dof_pos"].data_ptr()
-            io.frame_dof_vel, io.frame_contact = r["dof_vel"].data_ptr(), r["contact"].data_ptr()
-            io.frame_cursor, io.num_frames = s.frame_cursor.data_ptr(), s.replay_len
-            self._replay_version = s.replay_version
-            self._io_epoch += 1
+        self.flush_finalize()                        # (a deferred step's reduction nobody took: before io moves on, and before this step)
+        self._sync_replay_io()
         io.frame_index = s.take_host_frame()
         # _update_tasks_callback's re-draw of every env's episodic DR (legged_robot_base.py:390-395): decided on the host, done by the kernel
         # in this very step (after its torques, before its observations — where the reference does it)
@@ -782,7 +833,15 @@ class LeggedRobotMotionTracking:
         del prev
         self._flush_statistics()
         fs = self._finalize_stream
-        if fs is None:
+        if self._fin_deferred:
+            # the fused launch only: its reduction is owed (set_finalize_deferred) — taken over by the caller's next launch on this stream, or
+            # flushed before the next step / the next reader of the globals
+            st = _lib.current_stream()
+            _lib.check(self._lib.pbhc_env_step_launch(self._env, C.byref(io), st), "pbhc_env_step_launch")
+            if self._rec is not None:                # the recorder needs the step's per-env outputs only, not its reduction
+                _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), st), "pbhc_record_motion")
+            self._fin_owed = True
+        elif fs is None:
             _lib.check(self._lib.pbhc_env_step(self._env, C.byref(io), _lib.current_stream()), "pbhc_env_step")
             if self._rec is not None:
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), _lib.current_stream()), "pbhc_record_motion")
