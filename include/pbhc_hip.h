@@ -777,6 +777,12 @@ int pbhc_linear_act_fwd(const float* x, const float* w, const float* bias, float
  * output layer (14 / 9 us of launch for 0.14 GFLOP at 24 576 rows).  NO <= 32, K >= 4; out rows contiguous. */
 int pbhc_linear_act_fwd_out(const float* x, const float* w, const float* bias, float* y, float* pre, int M, int N, int K, int act, const float* w_out,
                             const float* b_out, int NO, float* out, void* stream);
+/* pbhc_linear_act_fwd_out for TWO stacks' tails in one launch (the same 32 x 128 tile code on a shared grid; the problem with the longer K
+ * takes the leading workgroups): each problem's y / pre / out are bit for bit those of its own pbhc_linear_act_fwd_out call.  Both argument
+ * sets are checked as there; the two M need not be equal. */
+int pbhc_linear_act_fwd_out_pair(const float* x0, const float* w0, const float* bias0, float* y0, float* pre0, int M0, int N0, int K0, int act0, const float* w_out0,
+                                 const float* b_out0, int NO0, float* out0, const float* x1, const float* w1, const float* bias1, float* y1, float* pre1, int M1,
+                                 int N1, int K1, int act1, const float* w_out1, const float* b_out1, int NO1, float* out1, void* stream);
 /* The same with row strides and a batch: batch b computes y[b] = act(x[b] . w^T + bias) with x[b] = x + b * x_batch_stride (rows lda floats
  * apart, lda >= K), y[b] = y + b * y_batch_stride (rows ldc floats apart, ldc >= N), one weight matrix for all — e.g. the L output positions of
  * nn.Conv1d(C -> O, kernel k, stride s) on time-major activations [B, T, C] (encoder_modules.py:60-107): window l is the [B, k*C] matrix at
@@ -891,6 +897,15 @@ int pbhc_mlp_fwd(const float* x, int ldx, const float* const* weights, const flo
  * scratch may be NULL (no column sums); act 0: saved unused. */
 int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, float* dx, float* scratch, int* num_row_blocks, int M, int N, int K,
                           int act, void* stream);
+/* pbhc_linear_dgrad_act for TWO layers in one launch on 32 x 128 tiles (the larger problem takes the leading workgroups; each problem has its
+ * own scratch and row-block count = ceil(M / 32)): bit for bit the results of two pbhc_linear_dgrad_act calls that run on 32 x 128 tiles.
+ * Refused for a problem that entry would not run so: needs 4 <= K <= 128 and N % 4 == 0.  The two M need not be equal. */
+/* 1 if pbhc_linear_dgrad_act itself runs (M, N, K) on those tiles (its own tile choice; no test / measurement setting active), else 0:
+ * ask this for BOTH problems before forming a pair, so that pairing never changes the tile height a layer runs on. */
+int pbhc_linear_dgrad_act_pairable(int M, int N, int K);
+int pbhc_linear_dgrad_act_pair(const float* dy0, const float* w0, const float* saved0, float* dx0, float* scratch0, int* num_row_blocks0, int M0, int N0, int K0,
+                               int act0, const float* dy1, const float* w1, const float* saved1, float* dx1, float* scratch1, int* num_row_blocks1, int M1, int N1,
+                               int K1, int act1, void* stream);
 /* The weight gradient of that Linear (autograd's `dy.t() @ x`): dw[N,K] = sum over the M rows of dy[m,N]^T x[m,K], N = out_features,
  * K = in_features.  The rows are split over pbhc_linear_wgrad_parts(M, N, K) workgroup groups (0: shape not supported — N % 4, M % 32, K < 4 —
  * use the library) whose partial images go to `scratch` (parts * N * K floats) and are summed in a fixed order. */

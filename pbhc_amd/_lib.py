@@ -103,7 +103,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
            "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
            "pbhc_motion_extend_batch", "pbhc_motion_augment_batch",
-           "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize"]
+           "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
+           "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable"]
 
 
 class PbhcError(RuntimeError):
@@ -167,6 +168,9 @@ def _load():
     lib.pbhc_linear_act_fwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
     lib.pbhc_linear_act_fwd_out.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp, vp]
     lib.pbhc_linear_dgrad_act.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i, vp]
+    lib.pbhc_linear_act_fwd_out_pair.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp] * 2 + [vp]
+    lib.pbhc_linear_dgrad_act_pairable.argtypes = [i, i, i]
+    lib.pbhc_linear_dgrad_act_pair.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i] * 2 + [vp]
     lib.pbhc_gemm_debug_force_shape.argtypes = [i]
     lib.pbhc_debug_out_bwd_variant.argtypes = [i]
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]

@@ -17,8 +17,9 @@ MI355X:
 * every fused backward ends in ONE finishing launch (`pbhc_colsum_final`: bias gradients, the output layer's weight gradient, split-K partials);
   an owner that brackets several stacks' backwards with begin_deferred_finish() / finish_deferred() gets one for all of them, and may hand
   finish_deferred() the second stage of its loss (`pbhc_colsum_final_ppo_reduce`: one more workgroup of that launch, not a launch of its own).
-  MHPPO's optimiser step is then 22 launches: 6 forward (the two 128-column ones with their output layers), the loss's first stage, per stack
-  the output layer's one-pass backward + 2 input-gradient and 3 weight-gradient GEMMs, the finishing launch, gradient norm, Adam.
+  MHPPO's optimiser step is then 20 launches: 5 forward (the two stacks' 128-column layers, with their output layers, share ONE — forward_pair),
+  the loss's first stage, per stack the output layer's one-pass backward + 3 weight-gradient GEMMs and the wide layer's input gradient, ONE
+  input-gradient launch for both 128-column layers, the finishing launch, gradient norm, Adam (per stack, PBHC_PAIR_TAILS=0: 22).
 Same arithmetic as autograd's (the column sums are two-stage fp32 in a fixed order); pinned by the update-parity tests.
 """
 from __future__ import annotations
@@ -151,6 +152,134 @@ def finish_deferred(reduce=None):
     del keep
 
 
+# ---- launches two stacks can share ---------------------------------------------------------------------------------------------------------
+# _FusedMLP's forward and backward are generators (_fwd_steps / _bwd_steps) that yield the GEMM launches of a stack's 128-wide tail as requests:
+#   "fwd_out"  (x, w, bias, y, pre, M, N, K, act, w_out, b_out, NO, out)                   pbhc_linear_act_fwd_out
+#   "dgrad"    (dy, w, saved, dx, scratch, M, N, K, act)                       -> rows     pbhc_linear_dgrad_act
+# Each of these is one to four rounds of 32-row tiles with a short K loop — prologue-, epilogue- and ramp-bound — and the actor's and the
+# critic's use the same kernel instantiation: _run_joint issues such a pair as ONE launch (`*_pair`: the same tile code on a shared grid,
+# bit for bit the same results).  Pairing never changes the tile shape a layer runs on — the column-sum partials, and with them the bias
+# gradients, depend on the tile height — so a pair is formed only where both single entries would choose 32 x 128 tiles themselves.
+def _issue(kind, a):
+    """one request through its own entry -> number of partial rows (None for the forward)"""
+    lib, st = _lib.lib(), _lib.current_stream()
+    if kind == "fwd_out":
+        _lib.check(lib.pbhc_linear_act_fwd_out(*a, st), "pbhc_linear_act_fwd_out")
+        return None
+    nb = C.c_int(0)
+    _lib.check(lib.pbhc_linear_dgrad_act(*a[:5], C.byref(nb), *a[5:], st), "pbhc_linear_dgrad_act")
+    return nb.value
+
+
+def _pairable(kind, a):
+    """would the single entry run this request on the 32-row tiles the pair kernels are built for?  The tile-choice rule lives in ONE place,
+    csrc/pbhc_gemm.hip (pick_shape): the forward yields "fwd_out" only under the condition on which it calls that entry at all (an entry
+    that always runs 32 x 128 tiles), and for the input gradient the library is asked."""
+    if kind == "fwd_out":
+        return True
+    M, N, K = a[5], a[6], a[7]
+    return bool(_lib.lib().pbhc_linear_dgrad_act_pairable(M, N, K))
+
+
+def _issue_pair(kind, a0, a1):
+    lib, st = _lib.lib(), _lib.current_stream()
+    if kind == "fwd_out":
+        _lib.check(lib.pbhc_linear_act_fwd_out_pair(*a0, *a1, st), "pbhc_linear_act_fwd_out_pair")
+        return None, None
+    nb0, nb1 = C.c_int(0), C.c_int(0)
+    _lib.check(lib.pbhc_linear_dgrad_act_pair(*a0[:5], C.byref(nb0), *a0[5:], *a1[:5], C.byref(nb1), *a1[5:], st), "pbhc_linear_dgrad_act_pair")
+    return nb0.value, nb1.value
+
+
+def _run_single(gen):
+    """run a _fwd_steps / _bwd_steps generator to its end, every request through its own entry -> the generator's result"""
+    try:
+        req = next(gen)
+        while True:
+            req = gen.send(_issue(*req))
+    except StopIteration as e:
+        return e.value
+
+
+def _run_joint(g0, g1):
+    """Two stacks' generators side by side: each runs to its first request (g0, then g1: a stack's own launches keep their order); where both
+    ask for the same pairable launch it is issued once for both, else each request through its own entry; then each generator runs to its
+    end alone, g0 first.  -> (result of g0, result of g1)"""
+    gens, res = (g0, g1), [None, None]
+
+    def step(j, reply=None, first=False):                  # -> the generator's next request, or None once it has returned (result kept)
+        try:
+            return next(gens[j]) if first else gens[j].send(reply)
+        except StopIteration as e:
+            res[j] = e.value
+            return None
+
+    r0, r1 = step(0, first=True), step(1, first=True)
+    if r0 is not None and r1 is not None and r0[0] == r1[0] and _pairable(*r0) and _pairable(*r1):
+        replies = _issue_pair(r0[0], r0[1], r1[1])
+    else:
+        replies = [None if r is None else _issue(*r) for r in (r0, r1)]
+    for j, r in enumerate((r0, r1)):
+        if r is not None:
+            r = step(j, replies[j])
+        while r is not None:
+            r = step(j, _issue(*r))
+    return res[0], res[1]
+
+
+class _Sub:
+    """a stack's share of a joint application's autograd context: what _fwd_steps leaves on `ctx` for _bwd_steps"""
+    grad_cols = None
+
+
+class _FusedMLPPair(torch.autograd.Function):
+    """Two independent stacks (MHPPO's actor and critic) in one application, so that the launches of their 128-wide tails can be paired:
+    forward  stack 0's and stack 1's wide layers, then ONE launch for both tails (last hidden layer + output layer);
+    backward each stack's output-layer backward and library weight gradient of the 128-wide layer, ONE launch for both input gradients of
+    that layer, then each stack's remaining chain as in _FusedMLP.  Same kernels on the same tiles: every result is bit for bit what two
+    _FusedMLP applications give."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, seq0, seq1, *params):
+        s0, s1 = _Sub(), _Sub()
+        (out0, saved0), (out1, saved1) = _run_joint(_FusedMLP._fwd_steps(s0, x0, seq0), _FusedMLP._fwd_steps(s1, x1, seq1))
+        ctx.subs, ctx.nsaved0 = (s0, s1), len(saved0)
+        ctx.save_for_backward(*saved0, *saved1)
+        return out0, out1
+
+    @staticmethod
+    def backward(ctx, dout0, dout1):
+        s0, s1 = ctx.subs
+        saved = ctx.saved_tensors
+        # (stack 1 leads, as autograd runs the later of two separate nodes first)
+        (dx1, flat1), (dx0, flat0) = _run_joint(_FusedMLP._bwd_steps(s1, saved[ctx.nsaved0:], dout1, ctx.needs_input_grad[1]),
+                                                _FusedMLP._bwd_steps(s0, saved[:ctx.nsaved0], dout0, ctx.needs_input_grad[0]))
+        return (dx0, dx1, None, None, *flat0, *flat1)
+
+
+def forward_pair(seq0, x0, seq1, x1):
+    """(seq0(x0), seq1(x1)) as ONE autograd node with the two stacks' 128-wide tails in paired launches, or None — nothing launched —
+    where that does not apply and the caller applies each stack on its own: both must be fused ELU / ReLU stacks that store their
+    gradients in place (grad_direct, no other live application), end in Linear(K, 128) - act - Linear(128, <= 32), and the rows must be
+    in the range where 32 x 128 tiles are chosen for both layers of every pair."""
+    if not (FUSED_GEMM and FWD_OUT and OUT_BWD and torch.is_grad_enabled()):
+        return None
+    B = x0.shape[0]
+    if not (x1.shape[0] == B and 8192 <= B <= 32 * _lib.K["PBHC_ACT_MAX_BLOCKS"]):
+        return None
+    params = []
+    for seq, x in ((seq0, x0), (seq1, x1)):
+        lin = [m for m in seq if isinstance(m, nn.Linear)]
+        if not (supported(seq) and len(lin) >= 2 and type(seq[1]) in (nn.ELU, nn.ReLU) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+                and getattr(seq, "_grad_direct", False) and len(seq._fused_live) == 0
+                and lin[-2].out_features == 128 and lin[-2].in_features >= 4 and lin[-1].out_features <= 32
+                and all(l.weight.is_contiguous() and l.weight.requires_grad and l.bias is not None for l in lin)):
+            return None
+        for l in lin:
+            params += [l.weight, l.bias]
+    return _FusedMLPPair.apply(x0, x1, seq0, seq1, *params)
+
+
 class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, seq, *params):
@@ -159,6 +288,15 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def _fwd(ctx, x, seq):
+        out, saved = _run_single(_FusedMLP._fwd_steps(ctx, x, seq))
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def _fwd_steps(ctx, x, seq):
+        """The forward as a generator: it launches everything itself except the launches a second stack's could share a grid with, which it
+        YIELDS as (kind, arguments) requests — `_run_single` issues each through its own entry, `_run_joint` pairs two stacks' requests.
+        `ctx`: any object (the autograd context, or a stack's `_Sub` of a joint one).  Returns (output, tensors to save)."""
         lin = [m for m in seq if isinstance(m, nn.Linear)]
         act = _ACT_ID[type(seq[1])] if len(lin) > 1 else 0
         saved_in, saved_act = [], []
@@ -180,10 +318,9 @@ class _FusedMLP(torch.autograd.Function):
                         and 8192 <= B <= 32 * _lib.K["PBHC_ACT_MAX_BLOCKS"]):
                     # 32-row tiles hold whole 128-wide rows: the narrow output layer is applied to them while they are in LDS
                     out = torch.empty(B, lo.out_features, device=h.device)
-                    _lib.check(lib.pbhc_linear_act_fwd_out(h.data_ptr(), l.weight.data_ptr(), l.bias.data_ptr() if l.bias is not None else None, z.data_ptr(),
-                                                           pre.data_ptr() if pre is not None else None, B, 128, l.in_features, act, lo.weight.data_ptr(),
-                                                           lo.bias.data_ptr() if lo.bias is not None else None, lo.out_features, out.data_ptr(), st),
-                               "pbhc_linear_act_fwd_out")
+                    yield ("fwd_out", (h.data_ptr(), l.weight.data_ptr(), l.bias.data_ptr() if l.bias is not None else None, z.data_ptr(),
+                                       pre.data_ptr() if pre is not None else None, B, 128, l.in_features, act, lo.weight.data_ptr(),
+                                       lo.bias.data_ptr() if lo.bias is not None else None, lo.out_features, out.data_ptr()))
                     h = z
                     saved_act.append(pre if pre is not None else h)
                     continue
@@ -209,8 +346,7 @@ class _FusedMLP(torch.autograd.Function):
         if getattr(seq, "_grad_direct", False):
             ctx.live = _Live()
             seq._fused_live.add(ctx.live)
-        ctx.save_for_backward(*saved_in, *saved_act)
-        return out
+        return out, [*saved_in, *saved_act]
 
     @staticmethod
     def backward(ctx, dout):
@@ -219,12 +355,17 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def _bwd(ctx, dout, need_dx):
+        return _run_single(_FusedMLP._bwd_steps(ctx, ctx.saved_tensors, dout, need_dx))
+
+    @staticmethod
+    def _bwd_steps(ctx, saved, dout, need_dx):
         """-> (input gradient or None, [gw, gb] per layer in forward order).  `ctx.grad_cols = c0`: only the input columns [c0, in) carry a
-        gradient (_FusedMLPCat) — the first layer's input-gradient GEMM runs on that column slice of its weight alone."""
+        gradient (_FusedMLPCat) — the first layer's input-gradient GEMM runs on that column slice of its weight alone.
+        A generator like _fwd_steps: the input-gradient GEMMs are yielded as requests, and the number of partial rows the launch leaves is
+        sent back."""
         lib, st = _lib.lib(), _lib.current_stream()
         lin = [m for m in ctx.seq if isinstance(m, nn.Linear)]
         L = ctx.n
-        saved = ctx.saved_tensors
         ins, acts = saved[:L], saved[L:]
         d = dout.contiguous()
         B = d.shape[0]
@@ -270,8 +411,8 @@ class _FusedMLP(torch.autograd.Function):
                 gw = l.weight.grad if direct else torch.empty(n, k_in, device=d.device)
                 part_dw = torch.empty(MAXB * n * k_in, device=d.device)    # (a local: alive until the finishing launch below has been queued)
                 dn = torch.empty(B, k_in, device=d.device)
-                saved = acts[i - 1]
-                _lib.check(lib.pbhc_linear_out_bwd(d.data_ptr(), ins[i].data_ptr(), None if saved.data_ptr() == ins[i].data_ptr() else saved.data_ptr(),
+                below = acts[i - 1]
+                _lib.check(lib.pbhc_linear_out_bwd(d.data_ptr(), ins[i].data_ptr(), None if below.data_ptr() == ins[i].data_ptr() else below.data_ptr(),
                                                    l.weight.data_ptr(), B, n, k_in, ctx.act, dn.data_ptr(), part_dw.data_ptr(), part.data_ptr(),
                                                    scratch[offs[i - 1]:].data_ptr(), C.byref(nb), st), "pbhc_linear_out_bwd")
                 jobs.append((part.data_ptr(), gb.data_ptr(), nb.value, n))
@@ -297,8 +438,8 @@ class _FusedMLP(torch.autograd.Function):
                 # d_below = (d W) * act'(output of the layer below) + its row-block column sums, in the GEMM's epilogue
                 k = l.in_features
                 dn = torch.empty(B, k, device=d.device)
-                _lib.check(lib.pbhc_linear_dgrad_act(d.data_ptr(), l.weight.data_ptr(), acts[i - 1].data_ptr(), dn.data_ptr(),
-                                                     scratch[offs[i - 1]:].data_ptr(), C.byref(nb), B, k, n, ctx.act, st), "pbhc_linear_dgrad_act")
+                nb.value = yield ("dgrad", (d.data_ptr(), l.weight.data_ptr(), acts[i - 1].data_ptr(), dn.data_ptr(), scratch[offs[i - 1]:].data_ptr(),
+                                            B, k, n, ctx.act))
                 d = dn
                 have_partials = True
             elif i > 0 or need_dx:

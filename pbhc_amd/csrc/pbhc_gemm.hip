@@ -329,17 +329,28 @@ struct GemmOutLayer { const float* w; const float* b; float* out; int no; };
 // VALU instructions per 32 MFMAs ran the matrix pipe at 67 %.  Hence the shape of this loop: per-lane addresses are stage-invariant 32-bit
 // offsets (the stage's advance lives in the SGPR base of `global_load_lds_dwordx4 v_off, s[base]`; LDS fragment addresses are constant
 // VGPRs + immediates because the ring position is a template constant), loop control is scalar, and nothing else touches the VALU.
+//
+// One problem's arguments; the tile code is a function of them and of (bid, nblk) — this problem's workgroup index and count — so that two
+// independent problems of one instantiation can share a grid (k_gemm2_pair below).
+struct Gemm2Args {
+  const float* A; const float* B; const float* bias; const float* S;
+  float* Cout; float* Pre; float* part;
+  int M, N, K, act, tiles_n, dbg, lda, ldc;
+  GemmOutLayer fo;
+};
 template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
-__global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ bias,
-                                                      const float* __restrict__ S, float* __restrict__ Cout, float* __restrict__ Pre, float* __restrict__ part,
-                                                      int M, int N, int K, int act, int tiles_n, int dbg, int lda, int ldc, long long a_batch, long long c_batch,
-                                                      GemmOutLayer fo) {
-  // MODE 0 only: row strides of A / of the outputs (floats; lda >= K, ldc >= N) and a batch over blockIdx.y with element strides a_batch / c_batch
-  // — the L output positions of a Conv1d window GEMM in one launch (agents/agent_modules.py).  MODE 1 is launched with lda = K, ldc = N, one batch.
+__device__ __forceinline__ void gemm2_tile(const Gemm2Args& g, int bid, const int nblk) {
+  // MODE 0 only: row strides lda / ldc of A / of the outputs (floats; lda >= K, ldc >= N).  MODE 1 is launched with lda = K, ldc = N.
   // fo (32 x 128 forward tiles with N = 128 only): the stack's narrow OUTPUT layer applied to the tile's activated rows in the epilogue.
-  A += (size_t)blockIdx.y * a_batch;
-  Cout += (size_t)blockIdx.y * c_batch;
-  if (Pre) Pre += (size_t)blockIdx.y * c_batch;
+  const float* __restrict__ A = g.A;
+  const float* __restrict__ B = g.B;
+  const float* __restrict__ bias = g.bias;
+  const float* __restrict__ S = g.S;
+  float* __restrict__ Cout = g.Cout;
+  float* __restrict__ Pre = g.Pre;
+  float* __restrict__ part = g.part;
+  const int M = g.M, N = g.N, K = g.K, act = g.act, tiles_n = g.tiles_n, dbg = g.dbg, lda = g.lda, ldc = g.ldc;
+  const GemmOutLayer fo = g.fo;
   const long long dbg_c0 = (dbg & 8) ? clock64() : 0, dbg_w0 = (dbg & 8) ? wall_clock64() : 0;
   if (dbg & 0xE0) {
     // diagnosis (tools/gemm_ablation.py): de-phase the co-resident workgroups of the first round — the second / third workgroup of a CU starts
@@ -364,9 +375,7 @@ __global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A
   constexpr int A_STAGE = BM * BK, STAGE = (BM + BN) * BK;
   extern __shared__ __attribute__((aligned(16))) float lds[];   // NS * STAGE floats
 
-  int bid = blockIdx.x;
-  const int nblk = gridDim.x;
-  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+  if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);    // (XCD-aware tile order as in k_gemm, over this problem's own workgroups)
   const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
   const int row0 = tile_m * BM, col0 = tile_n * BN;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -571,6 +580,8 @@ __global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A
     const bool cok = vec ? col < N : col < N;              // first column inside
     float csum[4] = {0.f, 0.f, 0.f, 0.f};
     f32x4 sv[NP];
+    // (requested here, after the K loop: started before the first stage's DMA — 16 / 32 VGPRs live across the loop on 32- / 64-row tiles — the
+    // update measured slower by 0.03 / 0.15 ms, profiles/update_paired_tails.txt)
     if (MODE == 1 && act) {                                // the lower layer's saved activations for all of this thread's rows, in flight together
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
@@ -690,6 +701,29 @@ __global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A
       }
     }
   }
+}
+
+template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
+__global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ bias,
+                                                      const float* __restrict__ S, float* __restrict__ Cout, float* __restrict__ Pre, float* __restrict__ part,
+                                                      int M, int N, int K, int act, int tiles_n, int dbg, int lda, int ldc, long long a_batch, long long c_batch,
+                                                      GemmOutLayer fo) {
+  // MODE 0 only: a batch over blockIdx.y with element strides a_batch / c_batch — the L output positions of a Conv1d window GEMM in one
+  // launch (agents/agent_modules.py).  MODE 1 is launched with one batch.
+  const size_t ao = (size_t)blockIdx.y * a_batch, co = (size_t)blockIdx.y * c_batch;
+  const Gemm2Args g{A + ao, B, bias, S, Cout + co, Pre ? Pre + co : nullptr, part, M, N, K, act, tiles_n, dbg, lda, ldc, fo};
+  gemm2_tile<MODE, WM, WN, TM, TN, BK, NS>(g, blockIdx.x, gridDim.x);
+}
+
+// Two independent problems of the same instantiation in ONE grid (the actor's and the critic's 128-wide layers: each alone is one to four
+// rounds of tiles with a 4-16-stage K loop — prologue-, epilogue- and ramp-bound): workgroups [0, n0) run problem 0, the rest problem 1.
+// The choice is one scalar compare; the tile code, and with it every result, is k_gemm2's.  Launched with dbg = 0 in both argument sets: the
+// diagnosis branches of the tile code read blockIdx / gridDim of the whole grid and are for k_gemm2 alone.
+template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
+__global__ __launch_bounds__(GEMM_T, 2) void k_gemm2_pair(Gemm2Args g0, Gemm2Args g1, int n0) {
+  const bool first = (int)blockIdx.x < n0;
+  const Gemm2Args g = first ? g0 : g1;
+  gemm2_tile<MODE, WM, WN, TM, TN, BK, NS>(g, first ? blockIdx.x : blockIdx.x - n0, first ? n0 : gridDim.x - n0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -875,13 +909,19 @@ static hipError_t gemm_launch(const float* A, const float* B, const float* bias,
 // 2 = 64x128 (1x4 waves of 2x1)
 static int tile_bm(int shape) { return shape == 0 ? 128 : shape == 1 ? 96 : shape == 4 ? 32 : 64; }   // (shape 3, forward only: 64 x 64, 2x2 waves of one tile)
 
+// dynamic LDS of a k_gemm2 / k_gemm2_pair workgroup: the K stages' ring, reused by the epilogue's [BM][BN + 4] image (+ the fused output layer's weights)
+template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
+constexpr int gemm2_lds_bytes() {
+  constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+  constexpr int RING_BYTES = NS * (BM + BN) * BK * 4, IMAGE_BYTES = (BM + (MODE == 0 && BM == 32 && BN == 128 ? 32 : 0)) * (BN + 4) * 4;
+  return RING_BYTES > IMAGE_BYTES ? RING_BYTES : IMAGE_BYTES;
+}
 template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
 static hipError_t gemm2_launch(const float* A, const float* B, const float* bias, const float* S, float* C, float* pre, float* part, int M, int N, int K, int act,
                                hipStream_t st, int lda = 0, int ldc = 0, long long a_batch = 0, long long c_batch = 0, int batches = 1,
                                GemmOutLayer fo = GemmOutLayer{nullptr, nullptr, nullptr, 0}) {
   constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
-  constexpr int RING_BYTES = NS * (BM + BN) * BK * 4, IMAGE_BYTES = (BM + (MODE == 0 && BM == 32 && BN == 128 ? 32 : 0)) * (BN + 4) * 4;   // K stages; the epilogue's [BM][BN + 4] image (+ the fused output layer's weights)
-  constexpr int LDS_BYTES = RING_BYTES > IMAGE_BYTES ? RING_BYTES : IMAGE_BYTES;
+  constexpr int LDS_BYTES = gemm2_lds_bytes<MODE, WM, WN, TM, TN, BK, NS>();
   static bool attr_set = LDS_BYTES <= 65536;               // (the shapes pick_shape() chooses stay below 64 KB: nothing to set, safe under stream capture)
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2<MODE, WM, WN, TM, TN, BK, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
@@ -969,18 +1009,93 @@ int pbhc_linear_act_fwd_out(const float* x, const float* w, const float* bias, f
   return PBHC_OK;
 }
 
+static int dgrad_shape(int M, int N, int K) {             // the tile shape pbhc_linear_dgrad_act runs (M, N, K) on
+  int shape = pick_shape(M, N, K, g_force_shape, false);
+  if (shape == 3) shape = 2;
+  if ((M + tile_bm(shape) - 1) / tile_bm(shape) > PBHC_ACT_MAX_BLOCKS) shape = 0;
+  return shape;
+}
+
+int pbhc_linear_dgrad_act_pairable(int M, int N, int K) {
+  // what k_gemm2_pair<1, ...> is built for: the LDS-DMA kernel (gemm_variant's v2ok) on 32 x 128 tiles, chosen by the entry itself
+  if (M < 1 || N < 1 || K < 1 || g_variant != 0 || g_dbg != 0) return 0;
+  const bool v2ok = K >= 4 && (N & 3) == 0 && (size_t)M * K < (1u << 30) && (size_t)K * N < (1u << 30);
+  return v2ok && dgrad_shape(M, N, K) == 4;
+}
+
 int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, float* dx, float* scratch, int* num_row_blocks, int M, int N, int K,
                           int act, void* stream) {
   GEMM_ARG(dy && w && dx && M >= 1 && N >= 1 && K >= 1 && act >= 0 && act <= 3 && (act == 0 || saved) && (!scratch || num_row_blocks));
   GEMM_ARG(((uintptr_t)dy & 3) == 0 && ((uintptr_t)w & 3) == 0);
-  int shape = pick_shape(M, N, K, g_force_shape, false);
-  if (shape == 3) shape = 2;
-  if ((M + tile_bm(shape) - 1) / tile_bm(shape) > PBHC_ACT_MAX_BLOCKS) shape = 0;
+  const int shape = dgrad_shape(M, N, K);
   const int nb = (M + tile_bm(shape) - 1) / tile_bm(shape);
   GEMM_ARG(!scratch || nb <= PBHC_ACT_MAX_BLOCKS);
   if (num_row_blocks) *num_row_blocks = nb;
   // A = dy [M, K] (K = out_features of the layer, the reduction), B = W [K, N] (N = in_features, contiguous)
   GEMM_HIP(gemm_dispatch<1>(shape, dy, w, nullptr, saved, dx, nullptr, scratch, M, N, K, act, (hipStream_t)stream));
+  return PBHC_OK;
+}
+
+}  // extern "C"
+
+// ---- two problems on 32 x 128 tiles in one launch (k_gemm2_pair) ----
+template <int MODE>
+static hipError_t gemm2_pair_launch(const Gemm2Args& p0, const Gemm2Args& p1, bool swap, hipStream_t st) {
+  constexpr int LDS_BYTES = gemm2_lds_bytes<MODE, 1, 4, 1, 1, 32, 2>();
+  static_assert(LDS_BYTES <= 65536, "no attribute to set");
+  const Gemm2Args& a = swap ? p1 : p0;                     // the larger problem (the longer K / the wider N) goes first in the grid: its tiles start first
+  const Gemm2Args& b = swap ? p0 : p1;
+  const int na = ((a.M + 31) / 32) * a.tiles_n, nb = ((b.M + 31) / 32) * b.tiles_n;
+  hipLaunchKernelGGL((k_gemm2_pair<MODE, 1, 4, 1, 1, 32, 2>), dim3(na + nb), dim3(GEMM_T), LDS_BYTES, st, a, b, na);
+  return hipGetLastError();
+}
+static int fwd_out_check(const float* x, const float* w, const float* y, int M, int N, int K, int act, const float* w_out, int NO, const float* out) {
+  GEMM_ARG(x && w && y && w_out && out && M >= 1 && N == 128 && K >= 4 && NO >= 1 && NO <= 32 && act >= 0 && act <= 3);
+  GEMM_ARG(((uintptr_t)x & 3) == 0 && ((uintptr_t)w & 3) == 0 && ((uintptr_t)w_out & 3) == 0);
+  GEMM_ARG((size_t)M * K < (1u << 30) && (size_t)N * K < (1u << 30));
+  return PBHC_OK;
+}
+static int dgrad_pair_check(const float* dy, const float* w, const float* saved, const float* dx, const float* scratch, int* num_row_blocks, int M, int N, int K,
+                            int act) {
+  GEMM_ARG(dy && w && dx && M >= 1 && N >= 1 && K >= 1 && act >= 0 && act <= 3 && (act == 0 || saved) && (!scratch || num_row_blocks));
+  GEMM_ARG(((uintptr_t)dy & 3) == 0 && ((uintptr_t)w & 3) == 0);
+  // what pbhc_linear_dgrad_act runs on 32 x 128 tiles of the LDS-DMA kernel: K = out_features <= 128, whole 16-byte chunks along n, 32-bit offsets
+  GEMM_ARG(K >= 4 && K <= 128 && (N & 3) == 0 && (size_t)M * K < (1u << 30) && (size_t)K * N < (1u << 30));
+  GEMM_ARG(!scratch || (M + 31) / 32 <= PBHC_ACT_MAX_BLOCKS);
+  return PBHC_OK;
+}
+
+extern "C" {
+
+int pbhc_linear_act_fwd_out_pair(const float* x0, const float* w0, const float* bias0, float* y0, float* pre0, int M0, int N0, int K0, int act0, const float* w_out0,
+                                 const float* b_out0, int NO0, float* out0, const float* x1, const float* w1, const float* bias1, float* y1, float* pre1, int M1,
+                                 int N1, int K1, int act1, const float* w_out1, const float* b_out1, int NO1, float* out1, void* stream) {
+  int rc = fwd_out_check(x0, w0, y0, M0, N0, K0, act0, w_out0, NO0, out0);
+  if (rc == PBHC_OK) rc = fwd_out_check(x1, w1, y1, M1, N1, K1, act1, w_out1, NO1, out1);
+  if (rc != PBHC_OK) return rc;
+  if (g_variant != 0 || g_dbg != 0) {                      // a diagnosis setting of the single entry (staging variant, ablation flags): two single launches
+    rc = pbhc_linear_act_fwd_out(x0, w0, bias0, y0, pre0, M0, N0, K0, act0, w_out0, b_out0, NO0, out0, stream);
+    return rc != PBHC_OK ? rc : pbhc_linear_act_fwd_out(x1, w1, bias1, y1, pre1, M1, N1, K1, act1, w_out1, b_out1, NO1, out1, stream);
+  }
+  const Gemm2Args p0{x0, w0, bias0, nullptr, y0, pre0, nullptr, M0, N0, K0, act0, 1, 0, K0, N0, GemmOutLayer{w_out0, b_out0, out0, NO0}};
+  const Gemm2Args p1{x1, w1, bias1, nullptr, y1, pre1, nullptr, M1, N1, K1, act1, 1, 0, K1, N1, GemmOutLayer{w_out1, b_out1, out1, NO1}};
+  GEMM_HIP(gemm2_pair_launch<0>(p0, p1, K1 > K0, (hipStream_t)stream));
+  return PBHC_OK;
+}
+
+int pbhc_linear_dgrad_act_pair(const float* dy0, const float* w0, const float* saved0, float* dx0, float* scratch0, int* num_row_blocks0, int M0, int N0, int K0,
+                               int act0, const float* dy1, const float* w1, const float* saved1, float* dx1, float* scratch1, int* num_row_blocks1, int M1, int N1,
+                               int K1, int act1, void* stream) {
+  int rc = dgrad_pair_check(dy0, w0, saved0, dx0, scratch0, num_row_blocks0, M0, N0, K0, act0);
+  if (rc == PBHC_OK) rc = dgrad_pair_check(dy1, w1, saved1, dx1, scratch1, num_row_blocks1, M1, N1, K1, act1);
+  if (rc != PBHC_OK) return rc;
+  GEMM_ARG(g_variant == 0 && g_dbg == 0);                  // (diagnosis settings change what the single entry runs: see pbhc_linear_dgrad_act_pairable)
+  if (num_row_blocks0) *num_row_blocks0 = (M0 + 31) / 32;
+  if (num_row_blocks1) *num_row_blocks1 = (M1 + 31) / 32;
+  const GemmOutLayer none{nullptr, nullptr, nullptr, 0};
+  const Gemm2Args p0{dy0, w0, nullptr, saved0, dx0, nullptr, scratch0, M0, N0, K0, act0, (N0 + 127) / 128, 0, K0, N0, none};
+  const Gemm2Args p1{dy1, w1, nullptr, saved1, dx1, nullptr, scratch1, M1, N1, K1, act1, (N1 + 127) / 128, 0, K1, N1, none};
+  GEMM_HIP(gemm2_pair_launch<1>(p0, p1, (size_t)N1 * K1 > (size_t)N0 * K0, (hipStream_t)stream));
   return PBHC_OK;
 }
 
