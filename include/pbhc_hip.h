@@ -541,6 +541,38 @@ int pbhc_motion_augment_batch(const PbhcSkeleton* skel, const float* pose_aa, co
                               const int32_t* in_start, const int32_t* out_start, int total_out, PbhcMotionAugment params, const int32_t* perm,
                               float* out_pose_aa, float* out_trans, float* out_contact, void* stream);
 
+/* Contact masks and a stability screen for the SOURCE clips of a library, before the augmentation, the extension and the build (reference:
+ * the offline steps motion_source/count_pkl_contact_mask.py foot_detect and smpl_retarget/motion_filter/utils/motion_filter.py
+ * compute_com_cop / compute_diff / check_conditions, the latter restated in robot space; config keys robot.motion.contact_detection and
+ * robot.motion.screening; semantics: csrc/pbhc_motion_screen.hip and DESIGN §8). */
+typedef struct PbhcMotionScreen {
+  int32_t foot[2];                    /* extended-body indices of the two feet: mask column 0 and 1 */
+  int32_t epsilon_stab_frames;        /* N of check_conditions */
+  int32_t pad;
+  double vel_threshold;               /* squared displacement per FRAME below which a foot is still */
+  double height_threshold;            /* foot z below which it is down */
+  double epsilon_stab;                /* a frame is stable iff its distance is finite and below this */
+  double cop_w, cop_k;                /* pressure weight exp(-cop_w z) above the ground, 1 - cop_k z below it */
+} PbhcMotionScreen;
+#define PBHC_SCREEN_REPORT 8          /* floats per clip: stable, first_dist, last_dist, max_dist, unstable_share, max_gap, 2 x reserved (0) */
+/* Per-frame half: the FK of every frame of the concatenated raw arrays (pose_aa [total,Bx,3], trans [total,3], in_start [num_clips+1] device
+ * int32 as for pbhc_motion_extend_batch), one launch that leaves ground[c] = the lowest real-body origin z of clip c's first frame, then
+ * one wave per frame.  foot_pos [total,2,3] (NULL: no contact half; the params' foot indices are then not read) receives the world
+ * positions of the two feet; dist [total] (NULL: no stability half; body_mass, body_com and ground may then be NULL) the horizontal
+ * distance between the mass-weighted centre of the real bodies (body_mass [B], body_com [B,3] in the body frame) and the pressure-weighted
+ * centre of their origins.  ground: device float [num_clips], scratch.  A clip whose in_start entries do not describe the input is left
+ * unwritten. */
+int pbhc_motion_screen_frames(const PbhcSkeleton* skel, const float* pose_aa, const float* trans, int total, int num_clips, const int32_t* in_start,
+                              PbhcMotionScreen params, const float* body_mass, const float* body_com, float* ground, float* foot_pos, float* dist,
+                              void* stream);
+/* Per-clip half, one workgroup per clip.  mask [total,2] (with foot_pos; both NULL: no contact half): rows of the clips with derive[c] != 0
+ * (device int32 [num_clips]) are written — frame 0 of a clip 1, frame f >= 1: 1 iff |p_f - p_(f-1)|^2 < vel_threshold and p_f.z <
+ * height_threshold, else 0 — the rows of the others are not touched.  report [num_clips,PBHC_SCREEN_REPORT] (with dist; both NULL: no
+ * stability half): stable = first and last frame stable and, if the clip has more than N frames, no two consecutive stable frames N or more
+ * apart; max_gap = the largest such distance (0 with fewer than two stable frames); max_dist is +inf if a distance is not finite. */
+int pbhc_motion_screen_clips(const float* foot_pos, const float* dist, int total, int num_clips, const int32_t* in_start, const int32_t* derive,
+                             PbhcMotionScreen params, float* mask, float* report, void* stream);
+
 /* Phase lookup + lerp/slerp.  Replaces MotionLibBase.get_motion_state (motion_lib_base.py:123-259).
  * ids [N] int64, times [N], offset [N,3] or NULL -> out [N,row] packed like a frame row
  * (positions include the offset). */

@@ -90,6 +90,7 @@ PbhcConvEncoder = _S["PbhcConvEncoder"]
 PbhcPpoReduce = _S["PbhcPpoReduce"]
 PbhcMotionExtend = _S["PbhcMotionExtend"]
 PbhcMotionAugment = _S["PbhcMotionAugment"]
+PbhcMotionScreen = _S["PbhcMotionScreen"]
 
 EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
            "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
@@ -102,7 +103,7 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
            "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
            "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
-           "pbhc_motion_extend_batch", "pbhc_motion_augment_batch",
+           "pbhc_motion_extend_batch", "pbhc_motion_augment_batch", "pbhc_motion_screen_frames", "pbhc_motion_screen_clips",
            "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
            "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable"]
 
@@ -129,6 +130,8 @@ def _load():
     lib.pbhc_motion_build_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
     lib.pbhc_motion_extend_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, i, PbhcMotionExtend, vp, vp, vp, vp]
     lib.pbhc_motion_augment_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, i, PbhcMotionAugment, vp, vp, vp, vp, vp]
+    lib.pbhc_motion_screen_frames.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, i, i, vp, PbhcMotionScreen, vp, vp, vp, vp, vp, vp]
+    lib.pbhc_motion_screen_clips.argtypes = [vp, vp, i, i, vp, vp, PbhcMotionScreen, vp, vp, vp]
     lib.pbhc_motion_state.argtypes = [C.POINTER(PbhcMotionTable), i, i, vp, vp, vp, i, vp, vp]
     lib.pbhc_sim_fk.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp]
     lib.pbhc_debug_fk.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp]

@@ -78,7 +78,8 @@ def rebase_heading(clip, target_heading):
 
 
 class MotionLib:
-    def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None, augmentation=None):
+    def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None, augmentation=None, contact_detection=None,
+                 screening=None):
         """clips: list of clip dicts (see load_motion_file).  max_len > 0: `load_motions` gives every env slot its own random crop of at most
         `max_len` frames of its clip (motion_lib_base.py:420-428) — the tables are then per SLOT (num_envs entries of max_len rows, allocated
         once so that the step kernel's pointers stay valid) instead of per unique clip.
@@ -87,7 +88,11 @@ class MotionLib:
         tables and crops describe the extended clips.  None, or both frame counts 0: no launch.
         augmentation (motion_augment.Augmentation or None): after the cut and before the extension every clip becomes V clips — itself, its
         mirror image, time-scaled copies — on the device (`pbhc_motion_augment_batch`): clip src * V + v is variant v of source clip src
-        (`variant_source`, `variant_info`), and everything downstream sees M * V ordinary clips.  None, or no mirror and no speed: no launch."""
+        (`variant_source`, `variant_info`), and everything downstream sees M * V ordinary clips.  None, or no mirror and no speed: no launch.
+        contact_detection / screening (motion_screen.ContactDetection / Screening or None): after the cut and before everything else, ONE
+        pre-pass over the source clips on the device (`_screen_device`) derives the contact masks of the clips that ship none (or of all,
+        `overwrite`) into copies of the clip dicts — `contact_derived` — and fills `screen_report`; `action: exclude` drops the unstable
+        clips there, so everything downstream sees the kept ones only.  Both None or not enabled: no upload, no launch."""
         if interpolation is not None:
             if interpolation.num_dof != skeleton.num_dof:
                 raise _lib.PbhcError(f"interpolation was set up for {interpolation.num_dof} dofs, the skeleton has {skeleton.num_dof}")
@@ -101,6 +106,14 @@ class MotionLib:
         self._csk = skeleton.to_c()
         Bx, D = skeleton.num_bodies_ext, skeleton.num_dof
         self.row = 2 * D + 2 + 13 * Bx
+        self.contact_detection = contact_detection if contact_detection is not None and contact_detection.active else None
+        self.screening = screening if screening is not None and screening.active else None
+        self.contact_derived = [False] * len(clips)      # per source clip as given: its mask was derived here, not shipped
+        self.screen_report = None                        # screening only: arrays over the source clips as given (see _screen_device)
+        self._screen_dist = self._screen_starts = None
+        self._raw_upload = None                          # (_screen_device's upload, handed to the first _upload_raw of the same clips)
+        if self.contact_detection is not None or self.screening is not None:
+            clips = self._screen_device(clips)
         self.has_contact_mask = all("contact_mask" in c for c in clips)
         self._contact_size = 2
         self.max_len = int(max_len)
@@ -121,11 +134,13 @@ class MotionLib:
         self.table = _lib.PbhcMotionTable()
         if self.max_len > 0 and any(F + added >= self.max_len for F in self._variant_frames):
             self._init_slot_tables(clips)
+            self._raw_upload = None
             return
         self.max_len = -1
         self._raw = None
         self.slot_table = self.slot_clip                 # the kernel's motion ids: unique-clip tables, slot -> clip
         self._build_unique_tables(clips)
+        self._raw_upload = None
 
     def _init_variants(self, clips):
         """`variant_source`, `variant_info`, the mirror tables and the frame count of every variant (before the extension); the skeleton's
@@ -151,6 +166,73 @@ class MotionLib:
                 self._d_perm = torch.from_numpy(mt.body_perm.astype(np.int32)).to(dev)
         self._num_unique_motions = len(self.variant_info)
         self.variant_source = torch.from_numpy(np.array([v[0] for v in self.variant_info], dtype=np.int64)).to(dev)
+
+    def _screen_device(self, clips):
+        """The pre-pass of `contact_detection` and `screening` on the source clips: the raw arrays uploaded once, the per-frame launch
+        (`pbhc_motion_screen_frames`: FK, the two foot positions, the stability distance) and the per-clip one (`pbhc_motion_screen_clips`:
+        mask rows, report rows), two small results read back -> the clips the library keeps, those whose mask was derived as copies.
+        `screen_report`: stable, first_dist, last_dist, max_dist, unstable_share, max_gap [len(clips)] and kept (new index -> old)."""
+        from . import motion_screen
+
+        cd, scr, dev, sk = self.contact_detection, self.screening, self.device, self.skeleton
+        Bx = sk.num_bodies_ext
+        for c in clips:
+            if np.asarray(c["pose_aa"]).shape[1] < Bx:
+                raise _lib.PbhcError(f"pose_aa has {np.asarray(c['pose_aa']).shape[1]} bodies, skeleton needs {Bx}")
+        derive = np.zeros(len(clips), dtype=np.int32)
+        if cd is not None:
+            derive[:] = [1 if cd.overwrite or "contact_mask" not in c else 0 for c in clips]
+        params = motion_screen.to_c(cd, scr, sk)           # (resolves the foot names: an unknown one is refused before anything is uploaded)
+        d_mass = d_com = None
+        if scr is not None:
+            scr.check_skeleton(sk)
+            d_mass, d_com = torch.from_numpy(sk.body_mass).to(dev), torch.from_numpy(np.ascontiguousarray(sk.body_com)).to(dev)
+        nframes = [np.asarray(c["pose_aa"]).shape[0] for c in clips]
+        M, starts = len(clips), np.concatenate([[0], np.cumsum(nframes)]).astype(np.int32)
+        total = int(starts[-1])
+        d_pose = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx] for c in clips], axis=0))).to(dev)
+        d_trans = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["root_trans_offset"], dtype=np.float32) for c in clips], axis=0))).to(dev)
+        d_start, d_derive = torch.from_numpy(starts).to(dev), torch.from_numpy(derive).to(dev)
+        contact = cd is not None and bool(derive.any())
+        d_foot = torch.empty(total, 2, 3, device=dev) if contact else None
+        d_mask = torch.zeros(total, 2, device=dev) if contact else None
+        d_dist = torch.empty(total, device=dev) if scr is not None else None
+        d_ground = torch.empty(M, device=dev) if scr is not None else None
+        d_report = torch.zeros(M, _lib.K["PBHC_SCREEN_REPORT"], device=dev) if scr is not None else None
+        if contact or scr is not None:
+            st = _lib.current_stream()
+            _lib.check(_lib.lib().pbhc_motion_screen_frames(C.byref(self._csk), _lib.ptr(d_pose), _lib.ptr(d_trans), total, M, _lib.ptr(d_start), params,
+                                                            _lib.ptr(d_mass), _lib.ptr(d_com), _lib.ptr(d_ground), _lib.ptr(d_foot), _lib.ptr(d_dist), st),
+                       "pbhc_motion_screen_frames")
+            _lib.check(_lib.lib().pbhc_motion_screen_clips(_lib.ptr(d_foot), _lib.ptr(d_dist), total, M, _lib.ptr(d_start), _lib.ptr(d_derive), params,
+                                                           _lib.ptr(d_mask), _lib.ptr(d_report), st), "pbhc_motion_screen_clips")
+        out = list(clips)
+        if contact:
+            mask = d_mask.cpu().numpy()                    # (the copy synchronises: the staging tensors above may die with this scope)
+            for i in np.flatnonzero(derive):
+                out[i] = dict(clips[i], contact_mask=mask[starts[i]:starts[i + 1]].copy())
+        self.contact_derived = [bool(d) for d in derive] if cd is not None else self.contact_derived
+        if scr is None:
+            self._raw_upload = ([id(c["pose_aa"]) for c in out], d_pose, d_trans)          # the raw arrays are uploaded once: the build starts from these
+            return out
+        rep = d_report.cpu().numpy().astype(np.float64)
+        kept = motion_screen.kept_clips(rep[:, 0] != 0.0, scr.action)
+        self.screen_report = dict(stable=rep[:, 0] != 0.0, first_dist=rep[:, 1], last_dist=rep[:, 2], max_dist=rep[:, 3], unstable_share=rep[:, 4],
+                                  max_gap=rep[:, 5].astype(np.int64), kept=np.asarray(kept, dtype=np.int64))
+        self._screen_dist, self._screen_starts = d_dist, starts
+        if len(kept) < M:                                  # the kept clips' frames, gathered on the device
+            rows = torch.from_numpy(np.concatenate([np.arange(starts[i], starts[i + 1]) for i in kept])).to(dev)
+            d_pose, d_trans = d_pose.index_select(0, rows), d_trans.index_select(0, rows)
+        out = [out[i] for i in kept]
+        self._raw_upload = ([id(c["pose_aa"]) for c in out], d_pose, d_trans)
+        return out
+
+    def stability_distance(self, i):
+        """the per-frame distance between centre of mass and centre of pressure of source clip `i` (as given, before `exclude`) [F] float32"""
+        if self._screen_dist is None:
+            raise _lib.PbhcError("stability_distance: the library was built without robot.motion.screening")
+        a, b = int(self._screen_starts[int(i)]), int(self._screen_starts[int(i) + 1])
+        return self._screen_dist[a:b].cpu().numpy()
 
     def _augment_device(self, d_pose, d_trans, d_contact, nframes):
         """Every variant of every clip in ONE launch (`pbhc_motion_augment_batch`), on the concatenated raw arrays as `_upload_raw` leaves them
@@ -210,8 +292,12 @@ class MotionLib:
         """-> (pose_aa [total,Bx,3], trans [total,3], contact [total,2] or None on the device, frames per clip) of the clips concatenated"""
         Bx, dev = self.skeleton.num_bodies_ext, self.device
         nframes = [np.asarray(c["pose_aa"]).shape[0] for c in clips]
-        d_pose = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx] for c in clips], axis=0))).to(dev)
-        d_trans = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["root_trans_offset"], dtype=np.float32) for c in clips], axis=0))).to(dev)
+        held, self._raw_upload = self._raw_upload, None
+        if held is not None and held[0] == [id(c["pose_aa"]) for c in clips]:        # the pre-pass uploaded these very arrays
+            d_pose, d_trans = held[1], held[2]
+        else:
+            d_pose = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["pose_aa"], dtype=np.float32)[:, :Bx] for c in clips], axis=0))).to(dev)
+            d_trans = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["root_trans_offset"], dtype=np.float32) for c in clips], axis=0))).to(dev)
         d_contact = None
         if self.has_contact_mask:
             d_contact = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(c["contact_mask"], dtype=np.float32) for c in clips], axis=0))).to(dev)
@@ -347,7 +433,8 @@ class MotionLib:
     def from_config(cls, mcfg, skeleton, num_envs, device, max_len=-1, robot=None):
         """mcfg = config.robot.motion (motion_file = .pkl / .npz / directory); max_len: see __init__.  mcfg.interpolation (absent by default):
         see motion_interp.Interpolation.from_config; robot = config.robot supplies its default joints and the dof names.  mcfg.augmentation
-        (absent by default): see motion_augment.Augmentation.from_config."""
+        (absent by default): see motion_augment.Augmentation.from_config.  mcfg.contact_detection, mcfg.screening (absent by default): see
+        motion_screen.ContactDetection.from_config / Screening.from_config."""
         path = str(mcfg.motion_file)
         if not os.path.isabs(path) and not os.path.exists(path):
             path = os.path.join(_lib.ROOT, path)
@@ -367,7 +454,14 @@ class MotionLib:
             if augmentation.active and mcfg.get("motion_lib_type", "origin") == "WJX":
                 raise _lib.PbhcError("robot.motion.augmentation with motion_lib_type WJX: a v1 library is ONE clip, the variants would make it "
                                      f"{augmentation.num_variants}")
-        return cls(skeleton, clips, num_envs, device, max_len=max_len, interpolation=interpolation, augmentation=augmentation)
+        contact_detection = screening = None
+        if mcfg.get("contact_detection", None) is not None or mcfg.get("screening", None) is not None:
+            from .motion_screen import ContactDetection, Screening
+
+            contact_detection = ContactDetection.from_config(mcfg.get("contact_detection", None))
+            screening = Screening.from_config(mcfg.get("screening", None))
+        return cls(skeleton, clips, num_envs, device, max_len=max_len, interpolation=interpolation, augmentation=augmentation,
+                   contact_detection=contact_detection, screening=screening)
 
     # ---- slot -> clip assignment (load_motions, motion_lib_base.py:293-305) -----------------
     def load_motions(self, random_sample=True, start_idx=0, max_len=-1, target_heading=None, sampling_prob=None, crop_starts=None):

@@ -26,6 +26,8 @@ class Skeleton:
     local_rot_wxyz: np.ndarray   # [Bx,4]
     dof_axis: np.ndarray         # [D,3]
     depth: np.ndarray = field(default=None)
+    body_mass: np.ndarray = field(default=None)   # [B] link masses in kg, or None (only the MJCF holds them)
+    body_com: np.ndarray = field(default=None)    # [B,3] centre of mass of every link in its own frame, or None
 
     def __post_init__(self):
         self.parents = np.asarray(self.parents, dtype=np.int32)
@@ -36,6 +38,13 @@ class Skeleton:
         for i, p in enumerate(self.parents):
             depth[i] = 0 if p < 0 else depth[p] + 1
         self.depth = depth
+        if self.body_mass is not None:
+            self.body_mass = np.asarray(self.body_mass, dtype=np.float32)
+            self.body_com = np.zeros((len(self.body_mass), 3), np.float32) if self.body_com is None else np.asarray(self.body_com, dtype=np.float32)
+            if self.body_mass.shape != (len(self.body_names),) or self.body_com.shape != (len(self.body_names), 3):
+                raise ValueError(f"body_mass {self.body_mass.shape} / body_com {self.body_com.shape}: expected one entry per real body ({len(self.body_names)})")
+        else:
+            self.body_com = None
 
     @property
     def num_bodies(self):
@@ -56,7 +65,7 @@ class Skeleton:
         world = root.find("worldbody")
         if world is None or world.find("body") is None:
             raise ValueError(f"{path}: no <worldbody>/<body>")
-        names, parents, offs, rots = [], [], [], []
+        names, parents, offs, rots, mass, com = [], [], [], [], [], []
         stack = [(world.find("body"), -1)]
         # explicit-stack DFS, children visited in document order
         while stack:
@@ -66,6 +75,9 @@ class Skeleton:
             parents.append(parent)
             offs.append([float(x) for x in node.attrib.get("pos", "0 0 0").split()])
             rots.append([float(x) for x in node.attrib.get("quat", "1 0 0 0").split()])
+            inertial = node.find("inertial")                 # <inertial mass pos>: a body without one weighs nothing
+            mass.append(float(inertial.attrib.get("mass", "0")) if inertial is not None else 0.0)
+            com.append([float(x) for x in inertial.attrib.get("pos", "0 0 0").split()] if inertial is not None else [0.0, 0.0, 0.0])
             for child in reversed(node.findall("body")):
                 stack.append((child, idx))
         joints = world.findall(".//joint")
@@ -83,17 +95,20 @@ class Skeleton:
             offs.append(list(e["pos"]))
             rots.append(list(e["rot"]))
             ext_names.append(e["joint_name"])
-        return cls(names, ext_names, parents, offs, rots, axes)
+        return cls(names, ext_names, parents, offs, rots, axes, body_mass=mass, body_com=com)
 
     @classmethod
     def from_json(cls, path):
         d = json.load(open(path))
-        return cls(d["body_names"], d["body_names_ext"], d["parents"], d["offsets"], d["local_rot_wxyz"], d["dof_axis"])
+        return cls(d["body_names"], d["body_names_ext"], d["parents"], d["offsets"], d["local_rot_wxyz"], d["dof_axis"],
+                   body_mass=d.get("body_mass"), body_com=d.get("body_com"))
 
     def to_json(self, path):
-        json.dump(dict(body_names=self.body_names, body_names_ext=self.body_names_ext, parents=self.parents.tolist(),
-                       offsets=self.offsets.tolist(), local_rot_wxyz=self.local_rot_wxyz.tolist(), dof_axis=self.dof_axis.tolist()),
-                  open(path, "w"), indent=1)
+        d = dict(body_names=self.body_names, body_names_ext=self.body_names_ext, parents=self.parents.tolist(),
+                 offsets=self.offsets.tolist(), local_rot_wxyz=self.local_rot_wxyz.tolist(), dof_axis=self.dof_axis.tolist())
+        if self.body_mass is not None:                        # only when present: a skeleton without masses writes the file it always wrote
+            d.update(body_mass=self.body_mass.tolist(), body_com=self.body_com.tolist())
+        json.dump(d, open(path, "w"), indent=1)
 
     @classmethod
     def from_motion_config(cls, mcfg):

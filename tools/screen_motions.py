@@ -1,0 +1,85 @@
+"""Run the ingestion pre-pass of `robot.motion.contact_detection` / `robot.motion.screening` on a motion file and write what it found: the
+clips with their derived contact masks (the job of the reference's motion_source/count_pkl_contact_mask.py) and the per-clip stability
+report (the job of smpl_retarget/motion_filter/utils/motion_filter.py, in robot space), on the GPU: `pbhc_motion_screen_frames`,
+`pbhc_motion_screen_clips`.
+
+    python tools/screen_motions.py --config <config.yaml> [--out <clips.npz>] [--report <report.json>] [--motion-file <.pkl / .npz / dir>]
+        [--mjcf <robot.xml>] [--overwrite] [--epsilon-stab 0.1 --epsilon-stab-frames 100] [--exclude]
+
+The config supplies the skeleton and — if it has the keys — robot.motion.contact_detection and robot.motion.screening; without the keys both
+run with the reference's constants.  The stability screen needs link masses, which only the robot's MJCF holds: --mjcf reads the skeleton
+from that file (with the config's extend_config) when the config's asset is a skeleton JSON.  Without masses only the contact masks are made.
+--out: the kept clips through `save_motion_npz`, masks included.  --report: one JSON object per source clip.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pbhc_amd import _lib  # noqa: E402
+from pbhc_amd.motion_lib import MotionLib, load_motion_file, save_motion_npz  # noqa: E402
+from pbhc_amd.motion_screen import REPORT_FIELDS, ContactDetection, Screening  # noqa: E402
+from pbhc_amd.skeleton import Skeleton  # noqa: E402
+from pbhc_amd.utils.config import load_config  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--out", default=None, help=".npz to write: the kept clips with their contact masks")
+    ap.add_argument("--report", default=None, help=".json to write: the per-clip stability report")
+    ap.add_argument("--motion-file", default=None, help="default: robot.motion.motion_file of the config")
+    ap.add_argument("--mjcf", default=None, help="the robot's MJCF: skeleton WITH link masses (default: the config's asset)")
+    ap.add_argument("--overwrite", action="store_true", default=None, help="derive the mask of every clip, shipped ones included")
+    ap.add_argument("--epsilon-stab", type=float, default=None)
+    ap.add_argument("--epsilon-stab-frames", type=int, default=None)
+    ap.add_argument("--exclude", action="store_true", help="action: exclude — write only the clips that pass")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+
+    cfg = load_config(args.config, {}, now="tool")
+    mcfg = cfg.robot.motion
+    if args.mjcf is not None:
+        skel = Skeleton.from_mjcf(args.mjcf, [dict(e) for e in mcfg.get("extend_config", [])])
+    else:
+        skel = Skeleton.from_motion_config(mcfg)
+    ccfg = dict(mcfg.get("contact_detection", None) or {}, enable=True)
+    if args.overwrite:
+        ccfg["overwrite"] = True
+    scfg = dict(mcfg.get("screening", None) or {}, enable=skel.body_mass is not None)
+    for key in ("epsilon_stab", "epsilon_stab_frames"):
+        if getattr(args, key) is not None:
+            scfg[key] = getattr(args, key)
+    if args.exclude:
+        scfg["action"] = "exclude"
+    if skel.body_mass is None:
+        print("the skeleton has no link masses (pass --mjcf): contact masks only, no stability report")
+    path = args.motion_file or str(mcfg.motion_file)
+    if not os.path.isabs(path) and not os.path.exists(path):
+        path = os.path.join(_lib.ROOT, path)
+    named = load_motion_file(path)
+    ml = MotionLib(skel, [c for _, c in named], 1, args.device, contact_detection=ContactDetection.from_config(ccfg), screening=Screening.from_config(scfg))
+    rep = ml.screen_report
+    kept = list(range(len(named))) if rep is None else rep["kept"].tolist()
+    rows = []
+    for i, (name, c) in enumerate(named):
+        row = dict(name=name, frames=int(np.asarray(c["pose_aa"]).shape[0]), contact_derived=bool(ml.contact_derived[i]), kept=i in kept)
+        if rep is not None:
+            row.update({k: (bool(rep[k][i]) if k == "stable" else int(rep[k][i]) if k == "max_gap" else float(rep[k][i])) for k in REPORT_FIELDS})
+        rows.append(row)
+        print(row)
+    if args.out is not None:
+        save_motion_npz(args.out, [(named[i][0], c) for i, c in zip(kept, ml._clips)])
+        print(f"wrote {args.out}: {len(kept)} of {len(named)} clip(s)")
+    if args.report is not None:
+        with open(args.report, "w") as f:
+            json.dump(rows, f, indent=1)
+        print(f"wrote {args.report}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
