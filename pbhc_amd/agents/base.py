@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib
 from .. import dist as pdist
+from ..utils import resume, rng_state
 from .modules import RolloutStorage
 
 # name -> default.  Read at the time of use, not at import: the tests flip them between two agents of one process.
@@ -205,9 +206,14 @@ class OnDeviceAgent:
 
     # ---- learn loop (mh_ppo.py:206-250, ppo_mimic.py:267-357) --------------------------------
     def _learn_loop(self, num_iterations, rollout, train, before_iteration=None):
-        if self.init_at_random_ep_len:
-            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
-        obs_dict = self.env.reset_all()
+        if self.__dict__.pop("_resume_in_loop", False):
+            # a training state written inside this loop (`model_{it}.pt`): the run that wrote it went straight on to iteration it + 1, from the
+            # observations its last rollout left — no random episode lengths, no reset_all()
+            obs_dict = self._last_obs
+        else:
+            if self.init_at_random_ep_len:
+                self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
+            obs_dict = self.env.reset_all()
         self._train_mode()
         n = self.num_learning_iterations if num_iterations is None else num_iterations
         tot_iter = self.current_learning_iteration + n
@@ -221,11 +227,86 @@ class OnDeviceAgent:
             self._post_epoch_logging(dict(it=it, loss_dict=loss_dict, num_learning_iterations=n))
             if self.log_dir is not None and it % self.save_interval == 0 and self.rank == 0:
                 self.current_learning_iteration = it
-                self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
+                self._save_point = ("in_loop", it + 1)
+                try:
+                    self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
+                finally:
+                    self._save_point = None
             self.ep_infos.clear()
         self.current_learning_iteration = tot_iter
         if self.log_dir is not None and self.rank == 0:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+    # ---- exact resume (DESIGN.md §8 "Exact resume") ---------------------------------------------
+    def training_state(self):
+        """Everything outside the reference's checkpoint dictionary that decides how training goes on, as tensors, numbers, strings, lists,
+        dicts and None (the file stays loadable with torch.load(weights_only=True)): where the state was taken (`resume_point` "in_loop" —
+        by `_learn_loop` after an iteration — or "after_loop") and the iteration that comes next, the env's state_dict(), the observations
+        the last rollout left, the episode book-keeping, the counters and the four process-wide generators.  Draws from no generator and
+        launches nothing that writes state."""
+        if self.world_size > 1:
+            raise NotImplementedError("algo.config.save_training_state with more than one rank: every rank owns an env shard, only rank 0 "
+                                      "writes the checkpoint")
+        point, nxt = self.__dict__.get("_save_point") or ("after_loop", int(self.current_learning_iteration))
+        ts = dict(version=resume.STATE_VERSION, resume_point=point, next_iteration=int(nxt), num_envs=int(self.env.num_envs),
+                  sample_seed=int(self._sample_seed), env=self.env.state_dict(), last_obs={k: v.clone() for k, v in self._last_obs.items()},
+                  cur_reward_sum=self.cur_reward_sum.clone(), cur_episode_length=self.cur_episode_length.clone(), ep_stats=self._ep_stats.clone(),
+                  tot_timesteps=int(self.tot_timesteps), tot_time=float(self.tot_time), rollouts_done=int(self.__dict__.get("_rollouts_done", 0)),
+                  rng=rng_state.capture_globals(self.device))
+        ts["agent"] = self._extra_training_state()
+        return ts
+
+    def _extra_training_state(self):
+        """hook: what a subclass adds to the training state ({name: tensor / number}); `_load_extra_training_state` takes it back"""
+        return {}
+
+    def _check_extra_training_state(self, extra):
+        pass
+
+    def _load_extra_training_state(self, extra):
+        pass
+
+    def check_training_state(self, ts):
+        """everything `load_training_state` would refuse, without writing anything"""
+        what = f"{type(self).__name__}.load_training_state"
+        resume.check_version(ts, what)
+        if ts["resume_point"] not in resume.RESUME_POINTS:
+            raise _lib.PbhcError(f"{what}: resume_point {ts['resume_point']!r} is none of {resume.RESUME_POINTS}")
+        resume.check_equal(what, "num_envs", int(ts["num_envs"]), int(self.env.num_envs))
+        resume.check_equal(what, "the sampler's Philox key `_sample_seed` (seed torch with the saving run's config.seed before building env and agent)",
+                           int(ts["sample_seed"]), int(self._sample_seed))
+        resume.check_tensors(what, ts["last_obs"], self._last_obs)
+        resume.check_tensors(what, ts, {"cur_reward_sum": self.cur_reward_sum, "cur_episode_length": self.cur_episode_length, "ep_stats": self._ep_stats})
+        self.env.check_state_dict(ts["env"])
+        self._check_extra_training_state(ts["agent"])
+
+    def load_training_state(self, ts):
+        """Take a `training_state()` back, after the weights and the optimiser: tensors in place, counters, generators last.  A state taken
+        "in_loop" makes the next learn() skip its preamble and start at `next_iteration` from the restored observations."""
+        if self.world_size > 1:
+            raise NotImplementedError("algo.config.load_training_state with more than one rank: the training state holds ONE env shard")
+        self.check_training_state(ts)
+        self.env.load_state_dict(ts["env"])
+        resume.restore(ts["last_obs"], self._last_obs)
+        resume.restore(ts, {"cur_reward_sum": self.cur_reward_sum, "cur_episode_length": self.cur_episode_length, "ep_stats": self._ep_stats})
+        self.tot_timesteps, self.tot_time = int(ts["tot_timesteps"]), float(ts["tot_time"])
+        self._rollouts_done = int(ts["rollouts_done"])            # paces update_start_sampling (NOT the gate of the first graph capture)
+        self.current_learning_iteration = int(ts["next_iteration"])
+        self._resume_in_loop = ts["resume_point"] == "in_loop"
+        self._load_extra_training_state(ts["agent"])
+        rng_state.restore_globals(ts["rng"], self.device)
+
+    def _with_training_state(self, ckpt):
+        """save(): the reference's dictionary, + ONE key "training_state" when algo.config.save_training_state is true"""
+        if self.config.get("save_training_state", False):
+            ckpt["training_state"] = self.training_state()
+        return ckpt
+
+    def _restore_training_state(self, ckpt):
+        """load(), after the weights and the optimiser: the file's training state, unless algo.config.load_training_state is false"""
+        ts = ckpt.get("training_state", None)
+        if ts is not None and self.config.get("load_training_state", True) is not False:
+            self.load_training_state(ts)
 
     def _compute_returns(self, last_obs_dict, last_values=None):
         """mh_ppo.py:348-395 / ppo_mimic.py:443-491 in one HIP pass over the [T,N,R] slab."""

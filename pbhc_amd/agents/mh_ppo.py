@@ -138,17 +138,18 @@ class MHPPO(OnDeviceAgent):
             self.set_learning_rate(float(d["actor_optimizer_state_dict"]["param_groups"][0]["lr"]),
                                    float(d["critic_optimizer_state_dict"]["param_groups"][0]["lr"]))
         self.current_learning_iteration = d["iter"]
+        self._restore_training_state(d)
         return d["infos"]
 
     def save(self, path, infos=None):
-        torch.save({
+        torch.save(self._with_training_state({
             "actor_model_state_dict": self.actor.state_dict(),
             "critic_model_state_dict": self.critic.state_dict(),
             "actor_optimizer_state_dict": self.actor_optimizer.state_dict(),
             "critic_optimizer_state_dict": self.critic_optimizer.state_dict(),
             "iter": self.current_learning_iteration,
             "infos": infos,
-        }, path)
+        }), path)
 
     def set_learning_rate(self, actor_learning_rate, critic_learning_rate):
         self.actor_learning_rate, self.critic_learning_rate = actor_learning_rate, critic_learning_rate

@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib
 from .. import dist as pdist
+from ..utils import resume
 from . import fused_mlp, rollout
 from .agent_modules import Actor, ActorCritic
 from .base import FlatAdamView, OnDeviceAgent, _load_checkpoint, switch_on
@@ -188,11 +189,29 @@ class PPO(OnDeviceAgent):
             self.learning_rate = d["optimizer_state_dict"]["param_groups"][0]["lr"]
             self.set_learning_rate(self.learning_rate)
         self.current_learning_iteration = d["iter"]
+        self._restore_training_state(d)
         return d["infos"]
 
     def save(self, path, infos=None):
-        torch.save({"model_state_dict": self.alg.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        torch.save(self._with_training_state({"model_state_dict": self.alg.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
+                                              "iter": self.current_learning_iteration, "infos": infos}), path)
+
+    def _extra_training_state(self):
+        """`counter` (it drives the priv_reg_coef schedule) and what the reference's dictionary leaves out of the second optimiser: the history
+        encoder's Adam moments, its step count and its learning rate (`hist_encoder_optimizer` is in no checkpoint entry)"""
+        o = self._o_hist
+        return {"counter": int(self.counter), "hist_exp_avg": self._mflat[1][o:].clone(), "hist_exp_avg_sq": self._vflat[1][o:].clone(),
+                "hist_adam_step": self._adam_step[1:2].clone(), "hist_lr": self._lr_hist.clone()}
+
+    def _check_extra_training_state(self, extra):
+        o = self._o_hist
+        resume.check_tensors("PPO.load_training_state", extra, {"hist_exp_avg": self._mflat[1][o:], "hist_exp_avg_sq": self._vflat[1][o:]})
+
+    def _load_extra_training_state(self, extra):
+        o = self._o_hist
+        self.counter = int(extra["counter"])
+        resume.restore(extra, {"hist_exp_avg": self._mflat[1][o:], "hist_exp_avg_sq": self._vflat[1][o:], "hist_adam_step": self._adam_step[1:2],
+                               "hist_lr": self._lr_hist})
 
     def set_learning_rate(self, learning_rate):
         self.learning_rate = learning_rate

@@ -285,7 +285,7 @@ def collect(agent, d, obs_dict):
                 if use_br:
                     cur.wait_stream(br)
 
-            graph_ok = (switch_on("PBHC_ROLLOUT_GRAPH") and split and d.graph_allowed() and agent.__dict__.get("_rollouts_done", 0) >= 1
+            graph_ok = (switch_on("PBHC_ROLLOUT_GRAPH") and split and d.graph_allowed() and agent.__dict__.get("_rollouts_here", 0) >= 1
                         and not agent.__dict__.get("_rollout_graph_failed", False) and hasattr(env, "rollout_graph_safe") and env.rollout_graph_safe(T))
             ran = False
             if graph_ok:
@@ -321,7 +321,10 @@ def collect(agent, d, obs_dict):
             st.rewards.addcmul_(st.values, agent._time_outs.to(torch.float32), value=gamma)
             last_values = vals[T]
         st.step = T
+        # two counts, equal in a run that never resumes: `_rollouts_done` paces update_start_sampling and is part of the training state
+        # (exact resume); `_rollouts_here` says "the loop has run eagerly once in THIS process" (the gate of the first capture) and is not
         agent._rollouts_done = agent.__dict__.get("_rollouts_done", 0) + 1
+        agent._rollouts_here = agent.__dict__.get("_rollouts_here", 0) + 1
         if agent._dp and agent._stat_mode == "rollout":
             env.sync_globals()                     # sigma / curricula / log means: the mean over the ranks, once per rollout
         so = getattr(env, "_start", None)          # start_sampling: the fold (outside the graph: an all-reduce under data parallelism)

@@ -46,6 +46,8 @@ class LeggedRobotGeneralTracking(LeggedRobotMotionTracking):
         self._redraw_start_times()                   # start_sampling: the buffered start times belong to the old table's clip lengths
         self.reset_all()
 
+    _STATE_HOST = LeggedRobotMotionTracking._STATE_HOST + ("motion_start_idx",)      # exact resume: next_task()'s position in the library
+
     def read_log(self):
         out = super().read_log()
         g = self.globals.cpu().numpy()

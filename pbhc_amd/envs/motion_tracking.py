@@ -24,6 +24,7 @@ import torch
 from .. import _lib
 from .. import dist as pdist
 from ..motion_lib import MotionLib
+from ..utils import resume, rng_state
 from . import env_config
 
 K = _lib.K
@@ -1230,6 +1231,90 @@ class LeggedRobotMotionTracking:
         host = torch.stack([out["success"].double().sum() / M] + [torch.nan_to_num(x).sum() / scored.sum() for x in err]).cpu().tolist()
         out.update(success_rate=host[0], E_gmpbpe_mean=host[1], E_mpbpe_mean=host[2], E_mpjpe_mean=host[3], unfinished=unfinished, waves=waves, steps=steps)
         return out
+
+    # ---- exact resume (DESIGN.md §8 "Exact resume") -------------------------------------------
+    _STATE_TENSORS = ("globals", "actions", "last_actions", "actions_after_delay", "action_queue", "action_delay_idx", "last_dof_pos", "last_dof_vel",
+                      "torques", "feet_air_time", "contacts", "contacts_filt", "last_contacts", "last_contacts_filt", "_kp_scale", "_kd_scale",
+                      "_rfi_lim_scale", "_rao_scale", "default_dof_pos", "motion_start_times", "motion_len", "end_time_ratio_buf", "_episode_sums",
+                      "_episode_rew_out", "_hist", "_episode_length_buf", "last_episode_length_buf", "reset_buf", "time_out_buf", "rew_buf",
+                      "_ref_time", "_ou_state", "_start_time", "_start_window", "_clip_window")
+    _STATE_HOST = ("common_step_counter", "_clip_draws", "_start_redraws")
+
+    def _state_tensors(self):
+        return {k: getattr(self, k) for k in self._STATE_TENSORS}
+
+    def config_fingerprint(self):
+        """the env's resolved config as text without addresses (utils/resume.py) + the motion table's clip count and frame counts: checked,
+        not restored, by load_state_dict — with `_seed`, the step's Philox key, among its members"""
+        ml = self._motion_lib
+        return resume.config_fingerprint(self._c, ml._num_unique_motions, ml.clip_frame_counts())
+
+    def _state_dict_refusal(self):
+        """why the env's state cannot be saved now, or None — host-side state only"""
+        if getattr(self, "_rec", None) is not None and not self._rec_dumped:
+            return "an evaluation recording is running (env.config.save_motion): its buffers and counters are not part of the state"
+        if self._start_suspended:
+            return "library_sweep() is running: the slot -> clip table and every env are the sweep's, not the training run's"
+        if torch.cuda.is_current_stream_capturing():
+            return "called inside a stream capture"
+        return None
+
+    def state_dict(self):
+        """Everything that decides how this env goes on, as copies: the `_STATE_TENSORS`, the host counters, the re-draw schedule, the
+        generator of ranks > 0, the simulator's and the motion library's state.  Waits for the last step's reduction; draws from no
+        generator, launches nothing that writes state and leaves every captured graph valid."""
+        why = self._state_dict_refusal()
+        if why is not None:
+            raise _lib.PbhcError("state_dict: " + why)
+        self.wait_finalize()
+        self._flush_statistics()
+        sd = resume.snapshot(self._state_tensors())
+        sd.update({k: int(getattr(self, k)) for k in self._STATE_HOST})
+        sd.update(version=resume.STATE_VERSION, num_envs=int(self.num_envs), seed=int(self._seed), fingerprint=self.config_fingerprint(),
+                  reinit_counter=float(self._reinit.counter), is_evaluating=bool(self._is_evaluating),
+                  gen=None if self._gen is None else rng_state.pack_torch(self._gen.get_state()),
+                  simulator=self.simulator.state_dict(), motion_lib=self._motion_lib.state_dict())
+        return sd
+
+    def check_state_dict(self, sd):
+        """everything `load_state_dict` would refuse, without writing anything: another version, num_envs, Philox key or config, a tensor
+        of another shape, a replay cursor outside the current window"""
+        what = f"{type(self).__name__}.load_state_dict"
+        resume.check_version(sd, what)
+        resume.check_equal(what, "num_envs", int(sd["num_envs"]), int(self.num_envs))
+        resume.check_equal(what, "the env's Philox key `_seed` (seed torch with the saving run's config.seed before building the env)",
+                           int(sd["seed"]), int(self._seed))
+        resume.check_fingerprint(what, sd["fingerprint"], self.config_fingerprint())
+        resume.check_tensors(what, sd, self._state_tensors())
+        if (sd["gen"] is None) != (self._gen is None):
+            raise _lib.PbhcError(f"{what}: the env's host generator differs: the saved state has {'none' if sd['gen'] is None else 'one'}, this "
+                                 f"run has {'none' if self._gen is None else 'one'} (another rank?)")
+        self.simulator.check_state_dict(sd["simulator"])
+        self._motion_lib.check_state_dict(sd["motion_lib"])
+
+    def load_state_dict(self, sd):
+        """Restore what `state_dict()` saved, every tensor in place (the step's io struct, the riders and the captured graphs hold the
+        addresses).  The caller has built this env as the saving run did — the same config, torch seeded the same way — and has set the
+        replay window the saving run had; a mismatch raises PbhcError naming what differs and both values, before anything is written."""
+        why = self._state_dict_refusal()
+        if why is not None:
+            raise _lib.PbhcError("load_state_dict: " + why)
+        self.check_state_dict(sd)
+        self.wait_finalize()
+        self._flush_statistics()
+        resume.restore(sd, self._state_tensors())
+        for k in self._STATE_HOST:
+            setattr(self, k, int(sd[k]))
+        self._reinit.counter = float(sd["reinit_counter"])
+        self.is_evaluating = bool(sd["is_evaluating"])
+        if self._gen is not None:
+            self._gen.set_state(rng_state.unpack_torch(sd["gen"]))
+        self.simulator.load_state_dict(sd["simulator"])
+        self._motion_lib.load_state_dict(sd["motion_lib"])
+        self.curr_motion_ids = self._motion_lib.slot_clip
+        self._ref_bodies = None                      # the lazy members of a step this process never ran
+        self.extras.invalidate()
+        self.extras["episode"] = EpisodeExtras(self)
 
     # ---- logging: device-side means, read back on demand (no per-step sync) ----------------
     def read_log(self):

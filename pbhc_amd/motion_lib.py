@@ -25,7 +25,7 @@ from . import _lib, motion_ingest
 from .motion_augment import Augmentation, mirror_tables
 from .motion_interp import Interpolation
 from .motion_screen import ContactDetection, Screening
-from .utils import safe_pkl
+from .utils import resume, rng_state, safe_pkl
 
 
 def load_motion_file(path):
@@ -374,6 +374,53 @@ class MotionLib:
                                               None if reset_buf is None else _lib.ptr(reset_buf), None, self.num_envs, M, K, int(seed), counter_ptr,
                                               int(salt) & 0xFFFFFFFF, _lib.ptr(start_time), _lib.current_stream() if stream is None else stream),
                    "pbhc_start_draw")
+
+    # ---- exact resume: the slot -> clip table with its crops, the sampling hooks, the start-time tables -----------------
+    def _state_tensors(self):
+        return {"slot_clip": self.slot_clip, "_sampling_prob": self._sampling_prob, "_termination_history": self._termination_history,
+                "_success_rate": self._success_rate, "_sampling_history": self._sampling_history, "_start_visits": self._start_visits,
+                "_start_failures": self._start_failures, "_start_prob": self._start_prob, "_start_cdf": self._start_cdf}
+
+    def clip_frame_counts(self):
+        """the frame count of every clip as the tables hold it (host list; one device -> host copy on first use)"""
+        if getattr(self, "_clip_frames", None) is None:
+            self._clip_frames = [int(r[0].shape[0]) for r in self._raw] if self.max_len > 0 else [int(f) for f in self.num_frames.tolist()]
+        return self._clip_frames
+
+    def state_dict(self):
+        """What a resumed run needs of the library, as copies.  The built tables are a function of the config and are not saved; the
+        per-slot crop tables are rebuilt from the saved crop starts."""
+        sd = resume.snapshot(self._state_tensors())
+        sd["_sampling_cdf"] = None if self._sampling_cdf is None else self._sampling_cdf.clone()
+        sd["crop_starts"] = self.crop_starts.clone() if self.max_len > 0 else None
+        pyrand = getattr(self, "pyrand", None)
+        sd.update(version=resume.STATE_VERSION, num_envs=int(self.num_envs), num_clips=int(self._num_unique_motions), max_len=int(self.max_len),
+                  pyrand=None if pyrand is None else rng_state.pack_python(pyrand.getstate()))
+        return sd
+
+    def check_state_dict(self, sd):
+        """everything `load_state_dict` would refuse, without writing anything"""
+        what = "MotionLib.load_state_dict"
+        resume.check_version(sd, what)
+        for k, here in (("num_envs", int(self.num_envs)), ("num_clips", int(self._num_unique_motions)), ("max_len", int(self.max_len))):
+            resume.check_equal(what, k, int(sd[k]), here)
+        resume.check_tensors(what, sd, self._state_tensors())
+        if self.max_len > 0:
+            resume.check_tensors(what, sd, {"crop_starts": self.crop_starts})
+        if (sd["pyrand"] is None) != (getattr(self, "pyrand", None) is None):
+            raise _lib.PbhcError(f"{what}: pyrand differs: the saved state has {'none' if sd['pyrand'] is None else 'a generator state'}, this "
+                                 f"run has {'none' if getattr(self, 'pyrand', None) is None else 'a generator'} (another rank?)")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        resume.restore(sd, self._state_tensors())
+        if sd["_sampling_cdf"] is not None:
+            self._cdf().copy_(sd["_sampling_cdf"].to(self.device))
+        self._curr_motion_ids = self.slot_clip
+        if self.max_len > 0:
+            self._build_slot_crops(sd["crop_starts"].cpu())         # (fixed starts: nothing is drawn)
+        if sd["pyrand"] is not None:
+            self.pyrand.setstate(rng_state.unpack_python(sd["pyrand"]))
 
     def built_clip(self, clip_id):
         """clip `clip_id` of the library as a host clip dict: the source clip itself without `augmentation`, else that variant (with the

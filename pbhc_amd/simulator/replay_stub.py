@@ -17,6 +17,7 @@ import torch
 from .. import _lib
 from .. import dist as pdist
 from ..skeleton import Skeleton
+from ..utils import resume
 
 
 class ReplaySimStub:
@@ -167,6 +168,39 @@ class ReplaySimStub:
         self.frame_cursor.copy_((self.frame_cursor + 1) % self.replay_len)
         self._host_frame = (k + 1) % self.replay_len
         return k
+
+    # ---- exact resume: the robot state, the per-env DR draws and the replay cursor ---------------------------------------
+    def _state_tensors(self):
+        return {"all_root_states": self.all_root_states, "dof_state": self.dof_state, "_base_com_bias": self._base_com_bias,
+                "_link_mass_scale": self._link_mass_scale, "_base_mass_scale": self._base_mass_scale, "friction_coeffs": self.friction_coeffs,
+                "frame_cursor": self.frame_cursor}
+
+    def state_dict(self):
+        """What a resumed run needs of the simulator, as copies.  The replay window itself is the caller's: they set the same window before
+        `load_state_dict`, which restores the cursor into it."""
+        sd = resume.snapshot(self._state_tensors())
+        sd.update(version=resume.STATE_VERSION, num_envs=int(self.num_envs), replay_len=int(self.replay_len) if self.replay is not None else 1,
+                  _host_frame=int(self._host_frame), _frame=int(self._frame), _substep=int(self._substep))
+        return sd
+
+    def check_state_dict(self, sd):
+        """everything `load_state_dict` would refuse, without writing anything"""
+        what = "ReplaySimStub.load_state_dict"
+        resume.check_version(sd, what)
+        resume.check_equal(what, "num_envs", sd["num_envs"], int(self.num_envs))
+        resume.check_tensors(what, sd, self._state_tensors())
+        n = int(self.replay_len) if self.replay is not None else 1
+        resume.check_equal(what, "the replay window's length (set the window the saving run had before loading)", int(sd["replay_len"]), n)
+        cur = int(sd["frame_cursor"].item())
+        if not 0 <= cur < n or not -1 <= int(sd["_host_frame"]) < n:
+            raise _lib.PbhcError(f"{what}: the saved replay cursor {cur} (host mirror {int(sd['_host_frame'])}) lies outside the current window of {n} frames")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        resume.restore(sd, self._state_tensors())
+        self._host_frame, self._frame, self._substep = int(sd["_host_frame"]), int(sd["_frame"]), int(sd["_substep"])
+        # the lazy rigid-body state / contact forces: those of the frame before the restored cursor, the one the saving run's last step consumed
+        self._pending = None if self.replay is None else (self.replay, -1)
 
     # ---- rigid-body state / contact forces of the simulator surface (reference names, isaacgym.py:574-618) -----------------------------
     # Nothing on the training path reads them, so the fused step does not store them (9.4 MB per step at 4096 envs): the env tells the stub
