@@ -815,6 +815,14 @@ int pbhc_linear_act_fwd_out(const float* x, const float* w, const float* bias, f
 int pbhc_linear_act_fwd_out_pair(const float* x0, const float* w0, const float* bias0, float* y0, float* pre0, int M0, int N0, int K0, int act0, const float* w_out0,
                                  const float* b_out0, int NO0, float* out0, const float* x1, const float* w1, const float* bias1, float* y1, float* pre1, int M1,
                                  int N1, int K1, int act1, const float* w_out1, const float* b_out1, int NO1, float* out1, void* stream);
+/* pbhc_linear_act_fwd for TWO wide layers in one launch: two problems that the single entry each runs on 64 x 128 tiles of the LDS-DMA kernel
+ * share a grid (the problem with more tile work takes the leading workgroups); y / pre are bit for bit the single call's, no output layer rides.
+ * pbhc_linear_act_fwd_pairable(M, N, K): 1 if pbhc_linear_act_fwd itself runs the problem on those tiles — its own tile choice or a shape
+ * forced with pbhc_gemm_debug_force_shape, K >= 4, no measurement setting active — else 0.  The pair entry refuses (PBHC_EINVAL, nothing
+ * launched) unless that holds for BOTH problems, so pairing never changes the tiles a layer runs on.  The two M need not be equal. */
+int pbhc_linear_act_fwd_pairable(int M, int N, int K);
+int pbhc_linear_act_fwd_pair(const float* x0, const float* w0, const float* bias0, float* y0, float* pre0, int M0, int N0, int K0, int act0, const float* x1,
+                             const float* w1, const float* bias1, float* y1, float* pre1, int M1, int N1, int K1, int act1, void* stream);
 /* The same with row strides and a batch: batch b computes y[b] = act(x[b] . w^T + bias) with x[b] = x + b * x_batch_stride (rows lda floats
  * apart, lda >= K), y[b] = y + b * y_batch_stride (rows ldc floats apart, ldc >= N), one weight matrix for all — e.g. the L output positions of
  * nn.Conv1d(C -> O, kernel k, stride s) on time-major activations [B, T, C] (encoder_modules.py:60-107): window l is the [B, k*C] matrix at

@@ -105,7 +105,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
            "pbhc_motion_extend_batch", "pbhc_motion_augment_batch", "pbhc_motion_screen_frames", "pbhc_motion_screen_clips",
            "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
-           "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable"]
+           "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
+           "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair"]
 
 
 class PbhcError(RuntimeError):
@@ -174,6 +175,8 @@ def _load():
     lib.pbhc_linear_act_fwd_out_pair.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp] * 2 + [vp]
     lib.pbhc_linear_dgrad_act_pairable.argtypes = [i, i, i]
     lib.pbhc_linear_dgrad_act_pair.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i] * 2 + [vp]
+    lib.pbhc_linear_act_fwd_pairable.argtypes = [i, i, i]
+    lib.pbhc_linear_act_fwd_pair.argtypes = [vp, vp, vp, vp, vp, i, i, i, i] * 2 + [vp]
     lib.pbhc_gemm_debug_force_shape.argtypes = [i]
     lib.pbhc_debug_out_bwd_variant.argtypes = [i]
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]

@@ -17,9 +17,10 @@ MI355X:
 * every fused backward ends in ONE finishing launch (`pbhc_colsum_final`: bias gradients, the output layer's weight gradient, split-K partials);
   an owner that brackets several stacks' backwards with begin_deferred_finish() / finish_deferred() gets one for all of them, and may hand
   finish_deferred() the second stage of its loss (`pbhc_colsum_final_ppo_reduce`: one more workgroup of that launch, not a launch of its own).
-  MHPPO's optimiser step is then 20 launches: 5 forward (the two stacks' 128-column layers, with their output layers, share ONE — forward_pair),
-  the loss's first stage, per stack the output layer's one-pass backward + 3 weight-gradient GEMMs and the wide layer's input gradient, ONE
-  input-gradient launch for both 128-column layers, the finishing launch, gradient norm, Adam (per stack, PBHC_PAIR_TAILS=0: 22).
+  MHPPO's optimiser step is then 18 launches: 3 forward (each layer of the two stacks shares ONE launch — forward_pair: the wide layers on
+  64 x 128 tiles, the 128-column layers with their output layers on 32 x 128), the loss's first stage, per stack the output layer's one-pass
+  backward + 3 weight-gradient GEMMs and the wide layer's input gradient, ONE input-gradient launch for both 128-column layers, the finishing
+  launch, gradient norm, Adam (PBHC_PAIR_WIDE=0: 20, the wide layers' forwards per stack; PBHC_PAIR_TAILS=0: 22, everything per stack).
 Same arithmetic as autograd's (the column sums are two-stage fp32 in a fixed order); pinned by the update-parity tests.
 """
 from __future__ import annotations
@@ -153,16 +154,21 @@ def finish_deferred(reduce=None):
 
 
 # ---- launches two stacks can share ---------------------------------------------------------------------------------------------------------
-# _FusedMLP's forward and backward are generators (_fwd_steps / _bwd_steps) that yield the GEMM launches of a stack's 128-wide tail as requests:
+# _FusedMLP's forward and backward are generators (_fwd_steps / _bwd_steps) that yield the GEMM launches of a stack's hidden layers as requests:
+#   "fwd"      (x, w, bias, y, pre, M, N, K, act)                                          pbhc_linear_act_fwd
 #   "fwd_out"  (x, w, bias, y, pre, M, N, K, act, w_out, b_out, NO, out)                   pbhc_linear_act_fwd_out
 #   "dgrad"    (dy, w, saved, dx, scratch, M, N, K, act)                       -> rows     pbhc_linear_dgrad_act
-# Each of these is one to four rounds of 32-row tiles with a short K loop — prologue-, epilogue- and ramp-bound — and the actor's and the
-# critic's use the same kernel instantiation: _run_joint issues such a pair as ONE launch (`*_pair`: the same tile code on a shared grid,
-# bit for bit the same results).  Pairing never changes the tile shape a layer runs on — the column-sum partials, and with them the bias
-# gradients, depend on the tile height — so a pair is formed only where both single entries would choose 32 x 128 tiles themselves.
+# The 128-wide tail's are one to four rounds of 32-row tiles with a short K loop — prologue-, epilogue- and ramp-bound — and the wide layers'
+# forwards are launches that each fill and drain the chip; the actor's and the critic's use the same kernel instantiation: _run_joint issues
+# such a pair as ONE launch (`*_pair`: the same tile code on a shared grid, bit for bit the same results).  Pairing never changes the tile shape a layer
+# runs on — the column-sum partials, and with them the bias gradients, depend on the tile height — so a pair is formed only where both single
+# entries would choose the pair kernel's tiles themselves: 32 x 128 (_issue_pair) or 64 x 128 (_issue_pair_wide).
 def _issue(kind, a):
     """one request through its own entry -> number of partial rows (None for the forward)"""
     lib, st = _lib.lib(), _lib.current_stream()
+    if kind == "fwd":
+        _lib.check(lib.pbhc_linear_act_fwd(*a, st), "pbhc_linear_act_fwd")
+        return None
     if kind == "fwd_out":
         _lib.check(lib.pbhc_linear_act_fwd_out(*a, st), "pbhc_linear_act_fwd_out")
         return None
@@ -172,13 +178,24 @@ def _issue(kind, a):
 
 
 def _pairable(kind, a):
-    """would the single entry run this request on the 32-row tiles the pair kernels are built for?  The tile-choice rule lives in ONE place,
-    csrc/pbhc_gemm.hip (pick_shape): the forward yields "fwd_out" only under the condition on which it calls that entry at all (an entry
-    that always runs 32 x 128 tiles), and for the input gradient the library is asked."""
+    """would the single entry run this request on the 32-row tiles the tail pair kernels are built for?  The tile-choice rule lives in ONE
+    place, csrc/pbhc_gemm.hip (pick_shape): the forward yields "fwd_out" only under the condition on which it calls that entry at all (an
+    entry that always runs 32 x 128 tiles), and for the input gradient the library is asked."""
     if kind == "fwd_out":
         return True
+    if kind == "fwd":
+        return False
     M, N, K = a[5], a[6], a[7]
     return bool(_lib.lib().pbhc_linear_dgrad_act_pairable(M, N, K))
+
+
+def _pairable_wide(kind, a):
+    """would the single entry run this request — a hidden layer's forward — on 64 x 128 tiles of the LDS-DMA kernel (the library's answer,
+    as above)?  The wide layers' input gradients are not paired: built, bit for bit, and measured slower (profiles/update_paired_wide.txt)."""
+    if kind != "fwd":
+        return False
+    M, N, K = a[5], a[6], a[7]
+    return bool(_lib.lib().pbhc_linear_act_fwd_pairable(M, N, K))
 
 
 def _issue_pair(kind, a0, a1):
@@ -191,6 +208,13 @@ def _issue_pair(kind, a0, a1):
     return nb0.value, nb1.value
 
 
+def _issue_pair_wide(kind, a0, a1):
+    """two "fwd" requests of wide layers as one launch on 64 x 128 tiles"""
+    assert kind == "fwd"
+    _lib.check(_lib.lib().pbhc_linear_act_fwd_pair(*a0, *a1, _lib.current_stream()), "pbhc_linear_act_fwd_pair")
+    return None, None
+
+
 def _run_single(gen):
     """run a _fwd_steps / _bwd_steps generator to its end, every request through its own entry -> the generator's result"""
     try:
@@ -201,10 +225,12 @@ def _run_single(gen):
         return e.value
 
 
-def _run_joint(g0, g1):
-    """Two stacks' generators side by side: each runs to its first request (g0, then g1: a stack's own launches keep their order); where both
-    ask for the same pairable launch it is issued once for both, else each request through its own entry; then each generator runs to its
-    end alone, g0 first.  -> (result of g0, result of g1)"""
+def _run_joint(g0, g1, wide=True, formed=None):
+    """Two stacks' generators side by side over all their requests.  A stack runs ahead, every request through its own entry, until it
+    holds one that a pair kernel could take (g0 first: a stack's own launches keep their order, and where nothing pairs the launch order is
+    that of two separate applications); while both hold such a request of the same kind it is issued once for both — the tails on 32-row
+    tiles, and with `wide` the wide layers on 64-row tiles (their kinds are appended to `formed`) — else each through its own entry, a
+    hidden layer's "fwd" before the other stack's tail.  -> (result of g0, result of g1)"""
     gens, res = (g0, g1), [None, None]
 
     def step(j, reply=None, first=False):                  # -> the generator's next request, or None once it has returned (result kept)
@@ -214,16 +240,40 @@ def _run_joint(g0, g1):
             res[j] = e.value
             return None
 
-    r0, r1 = step(0, first=True), step(1, first=True)
-    if r0 is not None and r1 is not None and r0[0] == r1[0] and _pairable(*r0) and _pairable(*r1):
-        replies = _issue_pair(r0[0], r0[1], r1[1])
-    else:
-        replies = [None if r is None else _issue(*r) for r in (r0, r1)]
-    for j, r in enumerate((r0, r1)):
-        if r is not None:
-            r = step(j, replies[j])
-        while r is not None:
-            r = step(j, _issue(*r))
+    def candidate(req):                                    # the pair kernel that could take this request: "tail", "wide" or None
+        if _pairable(*req):
+            return "tail"
+        return "wide" if wide and _pairable_wide(*req) else None
+
+    FIRST, HELD, DONE = object(), object(), object()
+    # todo[j]: the reply generator j is waiting for (HELD: its request has not been issued yet; DONE: it has returned)
+    r, c, todo = [None, None], [None, None], [FIRST, FIRST]
+    while todo[0] is not DONE or todo[1] is not DONE:
+        for j in (0, 1):                                   # g0 takes its reply and runs ahead to its next candidate (or its end) before g1 moves
+            if todo[j] is DONE or todo[j] is HELD:
+                continue
+            r[j] = step(j, first=True) if todo[j] is FIRST else step(j, todo[j])
+            while r[j] is not None:
+                c[j] = candidate(r[j])
+                if c[j] is not None:
+                    break
+                r[j] = step(j, _issue(*r[j]))
+            if r[j] is None:
+                todo[j] = DONE
+        live = [j for j in (0, 1) if todo[j] is not DONE]
+        if len(live) == 2 and r[0][0] == r[1][0] and c[0] == c[1]:
+            if c[0] == "tail":
+                todo[0], todo[1] = _issue_pair(r[0][0], r[0][1], r[1][1])
+            else:
+                todo[0], todo[1] = _issue_pair_wide(r[0][0], r[0][1], r[1][1])
+                if formed is not None:
+                    formed.append(r[0][0])
+        else:
+            if len(live) == 2 and (r[0][0] == "fwd") != (r[1][0] == "fwd"):      # the other stack's tail request waits for its partner
+                live = [j for j in live if r[j][0] == "fwd"]
+            for j in (0, 1):
+                if todo[j] is not DONE:
+                    todo[j] = _issue(*r[j]) if j in live else HELD
     return res[0], res[1]
 
 
@@ -233,17 +283,18 @@ class _Sub:
 
 
 class _FusedMLPPair(torch.autograd.Function):
-    """Two independent stacks (MHPPO's actor and critic) in one application, so that the launches of their 128-wide tails can be paired:
-    forward  stack 0's and stack 1's wide layers, then ONE launch for both tails (last hidden layer + output layer);
+    """Two independent stacks (MHPPO's actor and critic) in one application, so that their launches can be paired:
+    forward  ONE launch for both stacks' first layers, one for their second (`wide`: 64 x 128 tiles), ONE for both tails (last hidden layer
+    + output layer);
     backward each stack's output-layer backward and library weight gradient of the 128-wide layer, ONE launch for both input gradients of
     that layer, then each stack's remaining chain as in _FusedMLP.  Same kernels on the same tiles: every result is bit for bit what two
-    _FusedMLP applications give."""
+    _FusedMLP applications give.  `formed`: a list that receives the kinds of the wide pairs issued."""
 
     @staticmethod
-    def forward(ctx, x0, x1, seq0, seq1, *params):
+    def forward(ctx, x0, x1, seq0, seq1, wide, formed, *params):
         s0, s1 = _Sub(), _Sub()
-        (out0, saved0), (out1, saved1) = _run_joint(_FusedMLP._fwd_steps(s0, x0, seq0), _FusedMLP._fwd_steps(s1, x1, seq1))
-        ctx.subs, ctx.nsaved0 = (s0, s1), len(saved0)
+        (out0, saved0), (out1, saved1) = _run_joint(_FusedMLP._fwd_steps(s0, x0, seq0), _FusedMLP._fwd_steps(s1, x1, seq1), wide, formed)
+        ctx.subs, ctx.nsaved0, ctx.wide, ctx.formed = (s0, s1), len(saved0), wide, formed
         ctx.save_for_backward(*saved0, *saved1)
         return out0, out1
 
@@ -253,15 +304,17 @@ class _FusedMLPPair(torch.autograd.Function):
         saved = ctx.saved_tensors
         # (stack 1 leads, as autograd runs the later of two separate nodes first)
         (dx1, flat1), (dx0, flat0) = _run_joint(_FusedMLP._bwd_steps(s1, saved[ctx.nsaved0:], dout1, ctx.needs_input_grad[1]),
-                                                _FusedMLP._bwd_steps(s0, saved[:ctx.nsaved0], dout0, ctx.needs_input_grad[0]))
-        return (dx0, dx1, None, None, *flat0, *flat1)
+                                                _FusedMLP._bwd_steps(s0, saved[:ctx.nsaved0], dout0, ctx.needs_input_grad[0]), ctx.wide, ctx.formed)
+        return (dx0, dx1, None, None, None, None, *flat0, *flat1)
 
 
-def forward_pair(seq0, x0, seq1, x1):
+def forward_pair(seq0, x0, seq1, x1, wide=True, formed=None):
     """(seq0(x0), seq1(x1)) as ONE autograd node with the two stacks' 128-wide tails in paired launches, or None — nothing launched —
     where that does not apply and the caller applies each stack on its own: both must be fused ELU / ReLU stacks that store their
     gradients in place (grad_direct, no other live application), end in Linear(K, 128) - act - Linear(128, <= 32), and the rows must be
-    in the range where 32 x 128 tiles are chosen for both layers of every pair."""
+    in the range where 32 x 128 tiles are chosen for both layers of every pair.  wide: also pair the wide layers' launches wherever both
+    stacks' run on 64 x 128 tiles (asked per launch: the hidden layers' forwards); formed: a list that receives the kinds of those pairs
+    ("fwd") as they are issued."""
     if not (FUSED_GEMM and FWD_OUT and OUT_BWD and torch.is_grad_enabled()):
         return None
     B = x0.shape[0]
@@ -277,7 +330,7 @@ def forward_pair(seq0, x0, seq1, x1):
             return None
         for l in lin:
             params += [l.weight, l.bias]
-    return _FusedMLPPair.apply(x0, x1, seq0, seq1, *params)
+    return _FusedMLPPair.apply(x0, x1, seq0, seq1, bool(wide), formed, *params)
 
 
 class _FusedMLP(torch.autograd.Function):
@@ -294,8 +347,8 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def _fwd_steps(ctx, x, seq):
-        """The forward as a generator: it launches everything itself except the launches a second stack's could share a grid with, which it
-        YIELDS as (kind, arguments) requests — `_run_single` issues each through its own entry, `_run_joint` pairs two stacks' requests.
+        """The forward as a generator: it launches everything itself except the hidden layers' GEMMs — launches a second stack's could share a
+        grid with — which it YIELDS as (kind, arguments) requests — `_run_single` issues each through its own entry, `_run_joint` pairs two stacks' requests.
         `ctx`: any object (the autograd context, or a stack's `_Sub` of a joint one).  Returns (output, tensors to save)."""
         lin = [m for m in seq if isinstance(m, nn.Linear)]
         act = _ACT_ID[type(seq[1])] if len(lin) > 1 else 0
@@ -324,8 +377,8 @@ class _FusedMLP(torch.autograd.Function):
                     h = z
                     saved_act.append(pre if pre is not None else h)
                     continue
-                _lib.check(lib.pbhc_linear_act_fwd(h.data_ptr(), l.weight.data_ptr(), l.bias.data_ptr() if l.bias is not None else None, z.data_ptr(),
-                                                   pre.data_ptr() if pre is not None else None, B, l.out_features, l.in_features, act, st), "pbhc_linear_act_fwd")
+                yield ("fwd", (h.data_ptr(), l.weight.data_ptr(), l.bias.data_ptr() if l.bias is not None else None, z.data_ptr(),
+                               pre.data_ptr() if pre is not None else None, B, l.out_features, l.in_features, act))
                 h = z
                 saved_act.append(pre if pre is not None else h)
                 continue

@@ -261,11 +261,13 @@ class MHPPO(OnDeviceAgent):
         # One stream for both networks: with the critic on a stream of its own the update measured 37.0 ms against 34.5 ms (MI355X, 4096 envs) —
         # the wide GEMMs are tuned to own the chip and lose more than the narrow ones gain.
         # Both stacks as one autograd node where their 128-wide tails can share launches (fused_mlp.forward_pair; PBHC_PAIR_TAILS=0: never),
-        # else each on its own; `_update_form` says which.
+        # else each on its own; `_update_form` says which.  The paired form also pairs the wide layers' forwards where both stacks' run on
+        # 64 x 128 tiles (PBHC_PAIR_WIDE=0: never); `_update_pairs` lists the kinds of those pairs this step issued.
         am, cm = self.actor.actor_module, self.critic.critic_module
         pair = None
+        self._update_pairs = []
         if switch_on("PBHC_PAIR_TAILS") and am._fused and cm._fused:
-            pair = fused_mlp.forward_pair(am.module, b["actor_obs"], cm.module, b["critic_obs"])
+            pair = fused_mlp.forward_pair(am.module, b["actor_obs"], cm.module, b["critic_obs"], wide=switch_on("PBHC_PAIR_WIDE"), formed=self._update_pairs)
         self._update_form = "per-stack" if pair is None else "paired"
         mu, value = pair if pair is not None else (am(b["actor_obs"]), cm(b["critic_obs"]))
         B = mu.shape[0]

@@ -1038,15 +1038,19 @@ int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, f
 
 }  // extern "C"
 
-// ---- two problems on 32 x 128 tiles in one launch (k_gemm2_pair) ----
-template <int MODE>
+// ---- two problems on 32 x 128 (TM 1) or 64 x 128 (TM 2) tiles in one launch (k_gemm2_pair) ----
+template <int MODE, int TM>
 static hipError_t gemm2_pair_launch(const Gemm2Args& p0, const Gemm2Args& p1, bool swap, hipStream_t st) {
-  constexpr int LDS_BYTES = gemm2_lds_bytes<MODE, 1, 4, 1, 1, 32, 2>();
+  constexpr int BM = 32 * TM;
+  constexpr int LDS_BYTES = gemm2_lds_bytes<MODE, 1, 4, TM, 1, 32, 2>();      // 40 960 B / 49 152 B: k_gemm2's, four / three workgroups per CU
   static_assert(LDS_BYTES <= 65536, "no attribute to set");
   const Gemm2Args& a = swap ? p1 : p0;                     // the larger problem (the longer K / the wider N) goes first in the grid: its tiles start first
   const Gemm2Args& b = swap ? p0 : p1;
-  const int na = ((a.M + 31) / 32) * a.tiles_n, nb = ((b.M + 31) / 32) * b.tiles_n;
-  hipLaunchKernelGGL((k_gemm2_pair<MODE, 1, 4, 1, 1, 32, 2>), dim3(na + nb), dim3(GEMM_T), LDS_BYTES, st, a, b, na);
+  // The tile code's XCD remap runs over a problem's own workgroups and takes local workgroup 0 to sit on XCD 0: true for the second problem
+  // when na % 8 == 0 (every shipped pair).  For other na the remap still runs and the second problem's tiles lose that locality; results
+  // do not depend on which workgroup computes a tile.
+  const int na = ((a.M + BM - 1) / BM) * a.tiles_n, nb = ((b.M + BM - 1) / BM) * b.tiles_n;
+  hipLaunchKernelGGL((k_gemm2_pair<MODE, 1, 4, TM, 1, 32, 2>), dim3(na + nb), dim3(GEMM_T), LDS_BYTES, st, a, b, na);
   return hipGetLastError();
 }
 static int fwd_out_check(const float* x, const float* w, const float* y, int M, int N, int K, int act, const float* w_out, int NO, const float* out) {
@@ -1079,7 +1083,7 @@ int pbhc_linear_act_fwd_out_pair(const float* x0, const float* w0, const float* 
   }
   const Gemm2Args p0{x0, w0, bias0, nullptr, y0, pre0, nullptr, M0, N0, K0, act0, 1, 0, K0, N0, GemmOutLayer{w_out0, b_out0, out0, NO0}};
   const Gemm2Args p1{x1, w1, bias1, nullptr, y1, pre1, nullptr, M1, N1, K1, act1, 1, 0, K1, N1, GemmOutLayer{w_out1, b_out1, out1, NO1}};
-  GEMM_HIP(gemm2_pair_launch<0>(p0, p1, K1 > K0, (hipStream_t)stream));
+  GEMM_HIP((gemm2_pair_launch<0, 1>(p0, p1, K1 > K0, (hipStream_t)stream)));
   return PBHC_OK;
 }
 
@@ -1095,7 +1099,30 @@ int pbhc_linear_dgrad_act_pair(const float* dy0, const float* w0, const float* s
   const GemmOutLayer none{nullptr, nullptr, nullptr, 0};
   const Gemm2Args p0{dy0, w0, nullptr, saved0, dx0, nullptr, scratch0, M0, N0, K0, act0, (N0 + 127) / 128, 0, K0, N0, none};
   const Gemm2Args p1{dy1, w1, nullptr, saved1, dx1, nullptr, scratch1, M1, N1, K1, act1, (N1 + 127) / 128, 0, K1, N1, none};
-  GEMM_HIP(gemm2_pair_launch<1>(p0, p1, (size_t)N1 * K1 > (size_t)N0 * K0, (hipStream_t)stream));
+  GEMM_HIP((gemm2_pair_launch<1, 1>(p0, p1, (size_t)N1 * K1 > (size_t)N0 * K0, (hipStream_t)stream)));
+  return PBHC_OK;
+}
+
+// ---- the wide layers' forward pair: two problems that pbhc_linear_act_fwd would each run on 64 x 128 tiles of the LDS-DMA kernel ----
+int pbhc_linear_act_fwd_pairable(int M, int N, int K) {
+  // 1 exactly when pbhc_linear_act_fwd itself launches k_gemm2<0, 1, 4, 2, 1, 32, 2>: pick_shape() says 2 (a forced shape counts: it is what
+  // the single entry runs), gemm_variant's v2ok holds and no diagnosis setting is active
+  if (M < 1 || N < 1 || K < 1 || g_variant != 0 || g_dbg != 0) return 0;
+  const bool v2ok = K >= 4 && (size_t)M * K < (1u << 30) && (size_t)N * K < (1u << 30);
+  return v2ok && pick_shape(M, N, K, g_force_shape, true) == 2;
+}
+
+int pbhc_linear_act_fwd_pair(const float* x0, const float* w0, const float* bias0, float* y0, float* pre0, int M0, int N0, int K0, int act0, const float* x1,
+                             const float* w1, const float* bias1, float* y1, float* pre1, int M1, int N1, int K1, int act1, void* stream) {
+  GEMM_ARG(x0 && w0 && y0 && M0 >= 1 && N0 >= 1 && K0 >= 1 && act0 >= 0 && act0 <= 3 && ((uintptr_t)x0 & 3) == 0 && ((uintptr_t)w0 & 3) == 0);
+  GEMM_ARG(x1 && w1 && y1 && M1 >= 1 && N1 >= 1 && K1 >= 1 && act1 >= 0 && act1 <= 3 && ((uintptr_t)x1 & 3) == 0 && ((uintptr_t)w1 & 3) == 0);
+  GEMM_ARG(pbhc_linear_act_fwd_pairable(M0, N0, K0) && pbhc_linear_act_fwd_pairable(M1, N1, K1));
+  const GemmOutLayer none{nullptr, nullptr, nullptr, 0};
+  const int tn0 = (N0 + 127) / 128, tn1 = (N1 + 127) / 128;
+  const Gemm2Args p0{x0, w0, bias0, nullptr, y0, pre0, nullptr, M0, N0, K0, act0, tn0, 0, K0, N0, none};
+  const Gemm2Args p1{x1, w1, bias1, nullptr, y1, pre1, nullptr, M1, N1, K1, act1, tn1, 0, K1, N1, none};
+  const size_t work0 = (size_t)((M0 + 63) / 64) * tn0 * K0, work1 = (size_t)((M1 + 63) / 64) * tn1 * K1;
+  GEMM_HIP((gemm2_pair_launch<0, 2>(p0, p1, work1 > work0, (hipStream_t)stream)));
   return PBHC_OK;
 }
 
