@@ -968,6 +968,37 @@ typedef struct PbhcGatherJob {
 } PbhcGatherJob;
 int pbhc_gather_rows(const PbhcGatherJob* jobs, int num_jobs, const int64_t* index, int nrows, void* stream);
 
+/* The left <-> right mirror of observation / action rows (algo.config.symmetry; the tables: pbhc_amd/envs/obs_mirror.py) for several tensors in ONE
+ * launch: dst_j[r * dst_pitch + c] = sign_j[c] * src_j[r * src_pitch + index_j[c]] for every job j, row r < nrows and column c < width.  index /
+ * sign: device arrays of `width` entries, index values in [0, width) (larger ones are read as width - 1).  dst_pitch >= width: a job may write the
+ * observation columns of an assembled first-layer input in place; the columns beyond `width` are not touched.  src and dst must not overlap.
+ * f32 only; a sign flip and a copy, so bit-exact.  NULL pointers, width < 1 or > PBHC_MIRROR_MAX_WIDTH, a pitch below the width, nrows < 1 or more
+ * than PBHC_MAX_MIRROR_JOBS jobs return PBHC_EINVAL without a launch. */
+#define PBHC_MAX_MIRROR_JOBS 8
+#define PBHC_MIRROR_MAX_WIDTH 4096
+typedef struct PbhcMirrorJob {
+  const float* src;
+  float* dst;
+  const int32_t* index;
+  const float* sign;
+  int32_t width;
+  int32_t src_pitch;
+  int32_t dst_pitch;
+} PbhcMirrorJob;
+int pbhc_mirror_rows(const PbhcMirrorJob* jobs, int num_jobs, int nrows, void* stream);
+/* The mirror-symmetry term of the policy mean with a detached target (rsl_rl's form), mu / mu_m / grad_mu_m [B, A] contiguous, A <= PBHC_MAX_DOF:
+ *   target[b, a] = act_sign[a] * mu[b, act_index[a]]          L = coef * mean over the B A elements of (mu_m - target)^2
+ *   grad_mu_m = dL / dmu_m = (2 coef / (B A)) (mu_m - target)  (nothing flows into mu)
+ * scalar_out[0] = L; acc_out (may be NULL): acc_out[0] += L.  The sum runs in two stages in a fixed order without atomics — thread t of block g adds up
+ * its elements (g + i * blocks) * PBHC_SYM_THREADS + t for i = 0, 1, ..., blocks = min(ceil(B A / (PBHC_SYM_THREADS * PBHC_SYM_ELEMS)),
+ * PBHC_SYM_MAX_BLOCKS); a block sums its threads by a 6-level butterfly per wave and then the waves in order; one block of PBHC_SYM_MAX_BLOCKS threads
+ * sums the block partials the same way — so two runs agree bit for bit.  scratch: PBHC_SYM_MAX_BLOCKS floats. */
+#define PBHC_SYM_THREADS 256
+#define PBHC_SYM_ELEMS 4
+#define PBHC_SYM_MAX_BLOCKS 512
+int pbhc_symmetry_loss(const float* mu, const float* mu_m, const int32_t* act_index, const float* act_sign, int B, int A, float coef, float* grad_mu_m,
+                       float* scratch, float* scalar_out, float* acc_out, void* stream);
+
 /* nn.utils.clip_grad_norm_(max_norm) + torch.optim.Adam.step() (mh_ppo.py:519-524; weight_decay > 0: torch.optim.AdamW, decoupled,
  * ppo_mimic.py:184-190,682-686) over ONE flat fp32 segment of n
  * parameters (param/grad/exp_avg/exp_avg_sq flat views; lr and step are device scalars, step is incremented).

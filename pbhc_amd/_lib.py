@@ -91,6 +91,7 @@ PbhcPpoReduce = _S["PbhcPpoReduce"]
 PbhcMotionExtend = _S["PbhcMotionExtend"]
 PbhcMotionAugment = _S["PbhcMotionAugment"]
 PbhcMotionScreen = _S["PbhcMotionScreen"]
+PbhcMirrorJob = _S["PbhcMirrorJob"]
 
 EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
            "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
@@ -106,7 +107,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_motion_extend_batch", "pbhc_motion_augment_batch", "pbhc_motion_screen_frames", "pbhc_motion_screen_clips",
            "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
            "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
-           "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair"]
+           "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair",
+           "pbhc_mirror_rows", "pbhc_symmetry_loss"]
 
 
 class PbhcError(RuntimeError):
@@ -180,6 +182,8 @@ def _load():
     lib.pbhc_gemm_debug_force_shape.argtypes = [i]
     lib.pbhc_debug_out_bwd_variant.argtypes = [i]
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]
+    lib.pbhc_mirror_rows.argtypes = [C.POINTER(PbhcMirrorJob), i, i, vp]
+    lib.pbhc_symmetry_loss.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp]
     lib.pbhc_debug_out_bwd_variant.restype = None
     lib.pbhc_linear_wgrad_parts.argtypes = [i, i, i]
     lib.pbhc_linear_act_fwd_strided.argtypes = [vp, i, C.c_longlong, vp, vp, vp, vp, i, C.c_longlong, i, i, i, i, i, vp]

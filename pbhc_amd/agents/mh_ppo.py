@@ -38,6 +38,10 @@ class MHPPO(OnDeviceAgent):
         self.actor_learning_rate = c.actor_learning_rate
         self.critic_learning_rate = c.critic_learning_rate
         self.cfg_l2c2 = c.l2c2 if "l2c2" in c else None
+        sym = c.get("symmetry", None)
+        if sym is not None and sym.get("enable", False):
+            raise NotImplementedError("algo.config.symmetry.enable with MHPPO: the mirror-symmetry term belongs to the general-tracking agent "
+                                      "(ppo_mimic.PPO) — a v1 library is one clip and has no mirrored variant to tie the policy to")
 
     # ------------------------------------------------------------------------------------
     def _setup_models_and_optimizer(self):

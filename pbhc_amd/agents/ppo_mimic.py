@@ -45,6 +45,7 @@ class PPO(OnDeviceAgent):
         self.counter = 0
         self.train_distill = c.get("teacher_model_path", None) is not None
         self.dagger_only = bool(c.get("dagger_only", False))
+        self._init_symmetry(c.get("symmetry", None))
         if self.dagger_only != self.train_distill:
             # the reference: distillation without dagger_only raises NotImplementedError in _update_distill (ppo_mimic.py:724);
             # dagger_only without a teacher stores no values/log-probs and fails in _update_ppo
@@ -55,6 +56,25 @@ class PPO(OnDeviceAgent):
             raise NotImplementedError("MoEMLP actors/critics")
         self.dagger_update_freq = c.get("dagger_update_freq", 20)
         self.hist_encoding = False
+
+    def _init_symmetry(self, sym):
+        """algo.config.symmetry: {enable, coef} — the mirror-symmetry term of the RL update: coef * mean (mu(M_o o) - M_a sg(mu(o)))^2.
+        Absent or `enable: false`: the update is the one without it, launch for launch."""
+        self.symmetry = bool(sym is not None and sym.get("enable", False))
+        self.symmetry_coef = float(sym.get("coef", 1.0)) if self.symmetry else 0.0
+        if not self.symmetry:
+            return
+        if self.train_distill or self.dagger_only:
+            raise NotImplementedError("algo.config.symmetry.enable with dagger_only / teacher_model_path: the distillation update regresses the student "
+                                      "onto the teacher's actions and has no PPO step the symmetry term could join")
+        lib_ = getattr(self.env, "_motion_lib", None)
+        aug = getattr(lib_, "augmentation", None)
+        if aug is None or not aug.mirror:
+            raise _lib.PbhcError("algo.config.symmetry.enable needs robot.motion.augmentation.mirror: without mirrored variants in the library the "
+                                 "policy never tracks the references the term would tie it to")
+        if not hasattr(self.env, "mirror_rows"):
+            raise _lib.PbhcError("algo.config.symmetry.enable needs the general-tracking env (env.mirror_maps / env.mirror_rows)")
+        self.env.mirror_maps()                      # refuses here, by name, what has no mirror
 
     def _preprocess_teacher_config(self):
         """ppo_mimic.py:121-145: the teacher's actor / future-target observation groups are added to the env under `teacher_*` names and
@@ -171,6 +191,11 @@ class PPO(OnDeviceAgent):
         # ppo_mimic.py:206-216: the future targets of all S steps in one row
         self._obs_width = {k: d * S if k in ("future_motion_targets", "teacher_future_motion_targets") else d for k, d in self.algo_obs_dim_dict.items()}
         self._register_storage(self._obs_width, {"teacher_actions": self.num_act} if self.train_distill else {})
+        if self.symmetry:
+            dev, A = self.device, self.num_act
+            self._grad_mu_m = torch.zeros(self._mb, A, device=dev)
+            self._sym_scratch = torch.zeros(_lib.K["PBHC_SYM_MAX_BLOCKS"], device=dev)
+            self._sym_scalar = torch.zeros(1, device=dev)
 
     def _eval_mode(self):
         self.alg.eval()
@@ -325,6 +350,46 @@ class PPO(OnDeviceAgent):
         bufs[1][:, wa:wa + wp].copy_(po)
         shuffled["_xin_actor"], shuffled["_xin_critic"] = bufs
 
+    MIRRORED_KEYS = ("actor_obs", "future_motion_targets", "priv_obs")
+
+    def _on_gather(self, shuffled):
+        self._assemble_inputs(shuffled)
+        if self.symmetry:
+            self._mirror_inputs(shuffled)
+
+    def _mirror_inputs(self, shuffled):
+        """once per update, on the shuffled [T * N, C] tensors: ONE launch mirrors the three groups the actor reads on the RL path.  The mirrored
+        actor_obs goes straight into the observation columns of a second assembled actor input (`_xin_actor_m`: both applications of the actor
+        stack are alive until the backward, so they cannot share one); without assembled inputs, into a plain tensor for `apply_cat`."""
+        bufs = self.__dict__.get("_mirrored")
+        rows = shuffled["actor_obs"].shape[0]
+        dev = shuffled["actor_obs"].device
+        if bufs is None or bufs["future_motion_targets"].shape[0] != rows:
+            bufs = self._mirrored = {k: torch.empty(rows, shuffled[k].shape[1], device=dev) for k in self.MIRRORED_KEYS[1:]}
+        jobs = [(k, shuffled[k], bufs[k]) for k in self.MIRRORED_KEYS[1:]]
+        if "_xin_actor" in shuffled:
+            xm = self.__dict__.get("_xin_m")
+            if xm is None or xm.shape != shuffled["_xin_actor"].shape:
+                xm = self._xin_m = torch.empty_like(shuffled["_xin_actor"])
+            jobs.append(("actor_obs", shuffled["actor_obs"], xm))
+            shuffled["_xin_actor_m"] = xm
+        else:
+            if "actor_obs" not in bufs or bufs["actor_obs"].shape[0] != rows:
+                bufs["actor_obs"] = torch.empty(rows, shuffled["actor_obs"].shape[1], device=dev)
+            jobs.append(("actor_obs", shuffled["actor_obs"], bufs["actor_obs"]))
+            shuffled["_m_actor_obs"] = bufs["actor_obs"]
+        self.env.mirror_rows(jobs)
+        shuffled["_m_future_motion_targets"], shuffled["_m_priv_obs"] = bufs["future_motion_targets"], bufs["priv_obs"]
+
+    def _forward_mirrored(self, b):
+        """mu of the SAME actor on the mirrored inputs (motion encoder, privileged encoder, actor stack): the second live application of each"""
+        a = self.alg.actor
+        emb = a.motion_encoding(b["_m_future_motion_targets"])
+        latent = a.priv_encoding(b["_m_priv_obs"])
+        if "_xin_actor_m" in b:
+            return apply_into(a.actor_module, b["_xin_actor_m"], b["actor_obs"].shape[1], [emb, latent])
+        return apply_cat(a.actor_module, b["_m_actor_obs"], torch.cat([emb, latent], dim=-1))
+
     def _rollout_step(self, obs_dict):
         """ppo_mimic.py:371-438 through agents/rollout.py.  Per control step: encoders + actor (+ critic) forward, sampling, the fused env step,
         ONE bootstrap/done/episode-stat kernel.  The MLP stacks (actor, critic, privileged encoder; PBHC_STACK_NETS_V2=0: none) run as ONE launch
@@ -386,14 +451,20 @@ class PPO(OnDeviceAgent):
 
     METERS = ["Value", "Entropy", "Surrogate", "priv_reg_loss", "Actor_Load_Balancing_Loss", "Critic_Load_Balancing_Loss"]
 
+    def _meter_names(self):
+        """the meters an optimiser step adds to, then the two load-balancing meters (they stay zero: no mixture-of-experts stacks here);
+        "Symmetry" exists only while algo.config.symmetry is on"""
+        return self.METERS if not self.symmetry else self.METERS[:4] + ["Symmetry"] + self.METERS[4:]
+
     def _training_step(self, indices=None):
-        meters, loss = self._begin_meters(self.METERS, summed=4)      # (the two load-balancing meters stay zero: no mixture-of-experts stacks here)
+        names = self._meter_names()
+        meters, loss = self._begin_meters(names, summed=len(names) - 2)
         for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, keys=self.UPDATE_KEYS, indices=indices,
-                                                       on_gather=self._assemble_inputs):
+                                                       on_gather=self._on_gather):
             self._update_ppo(batch, loss)
         self.update_counter()
         self.learning_rate = self._lr[0:1]
-        return self._end_meters(self.METERS, meters, loss)
+        return self._end_meters(names, meters, loss)
 
     def _training_step_dagger(self, indices=None):
         loss = {"hist_latent_loss": torch.zeros((), device=self.device)}
@@ -414,6 +485,7 @@ class PPO(OnDeviceAgent):
         lib = _lib.lib()
         alg = self.alg
         mu, value, priv_latent = self._forward(b, hist_encoding=False)
+        mu_m = self._forward_mirrored(b) if self.symmetry else None
         with torch.no_grad():
             hist_latent = alg.actor.history_encoding(b["prop_history"])
         priv_reg = (priv_latent - hist_latent).norm(p=2, dim=1).mean()
@@ -435,6 +507,14 @@ class PPO(OnDeviceAgent):
                                      self._grad_mu.data_ptr(), self._grad_value.data_ptr(), self._g_sigma.data_ptr(), self._loss_scalars.data_ptr(),
                                      loss["_acc"].data_ptr() if "_acc" in loss else None, self._lr.data_ptr(), self._loss_scratch.data_ptr(), st), "pbhc_ppo_loss")
         heads, grads = [mu, value], [self._grad_mu, self._grad_value]
+        if mu_m is not None:
+            # the target M_a mu is detached: the gradient reaches the weights through the mirrored application only, and `_grad_mu` stays the PPO one
+            index, sign = self.env.mirror_maps()["actions"]
+            _lib.check(lib.pbhc_symmetry_loss(mu.data_ptr(), mu_m.data_ptr(), index.data_ptr(), sign.data_ptr(), B, self.num_act, self.symmetry_coef,
+                                              self._grad_mu_m.data_ptr(), self._sym_scratch.data_ptr(), self._sym_scalar.data_ptr(),
+                                              loss["Symmetry"].data_ptr() if "Symmetry" in loss else None, st), "pbhc_symmetry_loss")
+            heads.append(mu_m)
+            grads.append(self._grad_mu_m)
         if coef != 0.0:
             heads.append(priv_reg * coef)
             grads.append(torch.ones((), device=self.device))

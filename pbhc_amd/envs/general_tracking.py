@@ -46,6 +46,69 @@ class LeggedRobotGeneralTracking(LeggedRobotMotionTracking):
         self._redraw_start_times()                   # start_sampling: the buffered start times belong to the old table's clip lengths
         self.reset_all()
 
+    # ---- the left <-> right mirror of observations and actions (algo.config.symmetry) ----------------------------------------
+    def rebuild_observations(self):
+        super().rebuild_observations()
+        self._mirror_maps = None                    # the groups changed: the maps are rebuilt on their next use
+
+    def mirror_maps(self):
+        """{group: (index int32[C], sign float32[C])} for every observation group, plus "actions", as device tensors:
+        `mirrored[j] = sign[j] * x[index[j]]` (envs/obs_mirror.py).  Built on first use and again after rebuild_observations()."""
+        maps = self.__dict__.get("_mirror_maps")
+        if maps is None:
+            from . import obs_mirror
+            from .motion_tracking import _TopView
+
+            aug = getattr(self._motion_lib, "augmentation", None)
+            host = obs_mirror.build(_TopView(self.config), self.skeleton, aug.symmetry_tol if aug is not None else 1e-4)
+            maps = self._mirror_maps = {g: (torch.from_numpy(i).to(self.device), torch.from_numpy(s).to(self.device)) for g, (i, s) in host.items()}
+        return maps
+
+    def mirror_rows(self, jobs):
+        """ONE `pbhc_mirror_rows` launch for [(group, x [rows, C] float32, out [rows, >= C])]: out[:, :C] = the mirror of x; the rows of x and of
+        out may be padded (unit inner stride), and out may be a wider tensor whose leading C columns are written in place.
+        No out may share memory with an x of the same call: refused."""
+        maps = self.mirror_maps()
+        arr = (_lib.PbhcMirrorJob * len(jobs))()
+        rows = jobs[0][1].shape[0]
+        for q, (group, x, out) in zip(arr, jobs):
+            index, sign = maps[group]
+            C_ = index.numel()
+            _lib.require_gpu_rows(x, f"mirror_rows[{group}] x", torch.float32, (rows, C_))
+            _lib.require_gpu_rows(out, f"mirror_rows[{group}] out", torch.float32)
+            if out.shape[0] != rows or out.shape[1] < C_:
+                raise _lib.PbhcError(f"mirror_rows[{group}] out: expected [{rows}, >= {C_}], got {tuple(out.shape)}")
+            if C_ > K["PBHC_MIRROR_MAX_WIDTH"]:
+                raise _lib.PbhcError(f"mirror_rows[{group}]: {C_} columns, at most {K['PBHC_MIRROR_MAX_WIDTH']}")
+            q.src, q.dst, q.index, q.sign = x.data_ptr(), out.data_ptr(), index.data_ptr(), sign.data_ptr()
+            q.width, q.src_pitch, q.dst_pitch = C_, x.stride(0), out.stride(0)
+        # the kernel gathers while other lanes and rows store: no destination of the launch may share memory with a source of it
+        span = lambda t, w: (t.data_ptr(), t.data_ptr() + 4 * ((rows - 1) * t.stride(0) + w))
+        for gd, _, out in jobs:
+            d0, d1 = span(out, maps[gd][0].numel())
+            for gs, x, _ in jobs:
+                s0, s1 = span(x, maps[gs][0].numel())
+                if d0 < s1 and s0 < d1:
+                    raise _lib.PbhcError(f"mirror_rows[{gd}] out overlaps the source of [{gs}]: the mirror cannot run in place")
+        _lib.check(self._lib.pbhc_mirror_rows(arr, len(jobs), rows, _lib.current_stream()), "pbhc_mirror_rows")
+
+    def mirror_observation(self, group, x, out=None):
+        """the mirror image of observation rows x [rows, C] of `group` (float32, device) -> out (a new tensor unless given; it must not
+        share memory with x)"""
+        if group not in self.mirror_maps() or group == "actions":
+            raise _lib.PbhcError(f"mirror_observation: {group!r} is not an observation group ({[g for g in self.mirror_maps() if g != 'actions']})")
+        if out is None:
+            out = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+        self.mirror_rows([(group, x, out)])
+        return out
+
+    def mirror_action(self, a, out=None):
+        """the mirror image of action rows a [rows, num_actions] -> out (a new tensor unless given; it must not share memory with a)"""
+        if out is None:
+            out = torch.empty(a.shape[0], a.shape[1], dtype=torch.float32, device=a.device)
+        self.mirror_rows([("actions", a, out)])
+        return out
+
     _STATE_HOST = LeggedRobotMotionTracking._STATE_HOST + ("motion_start_idx",)      # exact resume: next_task()'s position in the library
 
     def read_log(self):
