@@ -795,6 +795,34 @@ typedef struct PbhcPpoReduce {
   float entropy_coef, desired_kl;
 } PbhcPpoReduce;
 int pbhc_colsum_final_ppo_reduce(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, void* stream);
+/* pbhc_colsum_final_ppo_reduce that also leaves the sum of squares of the gradients, so that the optimiser pass needs no norm pass of its own
+ * (pbhc_adam_clip2_parts below).  Outputs are bit for bit those of pbhc_colsum_final (jobs) + pbhc_colsum_final_ppo_reduce (red).
+ * Up to two flat gradient segments (actor, critic; n == 0: unused).  Every workgroup adds, in double, the squares of the floats it stores and
+ * writes that ONE sum to its own slot of seg[s].part, s = the segment that contains the job's `out` (in no segment: no slot; straddling a
+ * segment's end: PBHC_EINVAL); workgroup 0 does the same for grad_std and advances step[0] and step[1] by one (as pbhc_adam_clip2's norm
+ * pass does).  range_off / range_len: the parts of the segment that NO job of this call (nor grad_std) writes, in floats from `base`,
+ * ascending and disjoint — the caller's statement; rider workgroups of the launch square them, PBHC_SQ_RANGE_FLOATS per workgroup (4-byte
+ * alignment is enough).  Slots per segment, in order: grad_std, the jobs' workgroups in job order, the riders; every slot is written exactly
+ * once per call, nothing needs zeroing.  num_jobs <= PBHC_SQ_MAX_JOBS (both exports): each PBHC_MAX_COLSUM_JOBS jobs are a launch, the slots are numbered across
+ * them, the last launch carries `red` and the riders.  pbhc_colsum_final_ppo_reduce_sqnorm_slots: slots[s] = the slot count of segment s for
+ * the same arguments (launches nothing; part may be NULL and part_cap 0 there); part_cap (doubles) must be at least that.
+ * The sum of a segment's slots is ||g||^2 in a fixed order, reproducible run to run, but grouped differently from pbhc_adam_clip2's strided
+ * norm pass: the float norm can land on the adjacent float of that one's. */
+#define PBHC_SQ_MAX_RANGES 16
+#define PBHC_SQ_MAX_JOBS 256
+#define PBHC_SQ_RANGE_FLOATS 4096
+typedef struct PbhcSqSegment {
+  const float* base;           /* the segment's gradients */
+  double* part;                /* part_cap doubles */
+  int32_t n, part_cap, num_ranges;
+  int32_t range_off[PBHC_SQ_MAX_RANGES], range_len[PBHC_SQ_MAX_RANGES];
+} PbhcSqSegment;
+typedef struct PbhcSqnorm {
+  PbhcSqSegment seg[2];
+  float* step;                 /* float[2] */
+} PbhcSqnorm;
+int pbhc_colsum_final_ppo_reduce_sqnorm(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq, void* stream);
+int pbhc_colsum_final_ppo_reduce_sqnorm_slots(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq, int32_t* slots);
 
 
 /* One Linear of a training-time Linear / activation stack on the fp32 matrix cores with its activation folded into the GEMM epilogue
@@ -1013,6 +1041,12 @@ int pbhc_adam_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
  * `optimizer.zero_grad()`, mh_ppo.py:513-514, done by the pass that read the gradients last: no fill launch of its own). */
 int pbhc_adam_clip2(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int n0, int n1, const float* lr, float* step, float max_norm, float beta1,
                     float beta2, float eps, float weight_decay, int zero_grad, double* scratch, float* norm_out, void* stream);
+/* pbhc_adam_clip2's optimiser pass ALONE, on norm partials that are already there: segment s is clipped by sqrt(sum of part_s[0 .. nparts_s)),
+ * summed as pbhc_adam_clip2 sums its own partials (same kernel, same arithmetic).  No norm pass, and `step` is NOT advanced: whoever left the
+ * partials has done that (pbhc_colsum_final_ppo_reduce_sqnorm).  nparts >= 1. */
+int pbhc_adam_clip2_parts(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int n0, int n1, const float* lr, const float* step, float max_norm,
+                          float beta1, float beta2, float eps, float weight_decay, int zero_grad, const double* part0, int nparts0, const double* part1,
+                          int nparts1, float* norm_out, void* stream);
 
 /* Test-only: the device functions of csrc/pbhc_math.h (the quaternion / rotation algebra every kernel inlines; SURVEY 8 row a1:
  * isaac_utils/rotations.py:28-669, utils/torch_utils.py:51-79,239-296) applied elementwise, so that they can be pinned directly against

@@ -88,6 +88,7 @@ PbhcMlpInput = _S["PbhcMlpInput"]
 PbhcRider = _S["PbhcRider"]
 PbhcConvEncoder = _S["PbhcConvEncoder"]
 PbhcPpoReduce = _S["PbhcPpoReduce"]
+PbhcSqnorm = _S["PbhcSqnorm"]
 PbhcMotionExtend = _S["PbhcMotionExtend"]
 PbhcMotionAugment = _S["PbhcMotionAugment"]
 PbhcMotionScreen = _S["PbhcMotionScreen"]
@@ -104,6 +105,7 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
            "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
            "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
+           "pbhc_colsum_final_ppo_reduce_sqnorm", "pbhc_colsum_final_ppo_reduce_sqnorm_slots", "pbhc_adam_clip2_parts",
            "pbhc_motion_extend_batch", "pbhc_motion_augment_batch", "pbhc_motion_screen_frames", "pbhc_motion_screen_clips",
            "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
            "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
@@ -171,6 +173,8 @@ def _load():
     lib.pbhc_linear_out_bwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
     lib.pbhc_ppo_loss_partials.argtypes = [vp] * 10 + [i, i, i, f, f, i, i, vp, vp, vp, C.POINTER(C.c_int), vp]
     lib.pbhc_colsum_final_ppo_reduce.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), vp]
+    lib.pbhc_colsum_final_ppo_reduce_sqnorm.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), C.POINTER(PbhcSqnorm), vp]
+    lib.pbhc_colsum_final_ppo_reduce_sqnorm_slots.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), C.POINTER(PbhcSqnorm), C.POINTER(C.c_int32)]
     lib.pbhc_linear_act_fwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
     lib.pbhc_linear_act_fwd_out.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp, vp]
     lib.pbhc_linear_dgrad_act.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i, vp]
@@ -207,6 +211,7 @@ def _load():
     lib.pbhc_gemm_debug_force_shape.restype = None
     lib.pbhc_adam_clip.argtypes = [vp, vp, vp, vp, i, vp, vp, f, f, f, f, f, vp, vp, vp]
     lib.pbhc_adam_clip2.argtypes = [vp, vp, vp, vp, i, i, vp, vp, f, f, f, f, f, i, vp, vp, vp]
+    lib.pbhc_adam_clip2_parts.argtypes = [vp, vp, vp, vp, i, i, vp, vp, f, f, f, f, f, i, vp, i, vp, i, vp, vp]
     lib.pbhc_policy_sample.argtypes = [vp, vp, vp, i, i, i, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     lib.pbhc_rollout_post.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp, vp]
     lib.pbhc_rollout_post2.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp, vp, vp]

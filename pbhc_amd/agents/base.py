@@ -18,7 +18,7 @@ from .modules import RolloutStorage
 # name -> default.  Read at the time of use, not at import: the tests flip them between two agents of one process.
 SWITCHES = {"PBHC_ROLLOUT_GRAPH": "1", "PBHC_ROLLOUT_SPLIT": "1", "PBHC_CRITIC_BATCHED": "1", "PBHC_FUSED_SAMPLE": "1", "PBHC_STACK_NETS": "actor",
             "PBHC_STACK_NETS_V2": "1", "PBHC_FWD_GRAPHS": "1", "PBHC_PERM_PREFETCH": "1", "PBHC_CHECK_GRAD_CLEAN": "0", "PBHC_ASSEMBLE_INPUTS": "1",
-            "PBHC_ROLLOUT_RIDERS": "1", "PBHC_PAIR_TAILS": "1", "PBHC_PAIR_WIDE": "1"}
+            "PBHC_ROLLOUT_RIDERS": "1", "PBHC_PAIR_TAILS": "1", "PBHC_PAIR_WIDE": "1", "PBHC_STEP_FINISH": "1"}
 
 
 def switch(name):

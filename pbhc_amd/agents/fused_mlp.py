@@ -17,10 +17,11 @@ MI355X:
 * every fused backward ends in ONE finishing launch (`pbhc_colsum_final`: bias gradients, the output layer's weight gradient, split-K partials);
   an owner that brackets several stacks' backwards with begin_deferred_finish() / finish_deferred() gets one for all of them, and may hand
   finish_deferred() the second stage of its loss (`pbhc_colsum_final_ppo_reduce`: one more workgroup of that launch, not a launch of its own).
-  MHPPO's optimiser step is then 18 launches: 3 forward (each layer of the two stacks shares ONE launch — forward_pair: the wide layers on
+  MHPPO's optimiser step is then 17 launches: 3 forward (each layer of the two stacks shares ONE launch — forward_pair: the wide layers on
   64 x 128 tiles, the 128-column layers with their output layers on 32 x 128), the loss's first stage, per stack the output layer's one-pass
   backward + 3 weight-gradient GEMMs and the wide layer's input gradient, ONE input-gradient launch for both 128-column layers, the finishing
-  launch, gradient norm, Adam (PBHC_PAIR_WIDE=0: 20, the wide layers' forwards per stack; PBHC_PAIR_TAILS=0: 22, everything per stack).
+  launch — which also leaves the gradient's sums of squares (finish_deferred(reduce, sqnorm=...)) — and Adam (PBHC_STEP_FINISH=0: 18, a
+  gradient-norm launch of its own; PBHC_PAIR_WIDE=0: 19, the wide layers' forwards per stack; PBHC_PAIR_TAILS=0: 21, everything per stack).
 Same arithmetic as autograd's (the column sums are two-stage fp32 in a fixed order); pinned by the update-parity tests.
 """
 from __future__ import annotations
@@ -86,6 +87,7 @@ def _wgrad(d, x, out, defer=None):
         if P > 0:
             scratch = torch.empty(P * n * k, device=d.device)
             _lib.check(lib.pbhc_linear_wgrad(d.data_ptr(), x.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, n, k, _lib.current_stream()), "pbhc_linear_wgrad")
+            LAUNCHES[0] += 1
             return out
     return _wgrad_library(d, x, out, defer)
 
@@ -104,12 +106,14 @@ def _wgrad_library(d, x, out, defer=None):
     P = 0 if n < 64 else 32 if nk <= 128 * 256 else 16 if nk <= 128 * 512 else 32 if nk <= 256 * 512 else 4 if nk <= 512 * 768 else 8
     if _WGRAD_P:                                       # measurement aid: PBHC_WGRAD_P="512x380:4,256x512:8"
         P = _WGRAD_P.get((n, k), P)
+    LAUNCHES[0] += 1
     if P == 0 or B % P or B // P < 256:
         return torch.mm(d.t(), x, out=out)
     part = torch.bmm(d.view(P, B // P, n).transpose(1, 2), x.view(P, B // P, k))
     if defer is not None and out.is_contiguous():
         defer.append((part, out))                          # summed by the caller's finishing launch (one launch for the whole backward
         return out                                         # instead of one torch.sum per layer: 5 x 6 us per optimiser step)
+    LAUNCHES[0] += 1
     return torch.sum(part, 0, out=out)
 
 
@@ -120,6 +124,10 @@ def _wgrad_library(d, x, out, defer=None):
 # the jobs read — to a pending list, and one launch per PBHC_MAX_COLSUM_JOBS jobs finishes them all.  Stacks that return gradients to autograd
 # finish at once as before (autograd may consume their outputs right after backward returns).
 _DEFER = {"on": False, "jobs": [], "keep": []}
+# launches issued by this module's training-time forward / backward (native entries and library GEMMs alike), for an owner that records
+# how many launches its optimiser step was (MHPPO._update_launches).  Bookkeeping kept by hand at the call sites, not read from the stream:
+# a launch added here must be counted here; the kernel traces under profiles/ are the measurement.
+LAUNCHES = [0]
 
 
 def begin_deferred_finish():
@@ -137,20 +145,106 @@ def _launch_jobs(job_list, st, reduce=None):
             j.part, j.out, j.num_row_blocks, j.n = part, out, nrb, n
         if reduce is not None and k + MAXJ >= len(job_list):
             _lib.check(lib.pbhc_colsum_final_ppo_reduce(jobs, len(chunk), C.byref(reduce), st), "pbhc_colsum_final_ppo_reduce")
+            LAUNCHES[0] += 1
         elif chunk:
             _lib.check(lib.pbhc_colsum_final(jobs, len(chunk), st), "pbhc_colsum_final")
+            LAUNCHES[0] += 1
 
 
-def finish_deferred(reduce=None):
+class StepSqnorm:
+    """An owner's description of its flat gradient buffer for finish_deferred(reduce, sqnorm=...): two consecutive segments (actor
+    [0, n0), critic [n0, n0 + n1) of `gflat`) and the two Adam step counters `step`.  The finishing launch then also leaves each segment's
+    sum of squares as per-workgroup partials (`pbhc_colsum_final_ppo_reduce_sqnorm`) and advances the counters, and the optimiser pass
+    needs no norm pass (`pbhc_adam_clip2_parts` on `plan.part_ptr` / `plan.nparts`).
+    What the jobs of a finish cover, the ranges they leave uncovered (direct `torch.mm` weight gradients at small minibatches: squared by
+    rider workgroups) and the slot counts depend only on where the jobs WRITE — (out, rows, n) per job, fixed `.grad` views — and are worked
+    out once per such signature and kept with the ctypes arrays; the scratch addresses the jobs READ are not part of the key (they are the
+    allocator's to choose) and are refreshed in the kept job array every step, which is the one loop `_launch_jobs` runs anyway.
+    `misses` counts the plans built: one per distinct signature."""
+
+    class Plan:
+        __slots__ = ("jobs", "num_jobs", "sq", "part", "part_ptr", "nparts")
+
+    def __init__(self, gflat, n0, n1, step):
+        self.gflat, self.n, self.step = gflat, (int(n0), int(n1)), step
+        self._plans = {}
+        self.misses = 0
+
+    def _uncovered(self, base, n, covered):
+        """the complement, in [0, n) floats from address `base`, of the (address, floats) intervals that lie in it -> [(off, len)]"""
+        iv = sorted(((a - base) // 4, (a - base) // 4 + k) for a, k in covered if base <= a < base + 4 * n)
+        out, at = [], 0
+        for lo, hi in iv:
+            if lo > at:
+                out.append((at, lo - at))
+            at = max(at, hi)
+        if at < n:
+            out.append((at, n - at))
+        return out
+
+    def plan(self, job_list, reduce):
+        """-> the Plan of this finish, or None where the export's range table is too small for it (the caller takes the norm pass)"""
+        key = (tuple(j[1:] for j in job_list), reduce.grad_std, reduce.A, self.gflat.data_ptr())
+        got = self._plans.get(key)
+        if got is not None:
+            if got:
+                for j, job in zip(got.jobs, job_list):
+                    j.part = job[0]
+            return got or None
+        self.misses += 1
+        if len(self._plans) >= 8:
+            self._plans.clear()
+        lib = _lib.lib()
+        covered = [(out, n) for _, out, _, n in job_list] + [(reduce.grad_std, reduce.A)]
+        sq = _lib.PbhcSqnorm()
+        sq.step = self.step.data_ptr()
+        base = self.gflat.data_ptr()
+        for s, n in enumerate(self.n):
+            ranges = self._uncovered(base, n, covered)
+            if len(ranges) > _lib.K["PBHC_SQ_MAX_RANGES"]:
+                self._plans[key] = False
+                return None
+            g = sq.seg[s]
+            g.base, g.n, g.num_ranges = base, n, len(ranges)
+            for r, (off, ln) in enumerate(ranges):
+                g.range_off[r], g.range_len[r] = off, ln
+            base += 4 * n
+        P = StepSqnorm.Plan()
+        P.num_jobs = len(job_list)
+        P.jobs = (_lib._S["PbhcColsumJob"] * max(P.num_jobs, 1))()
+        for j, (part, out, nrb, n) in zip(P.jobs, job_list):
+            j.part, j.out, j.num_row_blocks, j.n = part, out, nrb, n
+        slots = (C.c_int32 * 2)()
+        _lib.check(lib.pbhc_colsum_final_ppo_reduce_sqnorm_slots(P.jobs, P.num_jobs, C.byref(reduce), C.byref(sq), slots), "pbhc_colsum_final_ppo_reduce_sqnorm_slots")
+        P.nparts = (int(slots[0]), int(slots[1]))
+        P.part = torch.empty(P.nparts[0] + P.nparts[1], dtype=torch.float64, device=self.gflat.device)     # (every slot is written by every finish)
+        P.part_ptr = (P.part.data_ptr(), P.part.data_ptr() + 8 * P.nparts[0])
+        for s in (0, 1):
+            sq.seg[s].part, sq.seg[s].part_cap = P.part_ptr[s], P.nparts[s]
+        P.sq = sq
+        self._plans[key] = P
+        return P
+
+
+def finish_deferred(reduce=None, sqnorm=None):
     """launch what the backwards since begin_deferred_finish() left pending (current stream = the stream those backwards ran on).
     reduce: the owner's PbhcPpoReduce — the loss's second stage, whose results nothing reads before the optimiser pass, as one more
-    workgroup of this launch instead of a one-workgroup launch of its own between the loss and the backward"""
+    workgroup of this launch instead of a one-workgroup launch of its own between the loss and the backward.
+    sqnorm (with reduce): the owner's StepSqnorm — the launch also leaves the gradient's sums of squares and advances the Adam step counters.
+    -> the StepSqnorm.Plan that ran (its partials feed pbhc_adam_clip2_parts), or None: the finish ran without the squares"""
     _DEFER["on"] = False
     job_list, keep = _DEFER["jobs"], _DEFER["keep"]
     _DEFER["jobs"], _DEFER["keep"] = [], []
-    if job_list or reduce is not None:
+    plan = sqnorm.plan(job_list, reduce) if (sqnorm is not None and reduce is not None) else None
+    if plan is not None:
+        MAXJ = _lib.K["PBHC_MAX_COLSUM_JOBS"]
+        _lib.check(_lib.lib().pbhc_colsum_final_ppo_reduce_sqnorm(plan.jobs, plan.num_jobs, C.byref(reduce), C.byref(plan.sq), _lib.current_stream()),
+                   "pbhc_colsum_final_ppo_reduce_sqnorm")
+        LAUNCHES[0] += max(1, (plan.num_jobs + MAXJ - 1) // MAXJ)
+    elif job_list or reduce is not None:
         _launch_jobs(job_list, _lib.current_stream(), reduce)
     del keep
+    return plan
 
 
 # ---- launches two stacks can share ---------------------------------------------------------------------------------------------------------
@@ -166,6 +260,7 @@ def finish_deferred(reduce=None):
 def _issue(kind, a):
     """one request through its own entry -> number of partial rows (None for the forward)"""
     lib, st = _lib.lib(), _lib.current_stream()
+    LAUNCHES[0] += 1
     if kind == "fwd":
         _lib.check(lib.pbhc_linear_act_fwd(*a, st), "pbhc_linear_act_fwd")
         return None
@@ -200,6 +295,7 @@ def _pairable_wide(kind, a):
 
 def _issue_pair(kind, a0, a1):
     lib, st = _lib.lib(), _lib.current_stream()
+    LAUNCHES[0] += 1
     if kind == "fwd_out":
         _lib.check(lib.pbhc_linear_act_fwd_out_pair(*a0, *a1, st), "pbhc_linear_act_fwd_out_pair")
         return None, None
@@ -211,6 +307,7 @@ def _issue_pair(kind, a0, a1):
 def _issue_pair_wide(kind, a0, a1):
     """two "fwd" requests of wide layers as one launch on 64 x 128 tiles"""
     assert kind == "fwd"
+    LAUNCHES[0] += 1
     _lib.check(_lib.lib().pbhc_linear_act_fwd_pair(*a0, *a1, _lib.current_stream()), "pbhc_linear_act_fwd_pair")
     return None, None
 
@@ -383,6 +480,7 @@ class _FusedMLP(torch.autograd.Function):
                 saved_act.append(pre if pre is not None else h)
                 continue
             z = torch.addmm(l.bias, h, l.weight.t())
+            LAUNCHES[0] += 1 if (i == len(lin) - 1 or act == 0) else 2          # (the library GEMM, and the eager activation pass)
             if i == len(lin) - 1:
                 out = z
             elif act == 1:
@@ -468,6 +566,7 @@ class _FusedMLP(torch.autograd.Function):
                 _lib.check(lib.pbhc_linear_out_bwd(d.data_ptr(), ins[i].data_ptr(), None if below.data_ptr() == ins[i].data_ptr() else below.data_ptr(),
                                                    l.weight.data_ptr(), B, n, k_in, ctx.act, dn.data_ptr(), part_dw.data_ptr(), part.data_ptr(),
                                                    scratch[offs[i - 1]:].data_ptr(), C.byref(nb), st), "pbhc_linear_out_bwd")
+                LAUNCHES[0] += 1
                 jobs.append((part.data_ptr(), gb.data_ptr(), nb.value, n))
                 jobs.append((part_dw.data_ptr(), gw.data_ptr(), nb.value, n * k_in))
                 keep += [part_dw, gw, gb]
@@ -478,6 +577,7 @@ class _FusedMLP(torch.autograd.Function):
             if not have_partials:
                 _lib.check(lib.pbhc_act_bwd_partials(d.data_ptr(), acts[i].data_ptr() if i < L - 1 else None, B, n, ctx.act if i < L - 1 else 0, d.data_ptr(),
                                                      part.data_ptr(), C.byref(nb), st), "pbhc_act_bwd_partials")
+                LAUNCHES[0] += 1
             jobs.append((part.data_ptr(), gb.data_ptr(), nb.value, n))
             keep.append(gb)
             room = deferred
@@ -496,6 +596,7 @@ class _FusedMLP(torch.autograd.Function):
                 d = dn
                 have_partials = True
             elif i > 0 or need_dx:
+                LAUNCHES[0] += 1
                 d = d @ (l.weight if (i > 0 or ctx.grad_cols is None) else l.weight[:, ctx.grad_cols:])
         for part_w, out_w in deferred:                              # [P, n, k] partials -> the weight gradient: the same fixed-order column sum
             jobs.append((part_w.data_ptr(), out_w.data_ptr(), part_w.shape[0], out_w.numel()))

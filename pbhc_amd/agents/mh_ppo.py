@@ -88,6 +88,7 @@ class MHPPO(OnDeviceAgent):
         self._adam_step = torch.zeros(2, device=dev)          # [actor, critic] step counts (float, like torch's `step` tensors)
         self._adam_scratch = torch.zeros(2, 512, dtype=torch.float64, device=dev)
         self._grad_norms = torch.zeros(2, device=dev)
+        self._finish_plan = None                              # set by _update_ppo for the _adam2 call that follows it (see there)
         self._loss_scalars = torch.zeros(4, device=dev)
         self.betas, self.adam_eps = (0.9, 0.999), 1e-8
         # kept for checkpoint (de)serialisation in torch.optim.Adam's format
@@ -252,11 +253,22 @@ class MHPPO(OnDeviceAgent):
 
     def _adam2(self, zero_grad):
         """both networks' clip_grad_norm_ + Adam in one launch pair (two segments of the flat buffers, each clipped by its own norm);
-        zero_grad: the pass leaves the gradient buffer zeroed — the next step's zero_grad()"""
-        _lib.check(_lib.lib().pbhc_adam_clip2(self._pflat.data_ptr(), self._gflat.data_ptr(), self._mflat.data_ptr(), self._vflat.data_ptr(), self._n_actor,
-                                              self._n_critic, self._lr.data_ptr(), self._adam_step.data_ptr(), float(self.max_grad_norm), self.betas[0],
-                                              self.betas[1], self.adam_eps, 0.0, zero_grad, self._adam_scratch.data_ptr(), self._grad_norms.data_ptr(),
-                                              _lib.current_stream()), "pbhc_adam_clip2")
+        zero_grad: the pass leaves the gradient buffer zeroed — the next step's zero_grad().
+        Where the backward's finishing launch has just left the gradient's sums of squares (`_finish_plan`, a fused_mlp.StepSqnorm.Plan set
+        by _update_ppo for this one call): the optimiser pass alone on those partials — no norm launch, and the step counters were
+        advanced by that launch.  (The plan comes by the attribute, consumed here, and not as a parameter: `_adam2(zero_grad)` is the one
+        hook of the optimiser pass, and what wraps it — tests/test_gpu_update_tail.py keeps the gradients through it — has that signature.)"""
+        plan, self._finish_plan = self._finish_plan, None
+        lib, P = _lib.lib(), lambda t: t.data_ptr()
+        if plan is not None:
+            _lib.check(lib.pbhc_adam_clip2_parts(P(self._pflat), P(self._gflat), P(self._mflat), P(self._vflat), self._n_actor, self._n_critic, P(self._lr),
+                                                 P(self._adam_step), float(self.max_grad_norm), self.betas[0], self.betas[1], self.adam_eps, 0.0, zero_grad,
+                                                 plan.part_ptr[0], plan.nparts[0], plan.part_ptr[1], plan.nparts[1], P(self._grad_norms),
+                                                 _lib.current_stream()), "pbhc_adam_clip2_parts")
+            return
+        _lib.check(lib.pbhc_adam_clip2(P(self._pflat), P(self._gflat), P(self._mflat), P(self._vflat), self._n_actor, self._n_critic, P(self._lr),
+                                       P(self._adam_step), float(self.max_grad_norm), self.betas[0], self.betas[1], self.adam_eps, 0.0, zero_grad,
+                                       P(self._adam_scratch), P(self._grad_norms), _lib.current_stream()), "pbhc_adam_clip2")
 
     def _update_ppo(self, b, loss):
         if self._need_next:
@@ -270,6 +282,7 @@ class MHPPO(OnDeviceAgent):
         am, cm = self.actor.actor_module, self.critic.critic_module
         pair = None
         self._update_pairs = []
+        launches0 = fused_mlp.LAUNCHES[0]
         if switch_on("PBHC_PAIR_TAILS") and am._fused and cm._fused:
             pair = fused_mlp.forward_pair(am.module, b["actor_obs"], cm.module, b["critic_obs"], wide=switch_on("PBHC_PAIR_WIDE"), formed=self._update_pairs)
         self._update_form = "per-stack" if pair is None else "paired"
@@ -295,7 +308,18 @@ class MHPPO(OnDeviceAgent):
         red.scalars, red.scalars_acc, red.lr = self._loss_scalars.data_ptr(), loss["_acc"].data_ptr() if "_acc" in loss else None, self._lr.data_ptr()
         red.num_partials, red.B, red.A, red.adapt_lr = npart.value, B, self.num_act, on_device_lr
         red.entropy_coef, red.desired_kl = float(self.entropy_coef), float(self.desired_kl or 0.0)
-        self._backward_both(mu, value, red)
+        # The gradient norm: every gradient element is produced or passed by the backward's finishing launch, which squares what it stores
+        # (PBHC_STEP_FINISH=0: a norm pass of its own over the flat buffer, as _adam2 runs it).  Not data-parallel: the all-reduce changes the
+        # gradients after the finish, so the norm has to follow it.  `_step_finish` says which form ran; `_update_launches` is the step's
+        # launch count by bookkeeping (fused_mlp.LAUNCHES at its call sites + this method's own: loss, (norm,) Adam, the data-parallel
+        # copy / all-reduce / rule) — not read from the stream.
+        sqnorm = None
+        if switch_on("PBHC_STEP_FINISH") and not self._dp and am._fused and cm._fused and all(getattr(q, "_grad_direct", False) for q in self._direct_stacks):
+            if self.__dict__.get("_sqnorm") is None or self._sqnorm.gflat is not self._gflat:
+                self._sqnorm = fused_mlp.StepSqnorm(self._gflat, self._n_actor, self._n_critic, self._adam_step)
+            sqnorm = self._sqnorm
+        plan = self._backward_both(mu, value, red, sqnorm)
+        self._step_finish = "squares" if plan is not None else "norm-pass"
         na, nc = self._n_actor, self._n_critic
         if self._dp:
             # ONE all-reduce per optimiser step (north_star: "a single RCCL all-reduce of policy gradients per PPO update"): actor + critic
@@ -305,20 +329,25 @@ class MHPPO(OnDeviceAgent):
             pdist.allreduce_mean_(self._gflat[:na + nc + 1])
             if adapt:                                    # the rule on the all-rank KL mean: one launch (pdist.kl_lr_rule_ is its host-tensor form)
                 _lib.check(lib.pbhc_kl_lr_rule(self._lr.data_ptr(), 2, self._gflat[na + nc:].data_ptr(), float(self.desired_kl), st), "pbhc_kl_lr_rule")
+        self._finish_plan = plan                          # (None: _adam2 runs its own norm pass)
         self._adam2(zero_grad=1)
+        self._update_launches = fused_mlp.LAUNCHES[0] - launches0 + (3 if plan is None else 2) + ((2 + adapt) if self._dp else 0)   # + loss, (norm,) Adam
         self._gflat_clean = True
         if "_acc" not in loss:                            # ("_acc": summed by the loss's second stage)
             loss["Value"] += self._loss_scalars[1]; loss["Surrogate"] += self._loss_scalars[0]; loss["Entropy"] += self._loss_scalars[2]
         return loss
 
-    def _backward_both(self, mu, value, reduce):
+    def _backward_both(self, mu, value, reduce, sqnorm=None):
         """both networks' backward on this stream, their finishing column-sum launches merged into one (fused_mlp.finish_deferred) that also
-        carries the loss's second stage (`reduce`, a PbhcPpoReduce)"""
+        carries the loss's second stage (`reduce`, a PbhcPpoReduce) and, with `sqnorm` (a fused_mlp.StepSqnorm), leaves the gradient's sums of
+        squares -> the StepSqnorm.Plan that ran, or None"""
         fused_mlp.begin_deferred_finish()
+        plan = None
         try:
             torch.autograd.backward([mu, value], [self._grad_mu, self._grad_value])
         finally:
-            fused_mlp.finish_deferred(reduce)
+            plan = fused_mlp.finish_deferred(reduce, sqnorm)
+        return plan
 
     def _update_ppo_eager(self, b, loss):
         """Eager PyTorch form of the update (used only for the optional L2C2 regulariser, mh_ppo.py:488-507)."""

@@ -172,7 +172,7 @@ struct ReduceArgs {
 // 1024 threads).  Chunk ch sums blocks ch, ch + 32, ... in that order and the chunks are added in order 0..31, whichever thread summed them:
 // the result does not depend on NT.
 template <int NT>
-__device__ __forceinline__ void ppo_reduce_body(const ReduceArgs& P) {
+__device__ __forceinline__ float ppo_reduce_body(const ReduceArgs& P) {        // -> the grad_std element this thread stored (0: none)
   __shared__ double sh_g[RED_CH][33];
   __shared__ double sh_s[RED_CH][4];
   __shared__ float sh_e[32];
@@ -222,11 +222,13 @@ __device__ __forceinline__ void ppo_reduce_body(const ReduceArgs& P) {
   }
   if (threadIdx.x < 32) sh_e[col] = col < A ? 0.5f + 0.9189385332046727f + logf(sig) : 0.0f;   // entropy terms (mean over rows of identical values)
   __syncthreads();
+  float gstd = 0.0f;
   if (threadIdx.x < A) {
     double t = 0.0;
     for (int ch = 0; ch < RED_CH; ++ch) t += sh_g[ch][threadIdx.x];
     // actor_loss = surrogate - entropy_coef * entropy ; entropy = sum_a (0.5 + 0.5 log(2 pi) + log sigma_a)
-    P.grad_std[threadIdx.x] = (float)t - P.entropy_coef / sig;
+    gstd = (float)t - P.entropy_coef / sig;
+    P.grad_std[threadIdx.x] = gstd;
   }
   if (threadIdx.x >= 32 && threadIdx.x < 35) {              // wave 0's upper half: the three scalar columns, each its own lane
     const int k = threadIdx.x - 32;
@@ -252,6 +254,7 @@ __device__ __forceinline__ void ppo_reduce_body(const ReduceArgs& P) {
     else if (kl_mean < P.desired_kl / 2.0f && kl_mean > 0.0f) l = fminf(1e-2f, l * 1.5f);
     P.lr[threadIdx.x] = l;
   }
+  return gstd;
 }
 __global__ __launch_bounds__(RED_T) void k_ppo_reduce(ReduceArgs P) { ppo_reduce_body<RED_T>(P); }
 
@@ -316,65 +319,100 @@ __global__ __launch_bounds__(ACT_T) void k_act_bwd_bias(const float* __restrict_
   }
 }
 // second stage: 32 columns x 8 slices per block, fixed order
-__device__ __forceinline__ void colsum_final_block(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out, int block);
+// SQ (all colsum block bodies below): also the sum, in double, of the squares of the floats the block stores — returned on thread 0.
+template <bool SQ>
+__device__ __forceinline__ double colsum_final_block(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out, int block);
 __global__ __launch_bounds__(ACT_T) void k_colsum_final(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out) {
-  colsum_final_block(part, nblocks, n, out, blockIdx.x);
+  colsum_final_block<false>(part, nblocks, n, out, blockIdx.x);
 }
 struct ColsumJobs { PbhcColsumJob job[PBHC_MAX_COLSUM_JOBS]; int first_block[PBHC_MAX_COLSUM_JOBS]; };
+// fixed-order sum over the 64 lanes of a wave (every lane gets it); call from wave-uniform control flow
+__device__ __forceinline__ double wave_sum_f64(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
 // Two job shapes.  TALL: many partial rows, few columns (bias gradients, the output layer's weight gradient: <= 1024 rows x <= 3k columns) —
 // 32 columns x 8 row slices per block.  WIDE: few partial images, many columns (the split-K partials of a hidden layer's weight gradient:
 // 2..32 images of up to 768 x 630) — a thread owns four consecutive columns, 1024 per block, and walks the images in order with all loads of
-// a run of eight in flight.
+// a run of eight in flight.  (Sixteen images a run was measured: the finishing launch 18.9 -> 26.5 us, profiles/update_step_finish.txt §3.)
 __host__ __device__ __forceinline__ bool colsum_wide(int num_row_blocks, int n) { return num_row_blocks <= 64 && n >= 4096 && (n & 3) == 0; }
 __host__ __device__ __forceinline__ int colsum_blocks(int num_row_blocks, int n) { return colsum_wide(num_row_blocks, n) ? (n + 1023) / 1024 : (n + 31) / 32; }
-__device__ __forceinline__ void colsum_wide_block(const float* __restrict__ part, int P, int n, float* __restrict__ out, int block) {
-  const int c = block * 1024 + 4 * (int)threadIdx.x;
-  if (c >= n) return;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+__device__ __forceinline__ void colsum_wide_images(const float* __restrict__ part, int P, int n, int c, double s[4]) {
   int b = 0;
   for (; b + 8 <= P; b += 8) {
     float4 v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(part + (size_t)(b + u) * n + c);
 #pragma unroll
-    for (int u = 0; u < 8; ++u) { s0 += (double)v[u].x; s1 += (double)v[u].y; s2 += (double)v[u].z; s3 += (double)v[u].w; }
+    for (int u = 0; u < 8; ++u) { s[0] += (double)v[u].x; s[1] += (double)v[u].y; s[2] += (double)v[u].z; s[3] += (double)v[u].w; }
   }
   for (; b < P; ++b) {
     const float4 v = *reinterpret_cast<const float4*>(part + (size_t)b * n + c);
-    s0 += (double)v.x; s1 += (double)v.y; s2 += (double)v.z; s3 += (double)v.w;
-  }
-  if (((uintptr_t)out & 15) == 0) {
-    *reinterpret_cast<float4*>(out + c) = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
-  } else {                                                         // a .grad view at an odd offset of the flat gradient buffer
-    out[c] = (float)s0; out[c + 1] = (float)s1; out[c + 2] = (float)s2; out[c + 3] = (float)s3;
+    s[0] += (double)v.x; s[1] += (double)v.y; s[2] += (double)v.z; s[3] += (double)v.w;
   }
 }
+template <bool SQ>
+__device__ __forceinline__ double colsum_wide_block(const float* __restrict__ part, int P, int n, float* __restrict__ out, int block) {
+  __shared__ double sh_w[ACT_T / 64];
+  const int c = block * 1024 + 4 * (int)threadIdx.x;
+  double q = 0.0;
+  if (c < n) {                                                       // (n is a multiple of 4: c + 3 < n)
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    colsum_wide_images(part, P, n, c, s);
+    const float f0 = (float)s[0], f1 = (float)s[1], f2 = (float)s[2], f3 = (float)s[3];
+    if (((uintptr_t)out & 15) == 0) {
+      *reinterpret_cast<float4*>(out + c) = make_float4(f0, f1, f2, f3);
+    } else {                                                         // a .grad view at an odd offset of the flat gradient buffer
+      out[c] = f0; out[c + 1] = f1; out[c + 2] = f2; out[c + 3] = f3;
+    }
+    if constexpr (SQ) q = (double)f0 * (double)f0 + (double)f1 * (double)f1 + (double)f2 * (double)f2 + (double)f3 * (double)f3;
+  }
+  if constexpr (SQ) {
+    q = wave_sum_f64(q);
+    if ((threadIdx.x & 63) == 0) sh_w[threadIdx.x >> 6] = q;
+    __syncthreads();
+    q = 0.0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int w = 0; w < ACT_T / 64; ++w) q += sh_w[w];
+    }
+  }
+  return q;
+}
 // the second stage of several layers in one launch (the bias gradients of a whole MLP backward)
-__device__ __forceinline__ void colsum_multi_block(const ColsumJobs& J, int num_jobs, int blk) {
+template <bool SQ>
+__device__ __forceinline__ double colsum_multi_block(const ColsumJobs& J, int num_jobs, int blk, int* job_index = nullptr) {
   int j = 0;
   while (j + 1 < num_jobs && blk >= J.first_block[j + 1]) ++j;
+  if (job_index) *job_index = j;
   const PbhcColsumJob job = J.job[j];
   const int block = blk - J.first_block[j];
   if (colsum_wide(job.num_row_blocks, job.n) && ((uintptr_t)job.part & 15) == 0) {
-    colsum_wide_block(job.part, job.num_row_blocks, job.n, job.out, block);
+    return colsum_wide_block<SQ>(job.part, job.num_row_blocks, job.n, job.out, block);
   } else if (colsum_wide(job.num_row_blocks, job.n)) {             // (unaligned partial images: the tall form over this block's 1024 columns)
+    double q = 0.0;
     for (int sub = 0; sub < 32; ++sub)
-      if ((block * 32 + sub) * 32 < job.n) { colsum_final_block(job.part, job.num_row_blocks, job.n, job.out, block * 32 + sub); __syncthreads(); }
+      if ((block * 32 + sub) * 32 < job.n) { q += colsum_final_block<SQ>(job.part, job.num_row_blocks, job.n, job.out, block * 32 + sub); __syncthreads(); }
+    return q;
   } else {
-    colsum_final_block(job.part, job.num_row_blocks, job.n, job.out, block);
+    return colsum_final_block<SQ>(job.part, job.num_row_blocks, job.n, job.out, block);
   }
 }
-__global__ __launch_bounds__(ACT_T) void k_colsum_final_multi(ColsumJobs J, int num_jobs) { colsum_multi_block(J, num_jobs, (int)blockIdx.x); }
+__global__ __launch_bounds__(ACT_T) void k_colsum_final_multi(ColsumJobs J, int num_jobs) { colsum_multi_block<false>(J, num_jobs, (int)blockIdx.x); }
 // The same launch with the loss's second stage (k_ppo_reduce's body) as workgroup 0: nothing reads the loss scalars, d(loss)/d(std) or the
 // learning rates before the optimiser pass that follows this launch, so the one-workgroup reduce need not be a launch of its own between the
 // loss and the backward.  It is the first workgroup because it is the longest (four dependent trips to memory).
 __global__ __launch_bounds__(ACT_T) void k_colsum_final_reduce(ColsumJobs J, int num_jobs, ReduceArgs Q) {
   if (blockIdx.x == 0) ppo_reduce_body<ACT_T>(Q);
-  else colsum_multi_block(J, num_jobs, (int)blockIdx.x - 1);
+  else colsum_multi_block<false>(J, num_jobs, (int)blockIdx.x - 1);
 }
-__device__ __forceinline__ void colsum_final_block(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out, int block) {
+template <bool SQ>
+__device__ __forceinline__ double colsum_final_block(const float* __restrict__ part, int nblocks, int n, float* __restrict__ out, int block) {
   // 32 columns x 8 row slices per block (a slice reads rows slice, slice + 8, ...: eight independent loads in flight per thread), then the
-  // slices in order 0..7: fixed order, deterministic
+  // slices in order 0..7: fixed order, deterministic.  (Longer trips — 48 or 128 loads a thread before the first add — were measured:
+  // 0.6-1.0 us of the launch, nothing at the update's gate, twice the registers of the plain column-sum kernels; not kept,
+  // profiles/update_step_finish.txt §3.)
   __shared__ double sh[8][32];
   const int col = threadIdx.x & 31, slice = threadIdx.x >> 5, c = block * 32 + col;
   double s = 0.0;
@@ -391,11 +429,101 @@ __device__ __forceinline__ void colsum_final_block(const float* __restrict__ par
   }
   sh[slice][col] = s;
   __syncthreads();
+  float f = 0.0f;
   if (slice == 0 && c < n) {
     double t = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) t += sh[k][col];
-    out[c] = (float)t;
+    f = (float)t;
+    out[c] = f;
+  }
+  double q = 0.0;
+  if constexpr (SQ) {
+    if (threadIdx.x < 64) q = wave_sum_f64((double)f * (double)f);    // (wave 0 holds slice 0; its upper half adds zeros)
+  }
+  return q;
+}
+
+// ---- the finishing launch that also leaves ||g||^2 ------------------------------------------------------------------------------------
+// k_colsum_final_reduce whose blocks square what they store: every gradient element of a 24 576-row minibatch is produced by this launch
+// (bias gradients, the output layers' dW, the split-K sums of the hidden dW, grad_std), so k_sqnorm_partial's pass over the flat gradient —
+// a launch that re-reads what this one has just written — is not needed.  Each workgroup writes ONE double to its own slot of its segment's
+// partial buffer (no atomics, no ticket: k_adam_clip sums the slots in a fixed order); ranges of a segment that no job writes are squared
+// by rider workgroups behind the column sums (they read what EARLIER launches wrote and depend on nothing in this one).
+struct __attribute__((packed, aligned(4))) AdamF4 { float v[4]; };
+#define SQ_RANGES (2 * PBHC_SQ_MAX_RANGES)
+struct SqArgs {
+  double* part[2];
+  const float* base[2];
+  float* step;                                       // both Adam step counters, advanced by workgroup 0 (as k_sqnorm_partial's block 0 does)
+  int slot0[PBHC_MAX_COLSUM_JOBS], seg[PBHC_MAX_COLSUM_JOBS];   // job j's blocks write part[seg[j]][slot0[j] + block]; seg < 0: in no segment
+  int red_seg, red_slot;                             // grad_std's slot
+  int num_ranges;
+  int r_seg[SQ_RANGES], r_off[SQ_RANGES], r_len[SQ_RANGES], r_slot0[SQ_RANGES], r_first[SQ_RANGES + 1];     // r_first: rider workgroups before range k
+};
+__device__ __forceinline__ void sq_rider_block(const SqArgs& X, int r) {
+  __shared__ double sh_r[ACT_T / 64];
+  int k = 0;
+  while (k + 1 < X.num_ranges && r >= X.r_first[k + 1]) ++k;
+  const int chunk = r - X.r_first[k], sg = X.r_seg[k];
+  const float* __restrict__ g = X.base[sg];
+  const size_t end = (size_t)X.r_off[k] + (size_t)X.r_len[k];
+  const size_t i0 = (size_t)X.r_off[k] + (size_t)chunk * PBHC_SQ_RANGE_FLOATS + 4 * threadIdx.x;
+  const size_t cend = min(end, (size_t)X.r_off[k] + (size_t)(chunk + 1) * PBHC_SQ_RANGE_FLOATS);
+  constexpr int RU = PBHC_SQ_RANGE_FLOATS / (4 * ACT_T);
+  AdamF4 q[RU];
+#pragma unroll
+  for (int u = 0; u < RU; ++u) {                       // (ranges are only 4-byte aligned: dword-aligned dwordx4 loads, as k_adam_clip's)
+    const size_t i = i0 + (size_t)u * 4 * ACT_T;
+    if (i + 4 <= cend) q[u] = *reinterpret_cast<const AdamF4*>(g + i);
+    else q[u] = AdamF4{{0.0f, 0.0f, 0.0f, 0.0f}};
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int u = 0; u < RU; ++u)
+    s += (double)q[u].v[0] * (double)q[u].v[0] + (double)q[u].v[1] * (double)q[u].v[1] + (double)q[u].v[2] * (double)q[u].v[2] + (double)q[u].v[3] * (double)q[u].v[3];
+#pragma unroll
+  for (int u = 0; u < RU; ++u) {                       // the range's last one to three floats
+    const size_t i = i0 + (size_t)u * 4 * ACT_T;
+    if (i < cend && i + 4 > cend)
+      for (size_t j = i; j < cend; ++j) s += (double)g[j] * (double)g[j];
+  }
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) sh_r[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < ACT_T / 64; ++w) t += sh_r[w];
+    X.part[sg][X.r_slot0[k] + chunk] = t;
+  }
+}
+// grid: [workgroup 0: the loss's second stage, when has_reduce] [colsum_blocks column-sum workgroups] [rider workgroups]
+// (three waves per SIMD, k_colsum_final_reduce's occupancy, asked for: two registers more would cost a wave)
+__global__ __launch_bounds__(ACT_T) __attribute__((amdgpu_waves_per_eu(3))) void k_colsum_final_reduce_sq(ColsumJobs J, int num_jobs, ReduceArgs Q, SqArgs X, int has_reduce, int colsum_blocks_total) {
+  int blk = (int)blockIdx.x;
+  if (has_reduce) {
+    if (blk == 0) {
+      float st0 = 0.0f, st1 = 0.0f;
+      if (threadIdx.x == 0) { st0 = X.step[0]; st1 = X.step[1]; }      // (requested with the reduce's partial rows, stored behind it)
+      const float gs = ppo_reduce_body<ACT_T>(Q);      // (0 on the threads that stored no grad_std element)
+      if (threadIdx.x < 64) {
+        const double q = wave_sum_f64((double)gs * (double)gs);
+        if (threadIdx.x == 0) {
+          if (X.red_seg >= 0) X.part[X.red_seg][X.red_slot] = q;
+          X.step[0] = st0 + 1.0f; X.step[1] = st1 + 1.0f;
+        }
+      }
+      return;
+    }
+    blk -= 1;
+  }
+  if (blk < colsum_blocks_total) {
+    int j;
+    const double q = colsum_multi_block<true>(J, num_jobs, blk, &j);
+    if (threadIdx.x == 0 && X.seg[j] >= 0) X.part[X.seg[j]][X.slot0[j] + blk - J.first_block[j]] = q;
+  } else {
+    sq_rider_block(X, blk - colsum_blocks_total);
   }
 }
 
@@ -412,7 +540,6 @@ struct AdamSegs {
   int n[ADAM_MAX_SEGS], nparts[ADAM_MAX_SEGS], first_norm_block[ADAM_MAX_SEGS + 1], first_adam_block[ADAM_MAX_SEGS + 1];
   int num;
 };
-struct __attribute__((packed, aligned(4))) AdamF4 { float v[4]; };
 __global__ __launch_bounds__(ADAM_T) void k_sqnorm_partial(AdamSegs S) {
   __shared__ double sh[ADAM_T];
   const int seg = (S.num > 1 && (int)blockIdx.x >= S.first_norm_block[1]) ? 1 : 0;
@@ -449,6 +576,20 @@ __global__ __launch_bounds__(ADAM_T) void k_adam_clip(AdamSegs S, float max_norm
   __shared__ double sh[ADAM_T];
   const int seg = (S.num > 1 && (int)blockIdx.x >= S.first_adam_block[1]) ? 1 : 0;
   const int b = blockIdx.x - S.first_adam_block[seg], nb = S.first_adam_block[seg + 1] - S.first_adam_block[seg];
+  float* __restrict__ p = S.p[seg];
+  float* __restrict__ g = S.g[seg];
+  float* __restrict__ m = S.m[seg];
+  float* __restrict__ v = S.v[seg];
+  const size_t n = (size_t)S.n[seg];
+  // the block's first p/g/m/v quad is requested BEFORE the norm reduction (nine barriers) and used after it: none of the four depends on the norm
+  const size_t i_first = ((size_t)b * ADAM_T + threadIdx.x) * 4;
+  const bool pre = i_first + 4 <= n;
+  const size_t i_pre = pre ? i_first : 0;
+  AdamF4 pp = {}, pg = {}, pm = {}, pv = {};
+  if (n >= 4) {
+    pp = *reinterpret_cast<const AdamF4*>(p + i_pre); pg = *reinterpret_cast<const AdamF4*>(g + i_pre);
+    pm = *reinterpret_cast<const AdamF4*>(m + i_pre); pv = *reinterpret_cast<const AdamF4*>(v + i_pre);
+  }
   {                                                    // ||g||^2 from the block partials: strided loads + a fixed-order tree (deterministic)
     const double* __restrict__ part = S.part[seg];
     double t = 0.0;
@@ -471,11 +612,6 @@ __global__ __launch_bounds__(ADAM_T) void k_adam_clip(AdamSegs S, float max_norm
     if (b == 0 && S.norm_out[seg]) S.norm_out[seg][0] = norm;
   }
   __syncthreads();
-  float* __restrict__ p = S.p[seg];
-  float* __restrict__ g = S.g[seg];
-  float* __restrict__ m = S.m[seg];
-  float* __restrict__ v = S.v[seg];
-  const size_t n = (size_t)S.n[seg];
   const float clipc = s_clip, step_size = s_lr / s_bc1, bc2s = s_bc2s;
   const float decay = 1.0f - s_lr * weight_decay;              // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) before the Adam update
   auto one = [&](float& pi, float& gi_, float& mi_, float& vi_) {
@@ -487,7 +623,15 @@ __global__ __launch_bounds__(ADAM_T) void k_adam_clip(AdamSegs S, float max_norm
     const float denom = sqrtf(vi) / bc2s + eps;
     pi = pi * decay - step_size * (mi / denom);
   };
-  for (size_t i = ((size_t)b * ADAM_T + threadIdx.x) * 4; i < n; i += (size_t)nb * ADAM_T * 4) {
+  size_t i = i_first;
+  if (pre) {                                           // the quad requested above
+#pragma unroll
+    for (int u = 0; u < 4; ++u) one(pp.v[u], pg.v[u], pm.v[u], pv.v[u]);
+    *reinterpret_cast<AdamF4*>(p + i) = pp; *reinterpret_cast<AdamF4*>(g + i) = pg;
+    *reinterpret_cast<AdamF4*>(m + i) = pm; *reinterpret_cast<AdamF4*>(v + i) = pv;
+    i += (size_t)nb * ADAM_T * 4;
+  }
+  for (; i < n; i += (size_t)nb * ADAM_T * 4) {
     if (i + 4 <= n) {
       AdamF4 qp = *reinterpret_cast<const AdamF4*>(p + i), qg = *reinterpret_cast<const AdamF4*>(g + i);
       AdamF4 qm = *reinterpret_cast<const AdamF4*>(m + i), qv = *reinterpret_cast<const AdamF4*>(v + i);
@@ -950,6 +1094,103 @@ int pbhc_colsum_final_ppo_reduce(const PbhcColsumJob* jobs, int num_jobs, const 
   return PBHC_OK;
 }
 
+static bool sq_inside(const float* a, size_t len, const float* base, int n) {          // [a, a + len) within [base, base + n)
+  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * len, b0 = (uintptr_t)base, b1 = b0 + 4 * (size_t)(n > 0 ? n : 0);
+  return n > 0 && a0 >= b0 && a1 <= b1;
+}
+static bool sq_overlaps(const float* a, size_t len, const float* base, int n) {
+  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * len, b0 = (uintptr_t)base, b1 = b0 + 4 * (size_t)(n > 0 ? n : 0);
+  return n > 0 && len > 0 && a0 < b1 && a1 > b0;
+}
+// Slot plan of a whole finish (all its launches): per segment grad_std, then the jobs' workgroups in job order, then the riders.
+// job_seg / job_slot0: num_jobs entries each (may be NULL).  -> PBHC_OK or PBHC_EINVAL
+static int sq_plan(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq, int* job_seg, int* job_slot0, SqArgs& X, int cnt[2]) {
+  cnt[0] = cnt[1] = 0;
+  X.red_seg = -1; X.red_slot = 0;
+  for (int s = 0; s < 2; ++s) {
+    const PbhcSqSegment& G = sq->seg[s];
+    ARG_CHECK(G.n >= 0 && (G.n == 0 || G.base) && G.num_ranges >= 0 && G.num_ranges <= PBHC_SQ_MAX_RANGES && (G.n > 0 || G.num_ranges == 0));
+    if (sq_overlaps(red->grad_std, (size_t)red->A, G.base, G.n)) {
+      ARG_CHECK(sq_inside(red->grad_std, (size_t)red->A, G.base, G.n) && X.red_seg < 0);
+      X.red_seg = s; X.red_slot = cnt[s]++;
+    }
+  }
+  ARG_CHECK(!sq_overlaps(sq->seg[0].base, (size_t)sq->seg[0].n, sq->seg[1].base, sq->seg[1].n));
+  for (int j = 0; j < num_jobs; ++j) {
+    int sg = -1;
+    for (int s = 0; s < 2; ++s) {
+      const PbhcSqSegment& G = sq->seg[s];
+      if (sq_overlaps(jobs[j].out, (size_t)jobs[j].n, G.base, G.n)) {
+        ARG_CHECK(sq_inside(jobs[j].out, (size_t)jobs[j].n, G.base, G.n));          // (a job whose output straddles a segment's end)
+        sg = s;
+      }
+    }
+    if (job_seg) { job_seg[j] = sg; job_slot0[j] = sg >= 0 ? cnt[sg] : 0; }
+    if (sg >= 0) cnt[sg] += colsum_blocks(jobs[j].num_row_blocks, jobs[j].n);
+  }
+  int k = 0, riders = 0;
+  for (int s = 0; s < 2; ++s) {
+    const PbhcSqSegment& G = sq->seg[s];
+    int prev_end = 0;
+    for (int r = 0; r < G.num_ranges; ++r, ++k) {
+      ARG_CHECK(G.range_off[r] >= prev_end && G.range_len[r] >= 1 && G.range_len[r] <= G.n - G.range_off[r]);
+      prev_end = G.range_off[r] + G.range_len[r];
+      const int wgs = (G.range_len[r] + PBHC_SQ_RANGE_FLOATS - 1) / PBHC_SQ_RANGE_FLOATS;
+      X.r_seg[k] = s; X.r_off[k] = G.range_off[r]; X.r_len[k] = G.range_len[r]; X.r_slot0[k] = cnt[s]; X.r_first[k] = riders;
+      cnt[s] += wgs; riders += wgs;
+    }
+  }
+  X.num_ranges = k;
+  for (int r = k; r < SQ_RANGES; ++r) { X.r_seg[r] = 0; X.r_off[r] = 0; X.r_len[r] = 0; X.r_slot0[r] = 0; X.r_first[r] = riders; }
+  X.r_first[SQ_RANGES] = riders;
+  return PBHC_OK;
+}
+static int sq_check_common(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq) {
+  ARG_CHECK(red && sq && num_jobs >= 0 && num_jobs <= PBHC_SQ_MAX_JOBS && (jobs || num_jobs == 0));
+  for (int j = 0; j < num_jobs; ++j) ARG_CHECK(jobs[j].part && jobs[j].out && jobs[j].num_row_blocks >= 1 && jobs[j].n >= 1);
+  ARG_CHECK(((uintptr_t)red->scratch & 15) == 0);
+  ARG_CHECK(red->scratch && red->std && red->grad_std && red->scalars && red->lr && red->num_partials >= 1 && red->B >= 1 && red->A >= 1 && red->A <= 32);
+  return PBHC_OK;
+}
+
+int pbhc_colsum_final_ppo_reduce_sqnorm_slots(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq, int32_t* slots) {
+  if (int rc = sq_check_common(jobs, num_jobs, red, sq)) return rc;
+  ARG_CHECK(slots);
+  SqArgs X = {};
+  int cnt[2];
+  if (int rc = sq_plan(jobs, num_jobs, red, sq, nullptr, nullptr, X, cnt)) return rc;
+  slots[0] = cnt[0]; slots[1] = cnt[1];
+  return PBHC_OK;
+}
+
+int pbhc_colsum_final_ppo_reduce_sqnorm(const PbhcColsumJob* jobs, int num_jobs, const PbhcPpoReduce* red, const PbhcSqnorm* sq, void* stream) {
+  if (int rc = sq_check_common(jobs, num_jobs, red, sq)) return rc;
+  ARG_CHECK(sq->step);
+  SqArgs X = {};
+  int cnt[2];
+  int job_seg[PBHC_SQ_MAX_JOBS], job_slot0[PBHC_SQ_MAX_JOBS];
+  if (int rc = sq_plan(jobs, num_jobs, red, sq, job_seg, job_slot0, X, cnt)) return rc;
+  for (int s = 0; s < 2; ++s) {
+    ARG_CHECK(cnt[s] <= sq->seg[s].part_cap && (cnt[s] == 0 || sq->seg[s].part));
+    X.part[s] = sq->seg[s].part; X.base[s] = sq->seg[s].base;
+  }
+  X.step = sq->step;
+  const int riders = X.r_first[SQ_RANGES];
+  const ReduceArgs Q{red->scratch, red->scratch + (size_t)red->num_partials * LOSS_NP, red->std, red->num_partials, red->B, red->A, red->entropy_coef,
+                     red->desired_kl, red->adapt_lr & 1, red->grad_std, red->scalars, red->lr, red->scalars_acc};
+  for (int k = 0; k == 0 || k < num_jobs; k += PBHC_MAX_COLSUM_JOBS) {
+    const int nj = num_jobs - k < PBHC_MAX_COLSUM_JOBS ? num_jobs - k : PBHC_MAX_COLSUM_JOBS;
+    const bool last = k + PBHC_MAX_COLSUM_JOBS >= num_jobs;
+    ColsumJobs J;
+    const int blocks = colsum_fill(jobs + k, nj, J);
+    for (int j = 0; j < PBHC_MAX_COLSUM_JOBS; ++j) { X.seg[j] = j < nj ? job_seg[k + j] : -1; X.slot0[j] = j < nj ? job_slot0[k + j] : 0; }
+    hipLaunchKernelGGL(k_colsum_final_reduce_sq, dim3((last ? 1 : 0) + blocks + (last ? riders : 0)), dim3(ACT_T), 0, (hipStream_t)stream, J, nj, Q, X,
+                       last ? 1 : 0, blocks);
+    HIP_CHECK(hipGetLastError());
+  }
+  return PBHC_OK;
+}
+
 // The adaptive-KL learning-rate rule (mh_ppo.py:455-466) on a KL mean that is ready on the device — the data-parallel update applies it to
 // the mean over ALL ranks, which exists only after the gradient bucket's all-reduce; as eight tiny torch launches it was 40 us of every
 // optimiser step.  Same arithmetic as the rule inside k_ppo_reduce.
@@ -1006,6 +1247,21 @@ int pbhc_adam_clip2(float* param, float* grad, float* exp_avg, float* exp_avg_sq
   adam_fill(S, 1, param + n0, grad + n0, exp_avg + n0, exp_avg_sq + n0, n1, lr + 1, step + 1, scratch + 512, norm_out ? norm_out + 1 : nullptr);
   hipLaunchKernelGGL(k_sqnorm_partial, dim3(S.first_norm_block[2]), dim3(ADAM_T), 0, st, S);
   hipLaunchKernelGGL(k_adam_clip, dim3(S.first_adam_block[2]), dim3(ADAM_T), 0, st, S, max_norm, beta1, beta2, eps, weight_decay, zero_grad);
+  HIP_CHECK(hipGetLastError());
+  return PBHC_OK;
+}
+
+int pbhc_adam_clip2_parts(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int n0, int n1, const float* lr, const float* step, float max_norm,
+                          float beta1, float beta2, float eps, float weight_decay, int zero_grad, const double* part0, int nparts0, const double* part1,
+                          int nparts1, float* norm_out, void* stream) {
+  ARG_CHECK(param && grad && exp_avg && exp_avg_sq && lr && step && part0 && part1 && n0 >= 1 && n1 >= 1 && nparts0 >= 1 && nparts1 >= 1);
+  AdamSegs S = {};
+  S.num = 2;
+  adam_fill(S, 0, param, grad, exp_avg, exp_avg_sq, n0, lr, const_cast<float*>(step), const_cast<double*>(part0), norm_out);
+  adam_fill(S, 1, param + n0, grad + n0, exp_avg + n0, exp_avg_sq + n0, n1, lr + 1, const_cast<float*>(step) + 1, const_cast<double*>(part1),
+            norm_out ? norm_out + 1 : nullptr);
+  S.nparts[0] = nparts0; S.nparts[1] = nparts1;           // (k_adam_clip reads part / nparts / step, writes none of them)
+  hipLaunchKernelGGL(k_adam_clip, dim3(S.first_adam_block[2]), dim3(ADAM_T), 0, (hipStream_t)stream, S, max_norm, beta1, beta2, eps, weight_decay, zero_grad);
   HIP_CHECK(hipGetLastError());
   return PBHC_OK;
 }
