@@ -196,9 +196,16 @@ class MotionTrackingOracle:
     def _sigma_update(self, err, key):
         if not self.adaptive:
             return
-        alpha = self.cfg.rewards.adaptive_tracking_sigma.alpha
+        a = self.cfg.rewards.adaptive_tracking_sigma
+        alpha = a.alpha
+        kind = a.get("type", "origin")
         self.ema[key] = self.ema[key] * (1 - alpha) + err.mean().item() * alpha
-        self.sigma[key] = min(self.ema[key], self.sigma[key])        # type "origin" (motion_tracking.py:1046-1048)
+        if kind == "scale":                                           # motion_tracking.py:1039-1041
+            self.sigma[key] = min(self.ema[key] * a.get("scale", 1.0), self.sigma[key])
+        elif kind == "mean":                                          # motion_tracking.py:1042-1045
+            self.sigma[key] = (min(self.ema[key], self.sigma[key]) + self.ema[key]) / 2
+        elif kind == "origin":                                        # motion_tracking.py:1046-1048
+            self.sigma[key] = min(self.ema[key], self.sigma[key])
 
     # ------------------------------------------------------------------------------------
     def step(self, actions, frame, body_state, u_rfi=None, reset_samples=None, gate_u=None, redraw_samples=None):

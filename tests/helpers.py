@@ -282,3 +282,10 @@ for _pre, _init, _lo, _hi, _deg in (("soft_dof_pos", 0.5, 0.4, 0.56, 0.05), ("so
 TERM_NOISE_OVERRIDES = {"env.config.termination.terminate_by_contact": True, "env.config.termination.terminate_by_low_height": True,
                         "env.config.termination_scales.termination_min_base_height": 0.772, "obs.add_noise_currculum": True,
                         "obs.soft_dof_pos_curriculum_degree": 0.1}
+
+# overrides of the reference traces env_v1_walk_sigmamean.npz / env_v1_walk_sigmascale.npz / env_v2_student23_sigma.npz
+# (oracle/ref_harness/gen_switch_golden.py: SIGMA_MEAN, SIGMA_SCALE, V2_SIGMA)
+_AS = "rewards.adaptive_tracking_sigma."
+SIGMA_MEAN_OVERRIDES = {_AS + "type": "mean"}
+SIGMA_SCALE_OVERRIDES = {_AS + "type": "scale", _AS + "scale": 0.8}
+V2_SIGMA_OVERRIDES = {_AS + "enable": True, _AS + "type": "mean", _AS + "alpha": 0.05}

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import (GOLDEN, SOFT_LIMIT_OVERRIDES, TERM_NOISE_OVERRIDES, build_hip_env, clip_from_env_golden, fixture_config, load_env_golden, load_state_into_hip_env,
+from tests.helpers import (GOLDEN, SIGMA_MEAN_OVERRIDES, SIGMA_SCALE_OVERRIDES, SOFT_LIMIT_OVERRIDES, TERM_NOISE_OVERRIDES, build_hip_env, clip_from_env_golden, fixture_config, load_env_golden, load_state_into_hip_env,
                            skel_from_golden, state_dict_from_golden, synth_replay)
 
 pytestmark = pytest.mark.gpu
@@ -263,9 +263,11 @@ CASES = [("horse", "v1_g1_23dof_horse_stance.yaml"), ("walk", "v1_g1_23dof_walk.
                                                    ("walk_ctrlT", "v1_g1_23dof_walk.yaml", {"robot.control.control_type": "T"}),
                                                    ("walk_feetori", "v1_g1_23dof_walk.yaml", {"rewards.reward_scales.feet_heading_alignment": -0.5, "rewards.reward_scales.feet_heading_alignment_contact": -0.3, "rewards.reward_scales.penalty_feet_ori": -0.2, "rewards.reward_scales.penalty_feet_ori_contact": -0.4}),
                                                    ("walk_softlim", "v1_g1_23dof_walk.yaml", SOFT_LIMIT_OVERRIDES),
-                                                   ("walk_termnoise", "v1_g1_23dof_walk.yaml", TERM_NOISE_OVERRIDES)])
+                                                   ("walk_termnoise", "v1_g1_23dof_walk.yaml", TERM_NOISE_OVERRIDES),
+                                                   ("walk_sigmamean", "v1_g1_23dof_walk.yaml", SIGMA_MEAN_OVERRIDES),
+                                                   ("walk_sigmascale", "v1_g1_23dof_walk.yaml", SIGMA_SCALE_OVERRIDES)])
 def test_env_step_matches_reference_trace_of_a_switch(tag, cfgname, overrides):
-    """control types "V" and "T" (legged_robot_base.py:809-817), the four foot-orientation reward terms (:1030-1079), the soft-limit
+    """adaptive_tracking_sigma.type "mean" / "scale" (motion_tracking.py:1039-1045), control types "V" and "T" (legged_robot_base.py:809-817), the four foot-orientation reward terms (:1030-1079), the soft-limit
     curricula with min != max (:902-939), terminate_by_contact / terminate_by_low_height (:434-447) and the observation-noise curriculum
     (:591-592,637-646) — no shipped yaml uses them: the reference's own traces with the switch on (oracle/ref_harness/gen_switch_golden.py)"""
     test_env_step_matches_reference_trace(tag, cfgname, overrides)
@@ -333,12 +335,22 @@ def test_env_step_matches_reference_trace(tag, cfgname, overrides=None):
         assert abs(gl[K["PBHC_G_PENALTY_SCALE"]] - float(g["step__state__reward_penalty_scale"][k])) < 1e-9
         assert abs(gl[K["PBHC_G_AVG_EP_LEN"]] - float(g["step__state__average_episode_length"][k])) < 1e-5
         assert abs(gl[K["PBHC_G_MOTION_FAR_THR"]] - float(g["step__state__motion_far_threshold"][k])) < 1e-9
+        for i, name in enumerate(SIGMA_KEYS):
+            if "step__state__ema__" + name in g:
+                ref = float(g["step__state__ema__" + name][k])
+                assert abs(gl[K["PBHC_G_EMA"] + i] - ref) <= 2e-6 * abs(ref), w + "ema " + name
         log = env.read_log()
         for lk in ["terminate_by_gravity", "terminate_by_motion_far", "terminate_by_time_out", "upper_body_diff_norm", "joint_pos_diff_norm", "action_clip_frac"]:
             close(torch.tensor(log[lk]), g["step__log__" + lk][k], 1e-4, w + "log " + lk)
         for lk in ("terminate_by_contact", "terminate_by_low_height"):
             if "step__log__" + lk in g:
                 close(torch.tensor(log[lk]), g["step__log__" + lk][k], 1e-4, w + "log " + lk)
+        seen_reset = bool(g["step__reset_buf_out"][:k + 1].any())
+        checked = compare_log_block(log, g, k, seen_reset, w)
+        assert {"lower_body_diff_norm", "vr_3point_diff_norm", "terminate_by_motion_end"} <= checked
+        assert k + 1 == T or {"penalty_scale", "average_episode_length", "terminate_when_motion_far_threshold"} <= checked
+        assert k + 1 == T or not any("step__log__error_ema_" + n in g for n in SIGMA_KEYS) or any(lk.startswith("error_ema_") for lk in checked)
+        assert not seen_reset or {"end_time_ratio", "end_time_ratio_std"} <= checked
         for lk in ("soft_dof_pos_curriculum_value", "soft_dof_vel_curriculum_value", "soft_torque_curriculum_value", "current_noise_curriculum_value"):
             # the reference logs the fraction its reward pass USED in a step; after our step k the global holds the one step k + 1 will use
             if "step__log__" + lk in g and k + 1 < g["step__log__" + lk].shape[0]:
@@ -443,6 +455,55 @@ def _lib_K():
     return _lib.K
 
 
+# keys the reference logs BEFORE the step's own update of the value (legged_robot_base.py:750-761 in the reward pass, motion_tracking.py:341,350
+# in the termination test, :417-418 ahead of the rewards): its step k + 1 shows what our step k left (the alignment tests/test_oracle_env.py uses)
+LOG_BEFORE_UPDATE = ("penalty_scale", "average_episode_length", "terminate_when_motion_far_threshold", "terminate_when_dof_far_threshold",
+                     "soft_dof_pos_curriculum_value", "soft_dof_vel_curriculum_value", "soft_torque_curriculum_value", "current_noise_curriculum_value")
+
+
+def compare_log_block(log, g, k, seen_reset, w):
+    """EVERY `step__log__*` key of the reference trace `g` that `read_log()` returned, after step k -> the set of keys compared.  Means at 1e-4;
+    `error_ema_*` / `adp_sigma_*` at the sigma tolerance 2e-6 |ref|; the curriculum values at the 2e-7 |ref| of the checks above;
+    `end_time_ratio_std` at 1e-4 where the reference's value is at least 1e-3 and as a variance below that (it is formed from a sum of squares:
+    the cancellation error is absolute in the variance); the end-time-ratio pair only once an env was reset (`seen_reset`: before that the
+    reference's log still holds what its reset_all() left)."""
+    T = g["step__reset_buf_out"].shape[0]
+    done = set()
+    for key in g:
+        lk = key[len("step__log__"):]
+        if not key.startswith("step__log__") or lk not in log:
+            continue
+        lagged = lk in LOG_BEFORE_UPDATE or lk.startswith(("error_ema_", "adp_sigma_"))
+        j = k + 1 if lagged else k
+        if j >= T or (lk.startswith("end_time_ratio") and not seen_reset):
+            continue
+        ref, got = float(g[key][j]), float(log[lk])
+        if lk.startswith(("error_ema_", "adp_sigma_")):
+            assert abs(got - ref) <= 2e-6 * abs(ref), w + "log " + lk
+        elif lk.endswith("_curriculum_value"):
+            assert abs(got - ref) <= 2e-7 * abs(ref), w + "log " + lk
+        elif lk == "end_time_ratio_std" and ref < 1e-3:
+            close(torch.tensor(got * got), torch.tensor(ref * ref), 1e-4, w + "log end_time_ratio_std (variance)")
+        else:
+            close(torch.tensor(got), torch.tensor(ref), 1e-4, w + "log " + lk)
+        done.add(lk)
+    return done
+
+
+def sigma_and_ema_match_oracle(env, orc, w):
+    """adp_sigma_* / error_ema_* (the globals the reward pass of the NEXT step reads) against the oracle's, at the trace test's 2e-6 |ref|"""
+    from pbhc_amd.envs.env_config import SIGMA_KEYS
+
+    K = _lib_K()
+    env.wait_finalize()
+    gl = env.globals.cpu().numpy()
+    assert set(orc.sigma) <= set(SIGMA_KEYS) and orc.sigma
+    for i, name in enumerate(SIGMA_KEYS):
+        if name in orc.sigma:
+            for slot, ref in (("PBHC_G_SIGMA", float(orc.sigma[name])), ("PBHC_G_EMA", float(orc.ema[name]))):
+                assert abs(gl[K[slot] + i] - ref) <= 2e-6 * abs(ref), w + f"{slot} {name}: {gl[K[slot] + i]!r} vs {ref!r}"
+
+
 def _env_step_vs_oracle(N, T, tag="horse", cfgname="v1_g1_23dof_horse_stance.yaml", overrides=None, contact_hits=False, noise_curriculum=False, default_bias=False, gates=None,
                         redraw_steps=(), soft_limits=False):
     from oracle.env_v1 import MotionTrackingOracle
@@ -519,6 +580,7 @@ def _env_step_vs_oracle(N, T, tag="horse", cfgname="v1_g1_23dof_horse_stance.yam
         close(env.torques, orc.s["torques"], 3e-5, w + "torques", rtol=1e-5)
         for name, view in env.history.items():
             close(view, orc.hist[name], 3e-5, w + "hist " + name)
+        sigma_and_ema_match_oracle(env, orc, w)
         if redraw_steps:                                 # the episodic DR state of EVERY env after a re-draw (and of the reset ones otherwise)
             for a_, b_ in ((env._kp_scale, "kp_scale"), (env._kd_scale, "kd_scale"), (env._rfi_lim_scale, "rfi_lim_scale"), (env._rao_scale, "rao_scale")):
                 close(a_, orc.s[b_], 1e-7, w + b_)

@@ -7,12 +7,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import GOLDEN, build_hip_env, load_state_into_hip_env, state_dict_from_golden
-from tests.test_gpu_parity import ANGVEL, SLERP, angvel_tol, close
+from tests.helpers import GOLDEN, V2_SIGMA_OVERRIDES, build_hip_env, load_state_into_hip_env, state_dict_from_golden
+from tests.test_gpu_parity import ANGVEL, SLERP, angvel_tol, close, compare_log_block, sigma_and_ema_match_oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CASES = [("student23", "v2_g1_23dof_student.yaml", "g1_23dof"), ("teacher29", "v2_g1_29dof_teacher.yaml", "g1_29dof")]
+CASES = [("student23", "v2_g1_23dof_student.yaml", "g1_23dof"), ("teacher29", "v2_g1_29dof_teacher.yaml", "g1_29dof"),
+         ("student23_sigma", "v2_g1_23dof_student.yaml", "g1_23dof")]        # adaptive_tracking_sigma on, type "mean", alpha 0.05 (general_tracking.py:970-991)
 
 
 @pytest.mark.parametrize("tag,cfgname,robot", CASES)
@@ -28,7 +29,8 @@ def test_general_tracking_step_matches_reference_trace(tag, cfgname, robot):
     g, orc, oskel = build_oracle_v2(tag, cfgname, robot)
     orc.slot_clip = torch.zeros(orc.N, dtype=torch.long) if not hasattr(orc, "slot_clip") else orc.slot_clip
     T, N, D = g["actions_in"].shape
-    cfg, env = build_hip_env(cfgname, N, general=True, overrides={"domain_rand.push_robots": False})
+    cfg, env = build_hip_env(cfgname, N, general=True, overrides=dict({"domain_rand.push_robots": False}, **(V2_SIGMA_OVERRIDES if tag == "student23_sigma" else {})))
+    assert bool(env._c.adaptive_sigma) == (tag == "student23_sigma") and bool(orc.adaptive) == (tag == "student23_sigma")
     assert env.reward_names == list(g["reward_names"])
     assert env.key_body_id == list(g["key_body_id"]) and env.anchor_index == int(g["anchor_index"])
     load_state_into_hip_env(env, state_dict_from_golden(g), g)
@@ -82,6 +84,22 @@ def test_general_tracking_step_matches_reference_trace(tag, cfgname, robot):
         for lk in ["terminate_by_ref_pos_z", "terminate_by_ref_ori", "terminate_by_body_z", "terminate_by_time_out", "terminate_by_motion_end",
                    "key_body_diff_norm", "local_key_body_diff_norm", "local_upper_body_diff_norm", "joint_pos_diff_norm", "action_clip_frac"]:
             close(torch.tensor(log[lk]), g["step__log__" + lk][k], 1e-4, w + "log " + lk)
+        seen_reset = bool(g["step__reset_buf_out"][:k + 1].any())
+        checked = compare_log_block(log, g, k, seen_reset, w)
+        assert {"lower_body_diff_norm", "vr_3point_diff_norm", "local_lower_body_diff_norm", "local_vr_3point_diff_norm"} <= checked
+        assert not seen_reset or {"end_time_ratio", "end_time_ratio_std"} <= checked
+        from pbhc_amd.envs.env_config import SIGMA_KEYS
+        from pbhc_amd._lib import K
+
+        gl = env.globals.cpu().numpy()
+        for i, name in enumerate(SIGMA_KEYS):            # step__state__sigma__* / ema__* (the reference moves them only with the chain on)
+            for slot, pre in (("PBHC_G_SIGMA", "sigma__"), ("PBHC_G_EMA", "ema__")):
+                if "step__state__" + pre + name in g:
+                    ref = float(g["step__state__" + pre + name][k])
+                    assert abs(gl[K[slot] + i] - ref) <= 2e-6 * abs(ref), w + pre + name
+        if tag == "student23_sigma":                     # the chain ran: alpha 0.05 moved every EMA by far more than the tolerance
+            assert {"error_ema_" + n for n in orc.sigma} | {"adp_sigma_" + n for n in orc.sigma} <= checked or k + 1 == T
+            assert all(abs(float(g["step__state__ema__" + n][k]) - float(g["state0__ema__" + n])) > 1e-3 * float(g["state0__ema__" + n]) for n in orc.sigma)
 
 
 def _v2_algo(N, overrides=None, noise_off=True):
@@ -396,6 +414,7 @@ def _multi_clip_vs_oracle(N, T, M, library_seed=3):
         close(env.motion_len, orc.s["motion_len"], 1e-6, w + "motion_len")
         for name, view in env.history.items():
             close(view, orc.hist[name], 3e-5, w + "hist " + name)
+        sigma_and_ema_match_oracle(env, orc, w)
     assert nreset >= 48
 
 
