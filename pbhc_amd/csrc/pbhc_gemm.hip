@@ -523,6 +523,10 @@ __device__ __forceinline__ void gemm2_tile(const Gemm2Args& g, int bid, const in
           for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[k8 & 1][i][s], b[k8 & 1][j][s], acc[i][j], 0, 0, 0);
       // (s_setprio 1 / 3 around this block — favouring waves that are issuing MFMAs over co-resident waves in their prologue / epilogue —
       // measured in the update: 29.64 / 29.67 / 29.63 ms per update without / with priority 1 / 3: nothing)
+      // (the next stage's pieces one at a time behind MFMAs of these blocks instead of the burst above, and the loop rotated by one block so
+      // that barrier, waits and the first reads sit in front of MFMAs held in registers — built and measured, profiles/gemm_kloop_handover.txt:
+      // nothing at the kernel, -0.07 ... -0.12 ms per update at a spread of 0.06-0.2: the wave's MFMA-free interval is filled by the SIMD's
+      // other two waves)
     }
   };
 
