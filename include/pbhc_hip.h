@@ -1078,6 +1078,33 @@ int pbhc_debug_rotations(int fn, const float* a, const float* b, const float* c,
  * in double (out64 [n,3]) and — after rounding the quaternion to float — in float (out32 [n,3]); either output may be NULL. */
 int pbhc_debug_rotvec_host(const double* quat_xyzw, int n, double* out64, float* out32);
 
+/* The closed-loop joint-space simulator (pbhc_amd/simulator/joint_sim.py JointSpaceSim; k_joint_sim in csrc/pbhc_joint_sim.hip): ONE launch per control
+ * step on the stepping stream, directly in front of pbhc_env_step / pbhc_env_step_launch with the SAME env handle and io.  It writes the one-frame replay
+ * window the step then consumes through io->frame_* (io->num_frames must be 1, so frame_index 0 and the device cursor name the same frame):
+ *   joints  from io->dof_state (what the previous step left, resets included) `decimation` sub-steps of h = sim_dt of decoupled second-order dynamics
+ *           under the step's own PD law — the action clipped, the delayed action PEEKED from io->action_queue / action_delay_idx (the step still owns
+ *           and shifts the queue), the torque formula of legged_robot_base.py:795-838 re-evaluated with the current (q, v) in every sub-step, the RFI /
+ *           parallel_serial_tau draws of THIS control step (Philox streams 1 / 19 keyed with the globals' step counter, or io->u_rfi / io->ovr_ps_tau)
+ *           held over the sub-steps:  v <- (v + h tau / I_d) / (1 + h b_d / I_d),  q <- q + h v,  and with enforce_limits q clamped to
+ *           hard_dof_pos_limits with an outward v zeroed.  control_type "V" is refused.
+ *   root    the clip's root body at (episode_length_buf + 2) dt + motion_start_times (the step's own reference time, from the pre-step counter) with
+ *           pbhc_motion_state's lerp / slerp, + env_origins on the position.
+ *   contact contact_force (N) on z of a foot body when the clip's lerped contact mask is > 0.5 — or, for a library without masks, when the foot's
+ *           reference height is below foot_height_threshold — else 0; no other element of the contact frame is written (the caller zeroes it once).
+ * No gravity, no coupling between joints, no contact dynamics.  tau0 (may be NULL): device [N,D], the first sub-step's torque.
+ * NULL pointers, io->num_frames != 1, decimation outside [1, 64], an inertia <= 0 or a damping < 0 of a used dof return PBHC_EINVAL without a launch. */
+typedef struct PbhcJointSimParams {
+  float inertia[PBHC_MAX_DOF];    /* I_d  kg m^2 (armature included) */
+  float damping[PBHC_MAX_DOF];    /* b_d  N m s / rad, passive, taken implicitly */
+  float contact_force;
+  float foot_height_threshold;
+  int32_t enforce_limits;
+  int32_t decimation;
+  float* tau0;
+} PbhcJointSimParams;
+int pbhc_sizeof_joint_sim_params(void);
+int pbhc_joint_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcJointSimParams* params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

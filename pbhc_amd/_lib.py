@@ -93,6 +93,7 @@ PbhcMotionExtend = _S["PbhcMotionExtend"]
 PbhcMotionAugment = _S["PbhcMotionAugment"]
 PbhcMotionScreen = _S["PbhcMotionScreen"]
 PbhcMirrorJob = _S["PbhcMirrorJob"]
+PbhcJointSimParams = _S["PbhcJointSimParams"]
 
 EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
            "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
@@ -110,7 +111,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
            "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
            "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair",
-           "pbhc_mirror_rows", "pbhc_symmetry_loss"]
+           "pbhc_mirror_rows", "pbhc_symmetry_loss",
+           "pbhc_sizeof_joint_sim_params", "pbhc_joint_sim_step"]
 
 
 class PbhcError(RuntimeError):
@@ -128,7 +130,7 @@ def _load():
     if lib.pbhc_abi_version() != K["PBHC_ABI_VERSION"]:
         raise PbhcError("libpbhc_hip.so ABI version does not match include/pbhc_hip.h")
     if (lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO)
-            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO)):
+            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO) or lib.pbhc_sizeof_joint_sim_params() != C.sizeof(PbhcJointSimParams)):
         raise PbhcError("struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h — rebuild")
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     lib.pbhc_motion_build.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, f, vp, vp, vp]
@@ -187,6 +189,7 @@ def _load():
     lib.pbhc_debug_out_bwd_variant.argtypes = [i]
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]
     lib.pbhc_mirror_rows.argtypes = [C.POINTER(PbhcMirrorJob), i, i, vp]
+    lib.pbhc_joint_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcJointSimParams), vp]
     lib.pbhc_symmetry_loss.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp]
     lib.pbhc_debug_out_bwd_variant.restype = None
     lib.pbhc_linear_wgrad_parts.argtypes = [i, i, i]

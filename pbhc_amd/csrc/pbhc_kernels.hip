@@ -773,6 +773,14 @@ int pbhc_env_get_config(PbhcEnv* e, PbhcEnvConfig* out) {
   return PBHC_OK;
 }
 
+// for the library's other units (pbhc_joint_sim.hip; not part of the ABI): the parts of an env handle that a launch of theirs in front of the
+// step needs — the finalised config on the host and on the device, the motion table, the globals
+int pbhc_env_parts(PbhcEnv* e, const PbhcEnvConfig** host_cfg, const PbhcEnvConfig** dev_cfg, const PbhcMotionTable** tbl, double** glob) {
+  ARG_CHECK(e && host_cfg && dev_cfg && tbl && glob);
+  *host_cfg = &e->cfg; *dev_cfg = e->d_cfg; *tbl = &e->tbl; *glob = e->d_glob;
+  return PBHC_OK;
+}
+
 // config without the members k_env_step reads from the run-time copy even when specialised (pointers, env count, seed, reference yaw)
 static void strip_runtime_members(PbhcEnvConfig* c) {
   c->num_envs = 0; c->seed = 0; c->ref_init_yaw = 0.0f; c->map_image = nullptr;

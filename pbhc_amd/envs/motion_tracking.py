@@ -229,6 +229,8 @@ class LeggedRobotMotionTracking:
             self._ou_state.copy_(self._ou_stationary(N))
         self._init_save_motion()
         self._init_clip_statistics()
+        if hasattr(self.simulator, "bind"):         # a simulator that writes its own frames (JointSpaceSim): its window, its kernel's parameters
+            self.simulator.bind(self)
         self.init_done = True
 
     def specialise(self, mode="jit", verbose=False):
@@ -834,15 +836,20 @@ class LeggedRobotMotionTracking:
         del prev
         self._flush_statistics()
         fs = self._finalize_stream
+        advance = getattr(s, "advance", None)        # a closed-loop simulator writes this step's frame directly in front of the step launch
         if self._fin_deferred:
             # the fused launch only: its reduction is owed (set_finalize_deferred) — taken over by the caller's next launch on this stream, or
             # flushed before the next step / the next reader of the globals
             st = _lib.current_stream()
+            if advance is not None:
+                advance(self)
             _lib.check(self._lib.pbhc_env_step_launch(self._env, C.byref(io), st), "pbhc_env_step_launch")
             if self._rec is not None:                # the recorder needs the step's per-env outputs only, not its reduction
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), st), "pbhc_record_motion")
             self._fin_owed = True
         elif fs is None:
+            if advance is not None:
+                advance(self)
             _lib.check(self._lib.pbhc_env_step(self._env, C.byref(io), _lib.current_stream()), "pbhc_env_step")
             if self._rec is not None:
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), _lib.current_stream()), "pbhc_record_motion")
@@ -855,6 +862,8 @@ class LeggedRobotMotionTracking:
             # the policy forward of the new observations; the reduction is joined again before the next launch (wait_finalize)
             cur = torch.cuda.current_stream()
             self.wait_finalize()
+            if advance is not None:
+                advance(self)
             _lib.check(self._lib.pbhc_env_step_launch(self._env, C.byref(io), cur.cuda_stream), "pbhc_env_step_launch")
             if self._rec is not None:                # the recorder needs the step's per-env outputs only, not its reduction
                 _lib.check(self._lib.pbhc_record_motion(self._env, C.byref(io), C.byref(self._rec_io), cur.cuda_stream), "pbhc_record_motion")

@@ -1,0 +1,109 @@
+#!/usr/bin/env python
+"""Train MHPPO in the closed loop of JointSpaceSim (pbhc_amd/simulator/joint_sim.py) and print whether the tracking error moves.
+
+    python tools/closed_loop_train.py --config tests/golden/configs/v1_g1_23dof_walk.yaml --envs 1024 --iters 300 --sim joint
+
+Its own loop, not bench.py: rollout (timed with an event pair) -> update, and per iteration one line with
+    joint_diff   the batch mean of |dif_joint_angles| (rad) of the rollout's last step, as the step kernel logs it (joint_pos_diff_norm)
+    r_joint_pos  the batch mean of the joint-position reward term exp(-mean(dif^2) / sigma) of that step, over the envs that did not reset in
+                 it, recomputed here from the state the step left and the adaptive sigma it used
+    rollout_ms   the rollout's time on the device
+`--sim replay` runs the same loop on ReplaySimStub with a synthetic replay window, where actions do not move the state: the reference point
+for rollout_ms, and the control for the two tracking figures (they must NOT move there).
+
+The joint simulator is no physics engine (no gravity, no coupling between joints, no contact dynamics; the root rides the clip): a falling
+error here shows that the loop action -> torque -> joint state -> observation -> reward is closed and that PPO can use it, nothing more.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def build(args):
+    from pbhc_amd.agents.mh_ppo import MHPPO
+    from pbhc_amd.envs.motion_tracking import LeggedRobotMotionTracking
+    from pbhc_amd.utils.config import load_config
+
+    ov = {"num_envs": args.envs}
+    if args.sim == "joint":
+        ov["simulator._target_"] = "pbhc_amd.simulator.joint_sim.JointSpaceSim"
+        inertia = "subtree" if args.inertia == "subtree" else float(args.inertia)
+        ov["simulator.config.joint_sim"] = {"inertia": inertia, "armature": args.armature, "damping": args.damping}
+        if args.mjcf:                                         # "subtree" needs the link masses: the skeleton from the MJCF
+            ov["robot.motion.asset.assetFileName"] = args.mjcf
+    else:
+        ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
+    cfg = load_config(args.config, ov, now="closed_loop")
+    torch.manual_seed(args.seed)
+    env = LeggedRobotMotionTracking(cfg.env.config, args.device)
+    algo = MHPPO(env=env, config=cfg.algo.config, log_dir=None, device=args.device)
+    algo.setup()
+    return cfg, env, algo
+
+
+def tracking_figures(env):
+    log = env.read_log()
+    keep = env.reset_buf == 0
+    qref = env._motion_lib.get_motion_state(env.motion_ids, env._ref_time, offset=env.env_origins)["dof_pos"]
+    err = ((qref - env.simulator.dof_pos) ** 2).mean(dim=1)
+    r = torch.exp(-err / float(log["adp_sigma_teleop_joint_pos"]))
+    r = float(r[keep].mean()) if bool(keep.any()) else float("nan")
+    return float(log["joint_pos_diff_norm"]), r, float(log["average_episode_length"])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default=os.path.join(ROOT, "tests", "golden", "configs", "v1_g1_23dof_walk.yaml"))
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--sim", choices=("joint", "replay"), default="joint")
+    ap.add_argument("--inertia", default="subtree", help='"subtree" or one number (kg m^2) for every joint')
+    ap.add_argument("--armature", type=float, default=0.02)
+    ap.add_argument("--damping", type=float, default=0.05)
+    ap.add_argument("--mjcf", default="mjcf/g1_23dof_lock_wrist_fitmotionONLY.xml", help="robot.motion.asset.assetFileName for --sim joint ('' keeps the config's)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--print-every", type=int, default=1)
+    args = ap.parse_args()
+
+    cfg, env, algo = build(args)
+    algo._train_mode()
+    obs = env.reset_all()
+    if args.sim == "replay":
+        import bench
+
+        env.simulator.set_replay(*bench.make_replay_on_device(env, algo.num_steps_per_env * 8 + 3, seed=99))
+    else:
+        print("# inertia (kg m^2): " + " ".join(f"{v:.4f}" for v in env.simulator.inertia))
+    print(f"# sim {args.sim}, {args.envs} envs, {algo.num_steps_per_env} steps per rollout, {args.iters} iterations")
+    print("# iter joint_diff r_joint_pos avg_ep_len rollout_ms graph")
+    times, first, last = [], None, None
+    for it in range(args.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        algo.storage.clear()
+        e0.record()
+        obs = algo._rollout_step(obs)
+        e1.record()
+        algo._training_step()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1)
+        jd, rj, epl = tracking_figures(env)
+        if it >= 2:
+            times.append(ms)
+        first = (jd, rj) if first is None else first
+        last = (jd, rj)
+        if it % args.print_every == 0 or it == args.iters - 1:
+            print(f"{it:5d} {jd:.5f} {rj:.5f} {epl:8.2f} {ms:8.3f} {int(bool(getattr(algo, '_rollout_used_graph', False)))}", flush=True)
+    if times:
+        print(f"# rollout_ms median {statistics.median(times):.3f} min {min(times):.3f} max {max(times):.3f} over {len(times)} iterations")
+    print(f"# joint_diff {first[0]:.5f} -> {last[0]:.5f}   r_joint_pos {first[1]:.5f} -> {last[1]:.5f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,72 @@
+"""k_joint_sim under the profiler, next to the two kernels of the same mapping (k_dof_far_any, k_clip_stats).
+
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/joint_sim_probe.py steps ENVS [joint|replay]
+        reset_all + 20 control steps of the v1 walk config on one stream with terminate_when_dof_far and clip_statistics on: per step one
+        k_joint_sim (joint only), one k_dof_far_any, one k_env_step, one k_env_finalize and one k_clip_stats dispatch
+  python3 tools/joint_sim_probe.py summary DIR [DIR ...]
+        per directory: dispatches, median and minimum (microseconds) of those kernels
+"""
+import csv
+import glob
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+KERNELS = ("k_joint_sim", "k_dof_far_any", "k_clip_stats", "k_env_step", "k_env_finalize")
+
+
+def steps(num_envs, sim):
+    import torch
+
+    import bench
+    from pbhc_amd.envs.motion_tracking import LeggedRobotMotionTracking
+    from pbhc_amd.utils.config import load_config
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ov = {"num_envs": num_envs, "env.config.clip_statistics": True, "env.config.termination.terminate_when_dof_far": True}
+    if sim == "joint":
+        ov.update({"simulator._target_": "pbhc_amd.simulator.joint_sim.JointSpaceSim",
+                   "simulator.config.joint_sim": {"inertia": 0.1, "damping": 0.05}})
+    else:
+        ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
+    cfg = load_config(os.path.join(root, "tests", "golden", "configs", "v1_g1_23dof_walk.yaml"), ov, now="probe")
+    torch.manual_seed(0)
+    env = LeggedRobotMotionTracking(cfg.env.config, "cuda:0")
+    env.reset_all()
+    if sim != "joint":
+        env.simulator.set_replay(*bench.make_replay_on_device(env, 24, seed=1))
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    for _ in range(20):
+        env.step({"actions": torch.randn(num_envs, env.num_dof, device="cuda:0", generator=g)})
+    torch.cuda.synchronize()
+    print(f"envs {num_envs}, sim {sim}: specialised={env.is_specialised}, joint_pos_diff_norm {float(env.read_log()['joint_pos_diff_norm']):.4f}")
+
+
+def summary(dirs):
+    for d in dirs:
+        rows = {k: [] for k in KERNELS}
+        for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+            with open(path) as f:
+                for r in csv.DictReader(f):
+                    name = r["Kernel_Name"]
+                    for k in KERNELS:
+                        if k in name:
+                            rows[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0)
+        print(d)
+        for k in KERNELS:
+            v = rows[k]
+            if v:
+                print(f"  {k:16s} dispatches {len(v):4d}  median {statistics.median(v):7.2f} us  min {min(v):7.2f} us")
+            else:
+                print(f"  {k:16s} dispatches    0")
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "steps":
+        steps(int(sys.argv[2]), sys.argv[3] if len(sys.argv) > 3 else "joint")
+    elif sys.argv[1] == "summary":
+        summary(sys.argv[2:])
+    else:
+        raise SystemExit(__doc__)
