@@ -1105,6 +1105,65 @@ typedef struct PbhcJointSimParams {
 int pbhc_sizeof_joint_sim_params(void);
 int pbhc_joint_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcJointSimParams* params, void* stream);
 
+/* Retargeting at ingestion (pbhc_amd/motion_retarget.py; csrc/pbhc_retarget.hip; definition: DESIGN §8 "Retargeting"; reference:
+ * smpl_retarget/phc_retarget/fit_smpl_motion.py:137-179).  M clips concatenated: `starts` is the HOST array int32 [M + 1] (checked before any
+ * launch), `d_starts` its device copy; every other array is a device pointer.  keypoints [total, P, 3] world-frame targets of the bodies
+ * pick[0..P-1] (indices into the extended body list), trans [total, 3], dof [total, D], root_rot [total, 3] rotation vectors, root_off [M, 3].
+ *   loss of clip c   = mean over (frame, pick) of |p_pick - target|, body positions by pbhc_motion_build's FK of
+ *                      pose_aa = [root_rot, dof_axis[d] * dof[d], 0 for the extended bodies] rooted at trans + root_off[c].
+ *   pbhc_retarget_loss_grad   loss_out [M] and the analytic gradients g_dof [total, D], g_root_rot [total, 3], g_root_off [M, 3]; no update.
+ *                             body_pos_out [total, Bx, 3] or NULL; scratch: 4 * total floats.
+ *   pbhc_retarget_fit         `iterations` iterations from the state it is handed, all enqueued on `stream` with no synchronisation: dof takes
+ *                             torch's Adadelta step (dof_lr, rho, adadelta_eps), root_rot and root_off torch's Adam step (root_lr, beta1, beta2,
+ *                             adam_eps), dof is clamped to `limits` and smoothed along time by `filter_taps` (5, or 0 = off) Gaussian taps of
+ *                             `filter_sigma` frames, edge-replicated inside the clip.  loss_history [iterations, M]: the loss before each
+ *                             update.  state->step (Adam's step count) advances by `iterations`: k, then n - k iterations equal n.
+ *                             state->scratch: (D + 4) * total floats.
+ *   pbhc_retarget_finish      clamps state->dof once more and writes pose_aa_out [total, Bx, 3], root_trans_out = trans + root_off [total, 3],
+ *                             root_quat_out [total, 4] xyzw.
+ * Sums run in pick order inside a frame and in an order fixed by the clip's own frame count across frames, with no atomics: a clip fitted
+ * alone and inside a batch gives the same bits.  num_picks outside 1..PBHC_MAX_BODIES, a pick outside [0, Bx), filter_taps not 0 or 5, a
+ * limit with lo > hi, total != starts[M], a clip of 0 frames, iterations < 1, NULL pointers return PBHC_EINVAL without a launch. */
+typedef struct PbhcRetargetParams {
+  int32_t num_picks;
+  int32_t pick[PBHC_MAX_BODIES];
+  float dof_lr;
+  float root_lr;
+  float rho;
+  float adadelta_eps;
+  float beta1;
+  float beta2;
+  float adam_eps;
+  int32_t filter_taps;
+  float filter_sigma;
+  float limits[PBHC_MAX_DOF][2];
+} PbhcRetargetParams;
+typedef struct PbhcRetargetState {
+  float* dof;        /* [total, D] */
+  float* dof_sq;     /* [total, D] Adadelta square_avg */
+  float* dof_acc;    /* [total, D] Adadelta acc_delta */
+  float* root_rot;   /* [total, 3] */
+  float* root_m;     /* [total, 3] Adam exp_avg */
+  float* root_v;     /* [total, 3] Adam exp_avg_sq */
+  float* root_off;   /* [M, 3] */
+  float* off_m;      /* [M, 3] */
+  float* off_v;      /* [M, 3] */
+  float* scratch;    /* [(D + 4) * total] */
+  int32_t step;      /* Adam steps taken so far */
+} PbhcRetargetState;
+int pbhc_sizeof_retarget_params(void);
+int pbhc_sizeof_retarget_state(void);
+int pbhc_retarget_loss_grad(const PbhcSkeleton* skel, const PbhcRetargetParams* params, const float* keypoints, const float* trans,
+                            const float* dof, const float* root_rot, const float* root_off, int total, int num_clips, const int32_t* starts,
+                            const int32_t* d_starts, float* loss_out, float* g_dof, float* g_root_rot, float* g_root_off, float* body_pos_out,
+                            float* scratch, void* stream);
+int pbhc_retarget_fit(const PbhcSkeleton* skel, const PbhcRetargetParams* params, const float* keypoints, const float* trans, int total,
+                      int num_clips, const int32_t* starts, const int32_t* d_starts, PbhcRetargetState* state, int iterations,
+                      float* loss_history, void* stream);
+int pbhc_retarget_finish(const PbhcSkeleton* skel, const PbhcRetargetParams* params, const float* trans, int total, int num_clips,
+                         const int32_t* starts, const int32_t* d_starts, PbhcRetargetState* state, float* pose_aa_out, float* root_trans_out,
+                         float* root_quat_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

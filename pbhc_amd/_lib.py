@@ -94,6 +94,8 @@ PbhcMotionAugment = _S["PbhcMotionAugment"]
 PbhcMotionScreen = _S["PbhcMotionScreen"]
 PbhcMirrorJob = _S["PbhcMirrorJob"]
 PbhcJointSimParams = _S["PbhcJointSimParams"]
+PbhcRetargetParams = _S["PbhcRetargetParams"]
+PbhcRetargetState = _S["PbhcRetargetState"]
 
 EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
            "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
@@ -112,7 +114,8 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
            "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair",
            "pbhc_mirror_rows", "pbhc_symmetry_loss",
-           "pbhc_sizeof_joint_sim_params", "pbhc_joint_sim_step"]
+           "pbhc_sizeof_joint_sim_params", "pbhc_joint_sim_step",
+           "pbhc_sizeof_retarget_params", "pbhc_sizeof_retarget_state", "pbhc_retarget_loss_grad", "pbhc_retarget_fit", "pbhc_retarget_finish"]
 
 
 class PbhcError(RuntimeError):
@@ -130,7 +133,8 @@ def _load():
     if lib.pbhc_abi_version() != K["PBHC_ABI_VERSION"]:
         raise PbhcError("libpbhc_hip.so ABI version does not match include/pbhc_hip.h")
     if (lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO)
-            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO) or lib.pbhc_sizeof_joint_sim_params() != C.sizeof(PbhcJointSimParams)):
+            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO) or lib.pbhc_sizeof_joint_sim_params() != C.sizeof(PbhcJointSimParams)
+            or lib.pbhc_sizeof_retarget_params() != C.sizeof(PbhcRetargetParams) or lib.pbhc_sizeof_retarget_state() != C.sizeof(PbhcRetargetState)):
         raise PbhcError("struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h — rebuild")
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     lib.pbhc_motion_build.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, f, vp, vp, vp]
@@ -190,6 +194,10 @@ def _load():
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]
     lib.pbhc_mirror_rows.argtypes = [C.POINTER(PbhcMirrorJob), i, i, vp]
     lib.pbhc_joint_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcJointSimParams), vp]
+    _rt = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcRetargetParams)]
+    lib.pbhc_retarget_loss_grad.argtypes = _rt + [vp] * 5 + [i, i, vp, vp] + [vp] * 6 + [vp]
+    lib.pbhc_retarget_fit.argtypes = _rt + [vp, vp, i, i, vp, vp, C.POINTER(PbhcRetargetState), i, vp, vp]
+    lib.pbhc_retarget_finish.argtypes = _rt + [vp, i, i, vp, vp, C.POINTER(PbhcRetargetState), vp, vp, vp, vp]
     lib.pbhc_symmetry_loss.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp]
     lib.pbhc_debug_out_bwd_variant.restype = None
     lib.pbhc_linear_wgrad_parts.argtypes = [i, i, i]

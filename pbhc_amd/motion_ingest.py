@@ -1,6 +1,6 @@
 """The motion library's ingestion pipeline: host clip dicts -> one `ClipBatch` on the device -> packed table rows.
 
-    upload -> [screen] -> [augment] -> [extend] -> build
+    [retarget] -> upload -> [screen] -> [augment] -> [extend] -> build
 
 Every stage is a plain function from a batch to a batch (`build`: to the rows); the settings objects (`motion_screen`, `motion_augment`,
 `motion_interp`) say what a stage does, this module is how its one launch is fed.  `MotionLib`, the export tools and the probes all run
@@ -69,6 +69,26 @@ class ClipBatch:
             if contact is not None:
                 out[-1]["contact_mask"] = contact.copy()
         return out
+
+
+def retarget(clips, skeleton, device, settings):
+    """The first stage, `robot.motion.retarget`: the clip dicts that hold `keypoints` and no `pose_aa` are fitted in ONE batch
+    (`motion_retarget.fit`) and become ordinary clips (pose_aa, root_trans_offset, fps; no contact_mask, so that `contact_detection` can
+    derive it); every other clip passes through as the object it is.  settings None or not enabled: the list as given, no launch.
+    -> (clips, report or None); report: `clips` (indices of the fitted clips), `first_loss`, `last_loss` [fitted] in metres."""
+    if settings is None or not settings.active:
+        return clips, None
+    todo = [i for i, c in enumerate(clips) if "keypoints" in c and "pose_aa" not in c]
+    if not todo:
+        return clips, dict(clips=np.zeros(0, np.int64), first_loss=np.zeros(0), last_loss=np.zeros(0))
+    from . import motion_retarget
+
+    batch, _, _, hist = motion_retarget.fit([clips[i] for i in todo], skeleton, settings, device)
+    hist = hist.cpu().numpy().astype(np.float64)
+    out = list(clips)
+    for i, fitted in zip(todo, batch.to_host_clips()):
+        out[i] = fitted
+    return out, dict(clips=np.asarray(todo, np.int64), first_loss=hist[0], last_loss=hist[-1])
 
 
 def _csk(skeleton):

@@ -8,7 +8,7 @@ motion_lib_robot_WJX.py:146-293).  Differences by design:
 * all per-frame quantities live in ONE packed row per frame
   `[dof_pos D | dof_vel D | contact 2 | pos Bx*3 | rot Bx*4 | vel Bx*3 | ang Bx*3]`
   so a lookup reads two contiguous rows.
-Ingestion (`motion_ingest`): upload -> screen (contact masks, stability) -> augment (variants) -> extend (lead-in / lead-out frames) ->
+Ingestion (`motion_ingest`): retarget (key-point clips -> joint angles) -> upload -> screen (contact masks, stability) -> augment (variants) -> extend (lead-in / lead-out frames) ->
 build (FK tables); a stage whose key is absent is skipped.
 Motion files: the reference's joblib .pkl (read by the static, non-executing parser
 `pbhc_amd.utils.safe_pkl`) or an .npz with the same arrays.
@@ -24,6 +24,7 @@ import torch
 from . import _lib, motion_ingest
 from .motion_augment import Augmentation, mirror_tables
 from .motion_interp import Interpolation
+from .motion_retarget import RetargetSettings
 from .motion_screen import ContactDetection, Screening
 from .utils import resume, rng_state, safe_pkl
 
@@ -84,7 +85,7 @@ def rebase_heading(clip, target_heading):
 
 class MotionLib:
     def __init__(self, skeleton, clips, num_envs, device, max_len=-1, interpolation=None, augmentation=None, contact_detection=None,
-                 screening=None):
+                 screening=None, retarget=None):
         """clips: list of clip dicts (see load_motion_file).  max_len > 0: `load_motions` gives every env slot its own random crop of at most
         `max_len` frames of its clip (motion_lib_base.py:420-428) — the tables are then per SLOT (num_envs entries of max_len rows, allocated
         once so that the step kernel's pointers stay valid) instead of per unique clip.
@@ -95,7 +96,10 @@ class MotionLib:
         augmentation (motion_augment.Augmentation): every clip becomes V clips — itself, its mirror image, time-scaled copies: clip
         src * V + v is variant v of source clip src (`variant_source`, `variant_info`); everything downstream sees M * V ordinary clips.
         interpolation (motion_interp.Interpolation): every clip is cut to [clip_start:clip_end] on the host, first of all, and gets lead-in /
-        lead-out frames from / to a default pose: lengths, tables and crops describe the extended clips."""
+        lead-out frames from / to a default pose: lengths, tables and crops describe the extended clips.
+        retarget (motion_retarget.RetargetSettings): before everything else, the clips that hold `keypoints` and no `pose_aa` are fitted on
+        the device and become ordinary clips; `retarget_report` holds their indices and first / last loss."""
+        clips, self.retarget_report = motion_ingest.retarget(clips, skeleton, device, retarget)
         if interpolation is not None:
             if interpolation.num_dof != skeleton.num_dof:
                 raise _lib.PbhcError(f"interpolation was set up for {interpolation.num_dof} dofs, the skeleton has {skeleton.num_dof}")
@@ -270,7 +274,8 @@ class MotionLib:
         """mcfg = config.robot.motion (motion_file = .pkl / .npz / directory); max_len: see __init__.  mcfg.interpolation (absent by default):
         see motion_interp.Interpolation.from_config; robot = config.robot supplies its default joints and the dof names.  mcfg.augmentation
         (absent by default): see motion_augment.Augmentation.from_config.  mcfg.contact_detection, mcfg.screening (absent by default): see
-        motion_screen.ContactDetection.from_config / Screening.from_config."""
+        motion_screen.ContactDetection.from_config / Screening.from_config.  mcfg.retarget (absent by default): see
+        motion_retarget.RetargetSettings.from_config; `limits: mjcf` reads the asset's MJCF."""
         path = str(mcfg.motion_file)
         if not os.path.isabs(path) and not os.path.exists(path):
             path = os.path.join(_lib.ROOT, path)
@@ -281,7 +286,14 @@ class MotionLib:
         if augmentation is not None and augmentation.active and mcfg.get("motion_lib_type", "origin") == "WJX":
             raise _lib.PbhcError("robot.motion.augmentation with motion_lib_type WJX: a v1 library is ONE clip, the variants would make it "
                                  f"{augmentation.num_variants}")
-        return cls(skeleton, clips, num_envs, device, max_len=max_len, augmentation=augmentation,
+        rnode, mjcf = mcfg.get("retarget", None), None
+        if rnode is not None and rnode.get("enable", False) and rnode.get("limits", "mjcf") == "mjcf":
+            mjcf = os.path.join(str(mcfg.asset.assetRoot), str(mcfg.asset.assetFileName))   # the asset the skeleton came from, when an MJCF
+            if not os.path.isabs(mjcf) and not os.path.exists(mjcf):
+                mjcf = os.path.join(_lib.ROOT, mjcf)
+            mjcf = mjcf if mjcf.endswith(".xml") else None
+        retarget = RetargetSettings.from_config(rnode, mjcf=mjcf)
+        return cls(skeleton, clips, num_envs, device, max_len=max_len, augmentation=augmentation, retarget=retarget,
                    interpolation=Interpolation.from_config(mcfg.get("interpolation", None), skeleton.num_dof, robot=robot),
                    contact_detection=ContactDetection.from_config(mcfg.get("contact_detection", None)),
                    screening=Screening.from_config(mcfg.get("screening", None)))
