@@ -1105,6 +1105,44 @@ typedef struct PbhcJointSimParams {
 int pbhc_sizeof_joint_sim_params(void);
 int pbhc_joint_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcJointSimParams* params, void* stream);
 
+/* The articulated rigid-body simulator (pbhc_amd/simulator/articulated_sim.py ArticulatedSim; k_articulated_sim in csrc/pbhc_articulated_sim.hip): the
+ * same place in the step, the same one-frame window, root, contact, torque law and draws as pbhc_joint_sim_step — only the joint law differs.  The robot's
+ * tree (kinematics exactly pbhc_sim_fk's: R_b = R_parent local_rot_b Rot(axis_{b-1}, q_{b-1}), p_b = p_parent + R_parent offset_b, hinge d drives body
+ * d + 1 about an axis through that body's origin) carries link masses, centres of mass and inertia tensors (body frame, about the centre of mass, the six
+ * words xx yy zz xy xz yz).  The base is prescribed (the root row the kernel writes; constant over the sub-steps): R_0, w_0 and, with base_acceleration,
+ * a_0 = (v(tref) - v(tref - dt)) / dt and alpha_0 likewise from the angular velocity (else 0); gravity enters as a_0 - g.  Every sub-step, h = sim_dt:
+ *   tau from the current (q, v) by the step's torque law;  (M(q) + diag(armature + h b)) dv = h (tau - b v - c(q, v; R_0, w_0, alpha_0, a_0 - g));
+ *   v <- v + dv;  q <- q + h v;  with enforce_limits the clamp of pbhc_joint_sim_step.
+ * M: the joint-space inertia matrix at THIS sub-step's q; c: the inverse dynamics at q'' = 0.  No free root, no contact dynamics.
+ * tau0 (may be NULL): device [N,D], the first sub-step's torque.  base_acc (may be NULL): device [N,6], the a_0 and alpha_0 the kernel used.
+ * NULL pointers, io->num_frames != 1, B > PBHC_ART_MAX_BODIES, decimation outside [1, 64], a negative armature, damping or mass, control type "V"
+ * return PBHC_EINVAL without a launch. */
+#define PBHC_ART_MAX_BODIES 32
+typedef struct PbhcArticulatedParams {
+  float mass[PBHC_ART_MAX_BODIES];          /* m_b  kg; the root's entry is not used (the base is prescribed) */
+  float com[PBHC_ART_MAX_BODIES][3];        /* c_b  m, body frame */
+  float inertia[PBHC_ART_MAX_BODIES][6];    /* I_b  kg m^2 about the centre of mass, body frame: xx yy zz xy xz yz */
+  float armature[PBHC_MAX_DOF];             /* kg m^2, added to the diagonal of M */
+  float damping[PBHC_MAX_DOF];              /* b_d  N m s / rad, passive, taken implicitly */
+  float gravity[3];                         /* m / s^2, world */
+  int32_t base_acceleration;
+  float contact_force;
+  float foot_height_threshold;
+  int32_t enforce_limits;
+  int32_t decimation;
+  float* tau0;
+  float* base_acc;
+} PbhcArticulatedParams;
+int pbhc_sizeof_articulated_params(void);
+int pbhc_articulated_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcArticulatedParams* params, void* stream);
+/* Test-only: `steps` sub-steps of h seconds of the SAME device function as k_articulated_sim under a constant torque, n independent robots.
+ * base [n,13]: R_0 as a quaternion xyzw, w_0, alpha_0, a_0 (gravity is taken from params); q, v, tau [n,D]; limits: HOST [D,2], read only with
+ * enforce_limits; out_q, out_v [n,D] the final state, out_qdd0 [n,D] the first sub-step's dv / h.  steps outside [1, 4096], h <= 0, NULL pointers,
+ * a skeleton over the maxima, a negative armature, damping or mass return PBHC_EINVAL without a launch. */
+int pbhc_debug_articulated_substeps(const PbhcSkeleton* skel, const PbhcArticulatedParams* params, const float* base, const float* q, const float* v,
+                                    const float* tau, int n, int steps, float h, int enforce_limits, const float* limits, float* out_q, float* out_v,
+                                    float* out_qdd0, void* stream);
+
 /* Retargeting at ingestion (pbhc_amd/motion_retarget.py; csrc/pbhc_retarget.hip; definition: DESIGN §8 "Retargeting"; reference:
  * smpl_retarget/phc_retarget/fit_smpl_motion.py:137-179).  M clips concatenated: `starts` is the HOST array int32 [M + 1] (checked before any
  * launch), `d_starts` its device copy; every other array is a device pointer.  keypoints [total, P, 3] world-frame targets of the bodies

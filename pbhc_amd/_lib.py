@@ -94,6 +94,7 @@ PbhcMotionAugment = _S["PbhcMotionAugment"]
 PbhcMotionScreen = _S["PbhcMotionScreen"]
 PbhcMirrorJob = _S["PbhcMirrorJob"]
 PbhcJointSimParams = _S["PbhcJointSimParams"]
+PbhcArticulatedParams = _S["PbhcArticulatedParams"]
 PbhcRetargetParams = _S["PbhcRetargetParams"]
 PbhcRetargetState = _S["PbhcRetargetState"]
 
@@ -115,6 +116,7 @@ EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbh
            "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair",
            "pbhc_mirror_rows", "pbhc_symmetry_loss",
            "pbhc_sizeof_joint_sim_params", "pbhc_joint_sim_step",
+           "pbhc_sizeof_articulated_params", "pbhc_articulated_sim_step", "pbhc_debug_articulated_substeps",
            "pbhc_sizeof_retarget_params", "pbhc_sizeof_retarget_state", "pbhc_retarget_loss_grad", "pbhc_retarget_fit", "pbhc_retarget_finish"]
 
 
@@ -134,6 +136,7 @@ def _load():
         raise PbhcError("libpbhc_hip.so ABI version does not match include/pbhc_hip.h")
     if (lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO)
             or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO) or lib.pbhc_sizeof_joint_sim_params() != C.sizeof(PbhcJointSimParams)
+            or lib.pbhc_sizeof_articulated_params() != C.sizeof(PbhcArticulatedParams)
             or lib.pbhc_sizeof_retarget_params() != C.sizeof(PbhcRetargetParams) or lib.pbhc_sizeof_retarget_state() != C.sizeof(PbhcRetargetState)):
         raise PbhcError("struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h — rebuild")
     vp, i, f = C.c_void_p, C.c_int, C.c_float
@@ -194,6 +197,8 @@ def _load():
     lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]
     lib.pbhc_mirror_rows.argtypes = [C.POINTER(PbhcMirrorJob), i, i, vp]
     lib.pbhc_joint_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcJointSimParams), vp]
+    lib.pbhc_articulated_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcArticulatedParams), vp]
+    lib.pbhc_debug_articulated_substeps.argtypes = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcArticulatedParams), vp, vp, vp, vp, i, i, f, i, vp, vp, vp, vp, vp]
     _rt = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcRetargetParams)]
     lib.pbhc_retarget_loss_grad.argtypes = _rt + [vp] * 5 + [i, i, vp, vp] + [vp] * 6 + [vp]
     lib.pbhc_retarget_fit.argtypes = _rt + [vp, vp, i, i, vp, vp, C.POINTER(PbhcRetargetState), i, vp, vp]

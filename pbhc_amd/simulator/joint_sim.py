@@ -33,16 +33,16 @@ from .replay_stub import ReplaySimStub
 KEY = "simulator.config.joint_sim"
 
 
-def _per_dof(value, D, name):
+def _per_dof(value, D, name, key=KEY):
     """scalar or list of D -> float64 [D]; a list of another length is refused by name"""
     if isinstance(value, (int, float)) and not isinstance(value, bool):
         return np.full(D, float(value), np.float64)
     try:
         v = [float(x) for x in value]
     except (TypeError, ValueError):
-        raise _lib.PbhcError(f"{KEY}.{name}: expected a number or a list of {D} numbers, got {value!r}") from None
+        raise _lib.PbhcError(f"{key}.{name}: expected a number or a list of {D} numbers, got {value!r}") from None
     if len(v) != D:
-        raise _lib.PbhcError(f"{KEY}.{name}: a list must have one entry per dof ({D}), got {len(v)}")
+        raise _lib.PbhcError(f"{key}.{name}: a list must have one entry per dof ({D}), got {len(v)}")
     return np.asarray(v, np.float64)
 
 
@@ -195,13 +195,7 @@ class JointSpaceSim(ReplaySimStub):
             rb = rb[0].double().cpu().numpy()
             self.inertia = self._checked_inertia(subtree_inertia(self.skeleton, rb[:, 0:3], rb[:, 3:7], self._armature), self.dof_names)
             self._check_stability(self.config, self.inertia)
-        # contact is zeroed ONCE, here: the kernel writes z of the foot bodies and nothing else
-        self.replay = dict(root=self.robot_root_states.clone()[None].contiguous(), dof_pos=self.dof_pos.clone()[None].contiguous(),
-                           dof_vel=self.dof_vel.clone()[None].contiguous(), contact=torch.zeros(1, N, B, 3, device=dev))
-        self.replay_len = 1
-        self.frame_cursor.zero_()
-        self._host_frame = 0
-        self.replay_version += 1
+        self._bind_window()
         p = _lib.PbhcJointSimParams()
         for d in range(D):
             p.inertia[d], p.damping[d] = float(self.inertia[d]), float(self._damping[d])
@@ -209,6 +203,17 @@ class JointSpaceSim(ReplaySimStub):
         p.enforce_limits, p.decimation = int(self.enforce_limits), int(self.decimation)
         p.tau0 = None
         self._params = p
+
+    def _bind_window(self):
+        """the one-frame window the simulator's kernel writes and the step reads"""
+        N, B, dev = self.num_envs, self.num_bodies, self.device
+        # contact is zeroed ONCE, here: the kernel writes z of the foot bodies and nothing else
+        self.replay = dict(root=self.robot_root_states.clone()[None].contiguous(), dof_pos=self.dof_pos.clone()[None].contiguous(),
+                           dof_vel=self.dof_vel.clone()[None].contiguous(), contact=torch.zeros(1, N, B, 3, device=dev))
+        self.replay_len = 1
+        self.frame_cursor.zero_()
+        self._host_frame = 0
+        self.replay_version += 1
 
     def set_debug_torques(self, on=True):
         """keep the first sub-step's torque of every control step in `self.tau0 [N, D]` (what the step reports as `torques`)"""

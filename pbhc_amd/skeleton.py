@@ -17,6 +17,24 @@ import numpy as np
 from . import _lib
 
 
+def _inertia_tensor(inertial):
+    """<inertial>'s tensor about the centre of mass in the body frame, float64 [3,3]: MuJoCo's `fullinertia` (xx yy zz xy xz yz), or
+    R(quat) diag(diaginertia) R(quat)^T with `quat` (wxyz) the orientation of the principal axes; a body without <inertial> gets zeros"""
+    if inertial is None:
+        return np.zeros((3, 3))
+    if "fullinertia" in inertial.attrib:
+        xx, yy, zz, xy, xz, yz = (float(x) for x in inertial.attrib["fullinertia"].split())
+        return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+    d = np.array([float(x) for x in inertial.attrib.get("diaginertia", "0 0 0").split()])
+    w, x, y, z = (float(v) for v in inertial.attrib.get("quat", "1 0 0 0").split())
+    n = np.sqrt(w * w + x * x + y * y + z * z)
+    w, x, y, z = w / n, x / n, y / n, z / n
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    return R @ np.diag(d) @ R.T
+
+
 @dataclass
 class Skeleton:
     body_names: list
@@ -28,6 +46,7 @@ class Skeleton:
     depth: np.ndarray = field(default=None)
     body_mass: np.ndarray = field(default=None)   # [B] link masses in kg, or None (only the MJCF holds them)
     body_com: np.ndarray = field(default=None)    # [B,3] centre of mass of every link in its own frame, or None
+    body_inertia: np.ndarray = field(default=None)   # [B,3,3] inertia tensor of every link about its centre of mass, in its own frame, or None
 
     def __post_init__(self):
         self.parents = np.asarray(self.parents, dtype=np.int32)
@@ -45,6 +64,10 @@ class Skeleton:
                 raise ValueError(f"body_mass {self.body_mass.shape} / body_com {self.body_com.shape}: expected one entry per real body ({len(self.body_names)})")
         else:
             self.body_com = None
+        if self.body_inertia is not None:
+            self.body_inertia = np.asarray(self.body_inertia, dtype=np.float64)
+            if self.body_mass is None or self.body_inertia.shape != (len(self.body_names), 3, 3):
+                raise ValueError(f"body_inertia {self.body_inertia.shape}: expected [{len(self.body_names)}, 3, 3] next to body_mass")
 
     @property
     def num_bodies(self):
@@ -65,7 +88,7 @@ class Skeleton:
         world = root.find("worldbody")
         if world is None or world.find("body") is None:
             raise ValueError(f"{path}: no <worldbody>/<body>")
-        names, parents, offs, rots, mass, com = [], [], [], [], [], []
+        names, parents, offs, rots, mass, com, inertia = [], [], [], [], [], [], []
         stack = [(world.find("body"), -1)]
         # explicit-stack DFS, children visited in document order
         while stack:
@@ -78,6 +101,7 @@ class Skeleton:
             inertial = node.find("inertial")                 # <inertial mass pos>: a body without one weighs nothing
             mass.append(float(inertial.attrib.get("mass", "0")) if inertial is not None else 0.0)
             com.append([float(x) for x in inertial.attrib.get("pos", "0 0 0").split()] if inertial is not None else [0.0, 0.0, 0.0])
+            inertia.append(_inertia_tensor(inertial))
             for child in reversed(node.findall("body")):
                 stack.append((child, idx))
         joints = world.findall(".//joint")
@@ -95,19 +119,21 @@ class Skeleton:
             offs.append(list(e["pos"]))
             rots.append(list(e["rot"]))
             ext_names.append(e["joint_name"])
-        return cls(names, ext_names, parents, offs, rots, axes, body_mass=mass, body_com=com)
+        return cls(names, ext_names, parents, offs, rots, axes, body_mass=mass, body_com=com, body_inertia=inertia)
 
     @classmethod
     def from_json(cls, path):
         d = json.load(open(path))
         return cls(d["body_names"], d["body_names_ext"], d["parents"], d["offsets"], d["local_rot_wxyz"], d["dof_axis"],
-                   body_mass=d.get("body_mass"), body_com=d.get("body_com"))
+                   body_mass=d.get("body_mass"), body_com=d.get("body_com"), body_inertia=d.get("body_inertia"))
 
     def to_json(self, path):
         d = dict(body_names=self.body_names, body_names_ext=self.body_names_ext, parents=self.parents.tolist(),
                  offsets=self.offsets.tolist(), local_rot_wxyz=self.local_rot_wxyz.tolist(), dof_axis=self.dof_axis.tolist())
         if self.body_mass is not None:                        # only when present: a skeleton without masses writes the file it always wrote
             d.update(body_mass=self.body_mass.tolist(), body_com=self.body_com.tolist())
+        if self.body_inertia is not None:
+            d.update(body_inertia=self.body_inertia.tolist())
         json.dump(d, open(path, "w"), indent=1)
 
     @classmethod

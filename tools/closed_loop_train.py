@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Train MHPPO in the closed loop of JointSpaceSim (pbhc_amd/simulator/joint_sim.py) and print whether the tracking error moves.
+"""Train MHPPO in the closed loop of JointSpaceSim (pbhc_amd/simulator/joint_sim.py) or ArticulatedSim (pbhc_amd/simulator/articulated_sim.py)
+and print whether the tracking error moves.
 
     python tools/closed_loop_train.py --config tests/golden/configs/v1_g1_23dof_walk.yaml --envs 1024 --iters 300 --sim joint
 
@@ -13,6 +14,8 @@ for rollout_ms, and the control for the two tracking figures (they must NOT move
 
 The joint simulator is no physics engine (no gravity, no coupling between joints, no contact dynamics; the root rides the clip): a falling
 error here shows that the loop action -> torque -> joint state -> observation -> reward is closed and that PPO can use it, nothing more.
+`--sim articulated` runs the robot's tree with the MJCF's masses and inertia tensors under gravity and the gantry's accelerations (armature and
+damping from the same flags; --inertia is not used): still no free root, no contact dynamics, no balance.
 """
 import argparse
 import os
@@ -36,6 +39,11 @@ def build(args):
         inertia = "subtree" if args.inertia == "subtree" else float(args.inertia)
         ov["simulator.config.joint_sim"] = {"inertia": inertia, "armature": args.armature, "damping": args.damping}
         if args.mjcf:                                         # "subtree" needs the link masses: the skeleton from the MJCF
+            ov["robot.motion.asset.assetFileName"] = args.mjcf
+    elif args.sim == "articulated":
+        ov["simulator._target_"] = "pbhc_amd.simulator.articulated_sim.ArticulatedSim"
+        ov["simulator.config.articulated_sim"] = {"armature": args.armature, "damping": args.damping}
+        if args.mjcf:                                         # the masses and inertia tensors: the skeleton from the MJCF
             ov["robot.motion.asset.assetFileName"] = args.mjcf
     else:
         ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
@@ -62,7 +70,7 @@ def main():
     ap.add_argument("--config", default=os.path.join(ROOT, "tests", "golden", "configs", "v1_g1_23dof_walk.yaml"))
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=300)
-    ap.add_argument("--sim", choices=("joint", "replay"), default="joint")
+    ap.add_argument("--sim", choices=("joint", "articulated", "replay"), default="joint")
     ap.add_argument("--inertia", default="subtree", help='"subtree" or one number (kg m^2) for every joint')
     ap.add_argument("--armature", type=float, default=0.02)
     ap.add_argument("--damping", type=float, default=0.05)
@@ -79,7 +87,7 @@ def main():
         import bench
 
         env.simulator.set_replay(*bench.make_replay_on_device(env, algo.num_steps_per_env * 8 + 3, seed=99))
-    else:
+    elif args.sim == "joint":
         print("# inertia (kg m^2): " + " ".join(f"{v:.4f}" for v in env.simulator.inertia))
     print(f"# sim {args.sim}, {args.envs} envs, {algo.num_steps_per_env} steps per rollout, {args.iters} iterations")
     print("# iter joint_diff r_joint_pos avg_ep_len rollout_ms graph")

@@ -1,8 +1,9 @@
-"""k_joint_sim under the profiler, next to the two kernels of the same mapping (k_dof_far_any, k_clip_stats).
+"""k_joint_sim / k_articulated_sim under the profiler, next to the two kernels of the same mapping (k_dof_far_any, k_clip_stats).
 
-  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/joint_sim_probe.py steps ENVS [joint|replay]
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/joint_sim_probe.py steps ENVS [joint|articulated|both|replay]
         reset_all + 20 control steps of the v1 walk config on one stream with terminate_when_dof_far and clip_statistics on: per step one
-        k_joint_sim (joint only), one k_dof_far_any, one k_env_step, one k_env_finalize and one k_clip_stats dispatch
+        k_joint_sim (joint) or k_articulated_sim (articulated: the G1 MJCF, armature 0.02, damping 0.05), one k_dof_far_any, one k_env_step,
+        one k_env_finalize and one k_clip_stats dispatch; `both` runs the two simulators one after the other in ONE trace
   python3 tools/joint_sim_probe.py summary DIR [DIR ...]
         per directory: dispatches, median and minimum (microseconds) of those kernels
 """
@@ -14,7 +15,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-KERNELS = ("k_joint_sim", "k_dof_far_any", "k_clip_stats", "k_env_step", "k_env_finalize")
+KERNELS = ("k_joint_sim", "k_articulated_sim", "k_dof_far_any", "k_clip_stats", "k_env_step", "k_env_finalize")
 
 
 def steps(num_envs, sim):
@@ -29,13 +30,17 @@ def steps(num_envs, sim):
     if sim == "joint":
         ov.update({"simulator._target_": "pbhc_amd.simulator.joint_sim.JointSpaceSim",
                    "simulator.config.joint_sim": {"inertia": 0.1, "damping": 0.05}})
+    elif sim == "articulated":
+        ov.update({"simulator._target_": "pbhc_amd.simulator.articulated_sim.ArticulatedSim",
+                   "simulator.config.articulated_sim": {"armature": 0.02, "damping": 0.05},
+                   "robot.motion.asset.assetFileName": "mjcf/g1_23dof_lock_wrist_fitmotionONLY.xml"})
     else:
         ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
     cfg = load_config(os.path.join(root, "tests", "golden", "configs", "v1_g1_23dof_walk.yaml"), ov, now="probe")
     torch.manual_seed(0)
     env = LeggedRobotMotionTracking(cfg.env.config, "cuda:0")
     env.reset_all()
-    if sim != "joint":
+    if sim == "replay":
         env.simulator.set_replay(*bench.make_replay_on_device(env, 24, seed=1))
     g = torch.Generator(device="cuda:0").manual_seed(1)
     for _ in range(20):
@@ -65,7 +70,9 @@ def summary(dirs):
 
 if __name__ == "__main__":
     if sys.argv[1] == "steps":
-        steps(int(sys.argv[2]), sys.argv[3] if len(sys.argv) > 3 else "joint")
+        which = sys.argv[3] if len(sys.argv) > 3 else "joint"
+        for sim in (("joint", "articulated") if which == "both" else (which,)):
+            steps(int(sys.argv[2]), sim)
     elif sys.argv[1] == "summary":
         summary(sys.argv[2:])
     else:
