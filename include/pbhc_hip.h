@@ -863,10 +863,11 @@ int pbhc_linear_act_fwd_strided(const float* x, int lda, long long x_batch_strid
  * x rows ldx floats apart, y rows ldy apart; weights[l] = the PACKED copy (pbhc_mlp_pack, pbhc_mlp_packed_floats(dims[l+1], dims[l]) floats,
  * 16-byte aligned) of nn.Linear.weight [dims[l+1], dims[l]] — the MFMA operand fragments laid out 1 KiB-contiguous per wave-instruction;
  * the caller repacks when the weights change (once per rollout: they are constant over its steps).  biases[l] may be NULL; act as
- * pbhc_linear_act_fwd.  pbhc_mlp_fwd_lds_bytes: the launch's dynamic LDS (<= 160 KB or the call is refused). */
+ * pbhc_linear_act_fwd.  pbhc_mlp_fwd_lds_bytes: the launch's dynamic LDS (<= 160 KB or the call is refused): two images of 16 rows, image
+ * (l & 1) at the widest pitch ceil16(dims[l]) + 4 of its layers' inputs l < L and of the output row dims[L]. */
 #define PBHC_MLP_MAX_LAYERS 8
 /* pbhc_mlp_fwd_sample: the policy's stack with pbhc_policy_sample folded into the last layer's epilogue (mh_ppo.py:286-296: the rollout's
- * act() + log-prob + buffer writes): mu = the stack's output [M, A] (A = dims[L] <= 32), actions = mu + std * z with z from the Philox call
+ * act() + log-prob + buffer writes): mu = the stack's output [M, A] (A = dims[L] <= 32, else PBHC_EINVAL and nothing launched), actions = mu + std * z with z from the Philox call
  * pbhc_policy_sample makes — keyed by seed / (uint32)counter[0] + counter_offset / row / column — action_mean = mu, action_sigma = std,
  * logp[M] = the row's Normal log-density.  `counter`: a device double the caller keeps constant over a rollout (a snapshot of the env's step
  * counter at its start) with counter_offset = the step index, so that the launch does not wait for the previous step's reduction. */
@@ -938,7 +939,8 @@ int pbhc_mlp_fwd_cat_riders(const PbhcMlpInput* in, const float* const* weights,
 /* pbhc_conv_encoder_fwd: the general-tracking `ConvEncoder` (agents/modules/encoder_modules.py:22-107 of the reference: Linear(d -> H) + ReLU
  * per time step, Conv1d(H -> O1, k1, s1) + act, Conv1d(O1 -> O2, k2, s2) + act, Linear(L2 * O2 -> E)) under no_grad in ONE launch, 16 rows per
  * workgroup through all four layers (the rollout: 4 096 rows per control step).  x [M, T * d] with row pitch ldx >= (T - 1) * d + ceil16(d)
- * (a rollout slab's padded rows), y [M, E].  Weights packed by pbhc_mlp_pack from row-major matrices: w1 [H, d]; wc1 [O1, k1 * H] and wc2
+ * (a rollout slab's padded rows: the kernel reads whole 16-float k-steps, so the last step's read ends inside the padding, but the result
+ * depends on columns [0, T * d) only — the padding may hold anything, NaN included), y [M, E] with row pitch ldy >= E.  Weights packed by pbhc_mlp_pack from row-major matrices: w1 [H, d]; wc1 [O1, k1 * H] and wc2
  * [O2, k2 * O1] with the kernel tap OUTER (conv.weight.permute(0, 2, 1)); wo [E, L2 * O2] with its columns in (position, channel) order.
  * act: 1 ELU, 2 SiLU, 3 ReLU (the conv layers; layer 1 is ReLU, the output layer linear).  pbhc_conv_encoder_lds_bytes: the launch's LDS need
  * (<= 160 KB; the caller falls back to the per-layer kernels otherwise). */

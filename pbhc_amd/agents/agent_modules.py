@@ -374,7 +374,9 @@ class ConvEncoder(nn.Module):
         lin = self.encoder[0]
         ready = self.__dict__.get("_infer_ready", False)
         e = self.__dict__.get("_enc_c") if ready else None
+        # (whole 16-float k-steps: the last step's read ends in the row's padding, and for the last row that padding has to be x's own storage)
         if (e is not None and ONE_LAUNCH_ENCODER and B <= 16384 and x.stride(0) >= (T - 1) * d + (d + 15) // 16 * 16
+                and fused_mlp.rows_readable(x, (T - 1) * d + (d + 15) // 16 * 16)
                 and (out is None or (out.dim() == 2 and out.stride(1) == 1))):
             # the whole encoder as ONE launch (pbhc_conv_encoder_fwd: 16 rows per workgroup through the four layers, activations in LDS)
             import ctypes as C

@@ -703,6 +703,18 @@ def release_stack(seq):
         c["valid"] = False
 
 
+def rows_readable(x, span):
+    """every row of the 2-D view `x` can be READ `span` floats wide without leaving x's storage: the stack kernel's 16-byte pieces and the
+    one-launch encoder's 16-float k-steps read past a row's last column; inside the row pitch for every row but the last, whose over-read
+    must not be the first bytes behind the allocation (a column slice that ends where its storage ends)"""
+    return x.storage_offset() + (x.shape[0] - 1) * x.stride(0) + span <= x.untyped_storage().nbytes() // x.element_size()
+
+
+def _pieces_readable(x):
+    """the stack kernel takes its 16-byte path only with a row pitch % 4 == 0: then the piece that straddles the row's end is read whole"""
+    return x.stride(0) % 4 != 0 or rows_readable(x, (x.shape[1] + 3) // 4 * 4)
+
+
 def forward_inference(seq, x):
     """No-grad forward of the same stack (the rollout's policy / critic evaluation).  Between pack_stack() and release_stack() — the owner's
     promise that the weights are constant — the WHOLE stack is one launch (`pbhc_mlp_fwd`: a workgroup carries 16 rows through every layer,
@@ -713,7 +725,7 @@ def forward_inference(seq, x):
     lib, st = _lib.lib(), _lib.current_stream()
     # a rollout slab is a [N, C] view of 128-byte-padded rows: read in place through the row pitch (no .contiguous() copy of the slab)
     pitched = (not x.is_contiguous() and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 4 == 0
-               and x.data_ptr() % 16 == 0 and x.shape[1] >= 4 and len(lin) > 1)
+               and x.data_ptr() % 16 == 0 and x.shape[1] >= 4 and len(lin) > 1 and _pieces_readable(x))
     h = x if (x.is_contiguous() or pitched) else x.contiguous()
     B = h.shape[0]
     c = getattr(seq, "_pbhc_stack", None)
@@ -742,7 +754,7 @@ def forward_sample(seq, x, std, seed, counter, counter_offset, actions, action_m
     c = getattr(seq, "_pbhc_stack", None)
     lin = [m for m in seq if isinstance(m, nn.Linear)]
     B = x.shape[0]
-    if not (c is not None and c["valid"] and B <= _STACK_MAX_ROWS and x.dim() == 2 and x.stride(1) == 1 and lin[-1].out_features <= 32
+    if not (c is not None and c["valid"] and B <= _STACK_MAX_ROWS and x.dim() == 2 and x.stride(1) == 1 and lin[-1].out_features <= 32 and _pieces_readable(x)
             and actions.is_contiguous() and action_mean.is_contiguous() and action_sigma.is_contiguous() and logp.is_contiguous()):
         return False
     smp = _lib.PbhcMlpSample()
@@ -768,7 +780,7 @@ def forward_cat_inference(seq, xs, sample=None, riders=None):
     lin = [m for m in seq if isinstance(m, nn.Linear)]
     B = xs[0].shape[0]
     if not (c is not None and c["valid"] and B <= _STACK_MAX_ROWS and 1 <= len(xs) <= _lib.K["PBHC_MLP_MAX_SEGS"]
-            and all(x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B and x.dtype == torch.float32 and x.is_cuda for x in xs)
+            and all(x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B and x.dtype == torch.float32 and x.is_cuda and _pieces_readable(x) for x in xs)
             and sum(x.shape[1] for x in xs) == lin[0].in_features):
         return False
     if sample is not None and not (lin[-1].out_features <= 32 and all(sample[k].is_contiguous() for k in ("actions", "action_mean", "action_sigma", "logp"))):

@@ -280,7 +280,8 @@ __global__ __launch_bounds__(MLP_T) void k_mlp_fwd(MlpArgs a) {
 // A workgroup owns 16 envs and carries them through all four layers with the tile routine of the stack kernel above (packed weights straight
 // from L2 into the MFMA's B registers):
 //   layer 1  rows = the 16 envs at ONE time step: the A fragments come straight from the observation slab (global, 16 bytes per lane; the
-//            columns a k-step reads past the step's `d` are the next step's values against zero weights) -> image h [env][t * H + c];
+//            columns a k-step reads past the step's `d` are the next step's values against zero weights; behind the row's T * d columns they are
+//            its padding, which may hold anything, NaN included: zeroed in the fragments of the step(s) that reach it) -> image h [env][t * H + c];
 //   conv 1/2 output position l reads k consecutive time steps = ONE contiguous run of k * C floats of the image below: A = image + l * s * C,
 //            same row pitch -> images c1 [env][l * O1 + c], c2 [env][l * O2 + c];
 //   output   Linear on c2's rows as they lie (its columns re-ordered to (l, c) by the caller) -> global [env][E].
@@ -297,10 +298,11 @@ struct EncArgs {
 struct EncTrue { static constexpr bool value = true; };
 struct EncFalse { static constexpr bool value = false; };
 // one job: acc[t] = A[16, K] . Wp[tile_t]^T for two column tiles; A either an LDS image (row pitch P) or, GLOBAL_A, global rows `ga` (per-lane
-// pointer to row j, column 4 g of the first k-step; <= 8 k-steps, fetched up front)
+// pointer to row j, column 4 g of the first k-step; <= 8 k-steps, fetched up front; kpad >= 0: the columns from kpad on are the row's
+// PADDING, which may hold anything — zeroed in the fragments, not left to the zero weights: 0 * NaN is NaN; < 0: nothing to zero)
 template <bool GLOBAL_A>
 __device__ __forceinline__ void enc_job(const float* __restrict__ Wp, int nks, const int (&tile)[2], const float* __restrict__ A, int P, const float* __restrict__ ga,
-                                        f32x4 (&acc)[2]) {
+                                        int kpad, f32x4 (&acc)[2]) {
   if (!GLOBAL_A) {
     mlp_tiles<2>(Wp, nks, tile, A, P, acc);
   } else {
@@ -308,6 +310,16 @@ __device__ __forceinline__ void enc_job(const float* __restrict__ Wp, int nks, c
     f32x4 areg[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) areg[k] = reinterpret_cast<const MlpF4U*>(ga + 16 * min(k, nks - 1))->v;
+    if (kpad >= 0) {                                          // (wave-uniform: the jobs of the last time step(s))
+      int rem = kpad - 4 * (lane >> 4);                       // this lane's float q of k-step k is column 16 k + 4 g + q
+      asm volatile("" : "+v"(rem));                           // keeps the compares in this branch: hoisted out of the job loop their 32 lane masks
+                                                              // spill the scalar registers of EVERY job (measured: rollout 7.00 -> 7.05 ms)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) areg[k][q] = 16 * k + q < rem ? areg[k][q] : 0.0f;
+      }
+    }
     unsigned int woff[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) woff[t] = ((unsigned int)(tile[t] * nks) * 64u + (unsigned int)lane) * 16u;
@@ -355,7 +367,10 @@ __global__ __launch_bounds__(ENC_T) void k_conv_encoder_fwd(EncArgs a) {
       const int tile[2] = {2 * pr, min(2 * pr + 1, ntiles - 1)};
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       const float* ga = GA ? a.x + (size_t)min(row0 + j, a.M - 1) * a.ldx + pos * astep + 4 * g : nullptr;
-      enc_job<GA>(Wp, nks, tile, GA ? nullptr : Aimg + pos * astep, P, ga, acc);
+      // (global rows end (npos - pos) steps behind this job's first column: a job whose k-steps reach past that — the last time step's; with
+      // d < 16 some before it too — reads the row's padding there)
+      const int left = (npos - pos) * astep;
+      enc_job<GA>(Wp, nks, tile, GA ? nullptr : Aimg + pos * astep, P, ga, GA && 16 * nks > left ? left : -1, acc);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (t == 1 && 2 * pr + 1 >= ntiles) continue;           // (a clamped duplicate of the last tile)
@@ -414,12 +429,20 @@ int pbhc_mlp_pack(const float* w, int N, int K, float* packed, void* stream) {
   return PBHC_OK;
 }
 
-size_t pbhc_mlp_fwd_lds_bytes(const int* dims, int num_layers) {
+// row pitches of the two activation images: image (l & 1) holds layer l's input, and the image the LAST layer writes — image (num_layers & 1):
+// the sampling epilogue's log-prob terms, one per column of the output's 16-wide tiles — holds a row of dims[num_layers]
+static void mlp_pitches(const int* dims, int num_layers, int* pitch0, int* pitch1) {
   int p0 = 0, p1 = 0;
-  for (int l = 0; l < num_layers; ++l) {                   // image (l & 1) holds layer l's input
+  for (int l = 0; l <= num_layers; ++l) {
     const int p = mlp_pitch(dims[l]);
     if (l & 1) p1 = p > p1 ? p : p1; else p0 = p > p0 ? p : p0;
   }
+  *pitch0 = p0; *pitch1 = p1;
+}
+
+size_t pbhc_mlp_fwd_lds_bytes(const int* dims, int num_layers) {
+  int p0 = 0, p1 = 0;
+  mlp_pitches(dims, num_layers, &p0, &p1);
   return (size_t)MLP_ROWS * (size_t)(p0 + p1) * sizeof(float);
 }
 
@@ -451,11 +474,11 @@ static int mlp_launch(const PbhcMlpInput* in, const float* const* weights, const
   a.actions = a.action_mean = a.action_sigma = a.logp = nullptr;
   if (smp) {
     MLP_ARG(smp->std && smp->counter && smp->actions && smp->action_mean && smp->action_sigma && smp->logp);
+    MLP_ARG(dims[num_layers] >= 1 && dims[num_layers] <= 32);      // the epilogue's per-row sum is sized for an action row
     a.std = smp->std; a.counter = smp->counter; a.seed = smp->seed; a.counter_offset = smp->counter_offset;
     a.actions = smp->actions; a.action_mean = smp->action_mean; a.action_sigma = smp->action_sigma; a.logp = smp->logp;
   }
   a.nl = num_layers; a.act = act; a.M = M; a.ldy = ldy; a.y = y;
-  a.pitch0 = a.pitch1 = 0;
   for (int l = 0; l <= num_layers; ++l) {
     MLP_ARG(dims[l] >= 1 && dims[l] <= 4096);
     a.dim[l] = dims[l];
@@ -464,10 +487,8 @@ static int mlp_launch(const PbhcMlpInput* in, const float* const* weights, const
     MLP_ARG(weights[l] && (((uintptr_t)weights[l]) & 15) == 0 && pbhc_mlp_packed_floats(dims[l + 1], dims[l]) < (1u << 28));      // packed (pbhc_mlp_pack)
     a.w[l] = weights[l];
     a.b[l] = biases[l];
-    const int p = mlp_pitch(dims[l]);
-    if (l & 1) a.pitch1 = p > a.pitch1 ? p : a.pitch1; else a.pitch0 = p > a.pitch0 ? p : a.pitch0;
   }
-  if (a.pitch1 == 0) a.pitch1 = 4;
+  mlp_pitches(dims, num_layers, &a.pitch0, &a.pitch1);
   size_t lds = (size_t)MLP_ROWS * (size_t)(a.pitch0 + a.pitch1) * sizeof(float);
   MLP_ARG(lds <= 160 * 1024);
   // riders: extra workgroups behind the stack's
@@ -546,7 +567,8 @@ int pbhc_conv_encoder_fwd(const float* x, int ldx, const PbhcConvEncoder* e, flo
   MLP_ARG(e->T >= 1 && e->d >= 1 && e->d <= 128 && e->H >= 1 && e->O1 >= 1 && e->O2 >= 1 && e->E >= 1 && e->k1 >= 1 && e->s1 >= 1 && e->k2 >= 1 && e->s2 >= 1);
   const int L1 = (e->T - e->k1) / e->s1 + 1, L2 = e->T >= e->k1 ? (L1 - e->k2) / e->s2 + 1 : 0;
   MLP_ARG(e->T >= e->k1 && L1 >= e->k2 && L2 >= 1 && ldy >= e->E);
-  // layer 1 reads whole k-steps of 16 floats from the slab: the last step's over-read has to stay inside the row's pitch (and the allocation)
+  // layer 1 reads whole k-steps of 16 floats from the slab: the last step's over-read has to stay inside the row's pitch (and the allocation);
+  // what it fetches there is masked in the kernel
   MLP_ARG(ldx >= (e->T - 1) * e->d + ((e->d + 15) & ~15) && (((uintptr_t)x) & 3) == 0);
   // the conv windows are read as 16-byte LDS fragments: their starts have to be 16-byte aligned
   MLP_ARG(((e->s1 * e->H) & 3) == 0 && ((e->s2 * e->O1) & 3) == 0);
