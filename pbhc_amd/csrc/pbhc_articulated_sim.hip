@@ -1,9 +1,8 @@
 // pbhc_articulated_sim.hip — the articulated rigid-body simulator (pbhc_amd/simulator/articulated_sim.py ArticulatedSim).
 //
 //   k_articulated_sim   one launch per control step, where k_joint_sim sits (directly in front of k_env_step on the stepping stream), writing the
-//                       same one-frame replay window.  Root, contact, the delayed-action peek, the torque law and its draws are k_joint_sim's,
-//                       operation for operation (DUPLICATED from pbhc_joint_sim.hip, not shared: the lane mapping differs — here lane = body and
-//                       lane b owns dof b - 1 — and k_joint_sim's unit stays byte for byte what its tests pin).  Only the joint law differs:
+//                       same one-frame replay window.  Root, contact, the delayed-action peek, the torque law and its draws are k_joint_sim's:
+//                       the shared part lives in pbhc_closed_loop.h (here lane = body and lane b owns dof b - 1).  Only the joint law differs:
 //                       every sub-step solves  (M(q) + diag(armature + h b)) dv = h (tau - b v - c(q, v; base))  on the robot's tree with the
 //                       MJCF's masses, centres of mass and inertia tensors; the base (the root row this kernel writes) is prescribed.
 //   k_art_debug         test-only: the same device function (art_substep) under a constant torque.
@@ -33,15 +32,10 @@
 
 using namespace pbhc;
 
-extern thread_local char g_pbhc_err[512];
-extern "C" int pbhc_env_parts(PbhcEnv* e, const PbhcEnvConfig** host_cfg, const PbhcEnvConfig** dev_cfg, const PbhcMotionTable** tbl,
-                              double** glob);                  // pbhc_kernels.hip
-
 #undef PBHC_STAMPS                                          // (the phase stamps of the diagnostic build belong to the step kernel's unit)
 #include "pbhc_env_step.h"                                  // PBHC_G, at, clampf, frame_blend, slerp, rng_uniform / rng_normal
+#include "pbhc_closed_loop.h"                               // CL_EPB, ClFront and the cl_* pieces, CL_CHECK, cl_check_step
 
-#define ART_EPB 8                                           // envs per 256-thread workgroup: 32 lanes per env
-#define ART_MAX_DECIMATION 64
 #define ART_MAX_DEBUG_STEPS 4096
 static_assert(PBHC_ART_MAX_BODIES == PBHC_G, "one body per lane of an env group");
 
@@ -219,44 +213,19 @@ __device__ __forceinline__ void art_lane_inertial(ArtLane& L, const PbhcArticula
   L.arm_h = p.armature[dcl] + h * L.damping;
 }
 
-__global__ __launch_bounds__(PBHC_G* ART_EPB) void k_articulated_sim(const PbhcEnvConfig* __restrict__ cfgp, PbhcMotionTable tbl, PbhcStepIO io,
-                                                                     PbhcArticulatedParams p, ArtTree tree, const double* __restrict__ glob, int N) {
-  typedef const PbhcEnvConfig __attribute__((address_space(4))) ConstCfg;
-  ConstCfg& c = *(ConstCfg*)cfgp;
+__global__ __launch_bounds__(PBHC_G* CL_EPB) void k_articulated_sim(const PbhcEnvConfig* __restrict__ cfgp, PbhcMotionTable tbl, PbhcStepIO io,
+                                                                    PbhcArticulatedParams p, ArtTree tree, const double* __restrict__ glob, int N) {
+  ClCfg& c = *(ClCfg*)cfgp;
   typedef unsigned int u32;
-  const int D = c.skel.num_dof, B = c.skel.num_bodies, Bx = c.skel.num_bodies_ext, NF = c.num_feet, Q = max(c.queue_len, 1);
+  const int D = c.skel.num_dof, B = c.skel.num_bodies;
   const int lane = threadIdx.x & (PBHC_G - 1);
-  const int env = blockIdx.x * ART_EPB + (int)(threadIdx.x / PBHC_G);
-  const bool valid = env < N;
-  const int envc = valid ? env : N - 1;
-  const int dof = lane - 1;                                  // lane = body; its hinge
-  const int dc = min(max(dof, 0), D - 1);
-  const bool joint = lane >= 1 && lane < B;
-  const u32 eDc = (u32)envc * (u32)D;
-  const int o_pos = 2 * D + 2, o_rot = o_pos + 3 * Bx, o_vel = o_rot + 4 * Bx, o_ang = o_vel + 3 * Bx;     // columns of a packed motion-table row
-
-  // (1) the env scalars the reference rows' addresses hang on
-  const long long ep1 = (long long)io.episode_length_buf[envc] + 1;
-  const float start = io.motion_start_times[envc];
-  const int mid = (int)io.motion_ids[envc];
-  // (2) everything that depends on the env index only
-  const uint32_t step_ctr = (uint32_t)glob[PBHC_G_STEP_COUNTER];
-  const long long adelay = io.action_delay_idx[envc];
-  const float org = at(io.env_origins, (u32)envc * 3u + (u32)min(lane, 2));
-  const float a_in = at(io.actions_in, eDc + dc);
-  float q = at(io.dof_state, (eDc + dc) * 2), v = at(io.dof_state, (eDc + dc) * 2 + 1);
-  const float kp = at(io.kp_scale, eDc + dc), kd = at(io.kd_scale, eDc + dc), rfs = at(io.rfi_lim_scale, eDc + dc), ras = at(io.rao_scale, eDc + dc);
-  const float u_inj = at(io.u_rfi ? io.u_rfi : io.actions_in, eDc + dc);
-  const float k_dp = io.default_dof_pos ? at(io.default_dof_pos, eDc + dc) : c.default_dof_pos[dc];
-  float qold[PBHC_MAX_QUEUE];
-#pragma unroll
-  for (int k = 0; k < PBHC_MAX_QUEUE; ++k) qold[k] = at(io.action_queue, (u32)envc * (u32)(Q * D) + (u32)(min(k, Q - 1) * D) + (u32)dc);
-  const int sl = c.ps_tau ? c.ps_tau_slot[dc] : -1;
-  const float n_inj = (sl >= 0 && io.ovr_ps_tau) ? at(io.ovr_ps_tau, (u32)envc * (u32)c.ps_tau_num + (u32)sl) : 0.0f;
-  const float tl = c.torque_limits[dc], k_pg = c.p_gains[dc], k_dg = c.d_gains[dc], k_as = c.action_scale[dc];
+  const bool joint = lane >= 1 && lane < B;                  // lane = body; its hinge is dof lane - 1
+  ClFront F;
+  cl_load_env(F, c, io, glob, N, lane, min(max(lane - 1, 0), D - 1));
+  const int dc = F.dc;
   const float h = c.sim_dt;
   ArtLane L;
-  L.lo = c.hard_dof_pos_limits[dc][0]; L.hi = c.hard_dof_pos_limits[dc][1];
+  L.lo = F.lo; L.hi = F.hi;
   L.parent = max(c.skel.parent[lane], 0);
   L.depth = joint ? c.skel.depth[lane] : (lane == 0 ? 0 : -1);
   L.first_child = tree.first_child[lane]; L.next_sibling = tree.next_sibling[lane];
@@ -267,55 +236,15 @@ __global__ __launch_bounds__(PBHC_G* ART_EPB) void k_articulated_sim(const PbhcE
     L.axis = mul3(ax, 1.0f / fmaxf(norm3(ax), 1e-9f));
   }
   art_lane_inertial(L, p, lane, dc, h);
-  const int foot = c.feet[min(lane, max(NF, 1) - 1)];
   __builtin_amdgcn_sched_barrier(0);
-  // (3) the table rows: one root component per lane (lanes 0..12) at tref and, for the base acceleration, at tref - dt; one contact source per lane
-  float m_len = tbl.single_len, m_dt = tbl.single_dt;
-  int m_nf = tbl.single_num_frames, m_row0 = 0;
-  if (tbl.num_motions != 1) { m_len = tbl.motion_len[mid]; m_nf = tbl.num_frames[mid]; m_dt = tbl.motion_dt[mid]; m_row0 = tbl.length_starts[mid]; }
-  const float tref = (float)(ep1 + 1) * c.dt + start;         // the step's own reference time (motion_tracking.py:554,588), from the pre-step counter
-  int f0, f1, g0, g1;
-  float blend, blend_p;
-  frame_blend(tref, m_len, m_nf, m_dt, &f0, &f1, &blend);
-  frame_blend(tref - c.dt, m_len, m_nf, m_dt, &g0, &g1, &blend_p);
-  const float* r0 = tbl.frames + (size_t)(m_row0 + f0) * tbl.row;
-  const float* r1 = tbl.frames + (size_t)(m_row0 + f1) * tbl.row;
-  const float* s0 = tbl.frames + (size_t)(m_row0 + g0) * tbl.row;
-  const float* s1 = tbl.frames + (size_t)(m_row0 + g1) * tbl.row;
-  const int lr = min(lane, 12);
-  const int rcol = lr < 3 ? o_pos + lr : (lr < 7 ? o_rot + (lr - 3) : (lr < 10 ? o_vel + (lr - 7) : o_ang + (lr - 10)));     // body 0 of the row
-  const int ccol = c.has_contact_mask ? 2 * D + min(lane, 1) : o_pos + 3 * foot + 2;
-  const float rr0 = r0[rcol], rr1 = r1[rcol], cc0 = r0[ccol], cc1 = r1[ccol], ss0 = s0[rcol], ss1 = s1[rcol];
+  cl_load_rows<true>(F, c, tbl);                             // with the rows at tref - dt, for the base acceleration
   __builtin_amdgcn_sched_barrier(0);
+  cl_control(F, c, io);
 
-  // ---- the draws of this control step (computed while the loads fly), held over the sub-steps
-  float u_rfi = 0.5f, n_ps = 0.0f;
-  if (c.randomize_torque_rfi) u_rfi = io.u_rfi ? u_inj : rng_uniform(c.seed, (u32)env, step_ctr, 1, (u32)dc);
-  if (sl >= 0) n_ps = io.ovr_ps_tau ? n_inj : rng_normal(c.seed, (u32)env, step_ctr, 19, (u32)dc);
-
-  // ---- the action the step will apply (pbhc_env_step.h, _pre_physics_step): clipped, then the queue entry the delay index names AFTER the
-  // step's shift — the new action for index 0, else the entry one place in front of it as the queue stands now
-  const float a = clampf(a_in, -c.action_clip_value, c.action_clip_value);
-  float delayed = a;
-  if (c.randomize_ctrl_delay) {
-    const int didx = (int)adelay;
-#pragma unroll
-    for (int k = 1; k < PBHC_MAX_QUEUE; ++k)
-      if (k < Q && k == didx) delayed = qold[k - 1];
-  }
-  const float a_sc = delayed * k_as;
-
-  // ---- root state: lerp / slerp of the root body's two rows, exactly motion_lookup's expressions (k_motion_state)
-  const float al = 1.0f - blend;
-  const f4 q0 = mk4(shf(rr0, 3), shf(rr0, 4), shf(rr0, 5), shf(rr0, 6));
-  const f4 q1 = mk4(shf(rr1, 3), shf(rr1, 4), shf(rr1, 5), shf(rr1, 6));
-  const f4 qs = slerp(q0, q1, blend);
-  float rootv;
-  if (lane < 3) rootv = al * rr0 + blend * rr1 + org;
-  else if (lane < 7) rootv = lane == 3 ? qs.x : (lane == 4 ? qs.y : (lane == 5 ? qs.z : qs.w));
-  else rootv = al * rr0 + blend * rr1;
-  // ---- the base: R_0, w_0 of that row; a_0, alpha_0 from the row one control step earlier (lanes 7..12: one component each)
-  const float racc = p.base_acceleration ? (rootv - ((1.0f - blend_p) * ss0 + blend_p * ss1)) / c.dt : 0.0f;
+  // ---- the base: R_0, w_0 of the root row; a_0, alpha_0 from the row one control step earlier (lanes 7..12: one component each)
+  f4 qs;
+  const float rootv = cl_root(F, qs);
+  const float racc = p.base_acceleration ? (rootv - ((1.0f - F.blend_p) * F.ss0 + F.blend_p * F.ss1)) / c.dt : 0.0f;
   ArtBase base;
   base.R0 = quat_unit_fast(qs);
   base.w0 = mk3(shf(rootv, 10), shf(rootv, 11), shf(rootv, 12));
@@ -323,48 +252,27 @@ __global__ __launch_bounds__(PBHC_G* ART_EPB) void k_articulated_sim(const PbhcE
   base.a0g = mk3(shf(racc, 7) - p.gravity[0], shf(racc, 8) - p.gravity[1], shf(racc, 9) - p.gravity[2]);
 
   // ---- the sub-steps (legged_robot_base.py:287-295): torque from the current (q, v), then the tree's forward dynamics
+  float q = F.q, v = F.v;
   if (!joint) { q = 0.0f; v = 0.0f; }
   float tq0 = 0.0f;
   for (int s = 0; s < p.decimation; ++s) {
-    float tq;
-    if (c.control_type == 0) tq = kp * k_pg * (a_sc + k_dp - q) - kd * k_dg * v;
-    else tq = a_sc;                                            // "T" ("V" is refused by the host)
-    if (c.randomize_torque_rfi) tq = tq + (u_rfi * 2.0f - 1.0f) * c.rfi_lim * rfs * tl;
-    if (sl >= 0) tq = tq + (c.ps_tau_rfi_lim * tl) * n_ps;
-    if (c.use_rao) tq = tq + ras * tl;
-    if (c.clip_torques) tq = clampf(tq, -tl, tl);
+    const float tq = cl_torque(F, c, q, v);
     if (s == 0) tq0 = tq;
     art_substep(L, tree, base, lane, h, tq, p.enforce_limits != 0, q, v);
   }
 
-  // ---- contact: the clip's lerped mask, or the foot's reference height where the library has no masks
-  const float cl = al * cc0 + blend * cc1;
-  const bool touch = c.has_contact_mask ? cl > 0.5f : cl < p.foot_height_threshold;
-
-  float* f_root = const_cast<float*>(io.frame_root);           // the window is the simulator's own: one frame, [1, N, ...]
-  float* f_q = const_cast<float*>(io.frame_dof_pos);
-  float* f_qd = const_cast<float*>(io.frame_dof_vel);
-  float* f_c = const_cast<float*>(io.frame_contact);
-  if (valid) {
-    if (joint) {
-      at(f_q, eDc + (u32)dc) = q;
-      at(f_qd, eDc + (u32)dc) = v;
-      if (p.tau0) at(p.tau0, eDc + (u32)dc) = tq0;
-    }
-    if (lane < 13) at(f_root, (u32)envc * 13u + (u32)lane) = rootv;
-    if (lane < NF) at(f_c, (u32)envc * (u32)(B * 3) + (u32)(3 * foot + 2)) = touch ? p.contact_force : 0.0f;
-    if (p.base_acc && lane >= 7 && lane < 13) at(p.base_acc, (u32)envc * 6u + (u32)(lane - 7)) = racc;
-  }
+  cl_store_frame(F, c, io, joint, q, v, tq0, p.tau0, rootv, p.foot_height_threshold, p.contact_force);
+  if (F.valid && p.base_acc && lane >= 7 && lane < 13) at(p.base_acc, (u32)F.envc * 6u + (u32)(lane - 7)) = racc;
 }
 
-__global__ __launch_bounds__(PBHC_G* ART_EPB) void k_art_debug(ArtSkel sk, PbhcArticulatedParams p, ArtTree tree, const float* __restrict__ basep,
+__global__ __launch_bounds__(PBHC_G* CL_EPB) void k_art_debug(ArtSkel sk, PbhcArticulatedParams p, ArtTree tree, const float* __restrict__ basep,
                                                                const float* __restrict__ qp, const float* __restrict__ vp, const float* __restrict__ taup,
                                                                int n, int steps, float h, int enforce_limits, float* __restrict__ out_q,
                                                                float* __restrict__ out_v, float* __restrict__ out_qdd0) {
   typedef unsigned int u32;
   const int B = sk.num_bodies, D = B - 1;
   const int lane = threadIdx.x & (PBHC_G - 1);
-  const int env = blockIdx.x * ART_EPB + (int)(threadIdx.x / PBHC_G);
+  const int env = blockIdx.x * CL_EPB + (int)(threadIdx.x / PBHC_G);
   const bool valid = env < n;
   const int envc = valid ? env : n - 1;
   const int dc = min(max(lane - 1, 0), D - 1);
@@ -402,14 +310,6 @@ __global__ __launch_bounds__(PBHC_G* ART_EPB) void k_art_debug(ArtSkel sk, PbhcA
 
 extern "C" int pbhc_sizeof_articulated_params(void) { return (int)sizeof(PbhcArticulatedParams); }
 
-#define ART_CHECK(cnd)                                                                                             \
-  do {                                                                                                             \
-    if (!(cnd)) {                                                                                                  \
-      snprintf(g_pbhc_err, sizeof(g_pbhc_err), "%s:%d bad argument: %s", __FILE__, __LINE__, #cnd);                \
-      return PBHC_EINVAL;                                                                                          \
-    }                                                                                                              \
-  } while (0)
-
 // the kernel arguments travel by value: the largest set (the debug kernel's) must fit the 4 KB kernarg segment
 static_assert(sizeof(ArtSkel) + sizeof(PbhcArticulatedParams) + sizeof(ArtTree) + 12 * 8 <= 4096, "k_art_debug: kernel arguments over 4 KB");
 static_assert(sizeof(PbhcStepIO) + sizeof(PbhcMotionTable) + sizeof(PbhcArticulatedParams) + sizeof(ArtTree) + 4 * 8 <= 4096,
@@ -418,15 +318,15 @@ static_assert(sizeof(PbhcStepIO) + sizeof(PbhcMotionTable) + sizeof(PbhcArticula
 // child lists from the parents (bodies are in DFS order: a parent comes before its children); refuses a tree the kernel cannot walk
 static int art_tree(const PbhcSkeleton& sk, ArtTree* t) {
   const int B = sk.num_bodies;
-  ART_CHECK(B >= 2 && B <= PBHC_ART_MAX_BODIES && sk.num_dof == B - 1 && sk.max_depth >= 1 && sk.max_depth <= PBHC_MAX_DEPTH);
+  CL_CHECK(B >= 2 && B <= PBHC_ART_MAX_BODIES && sk.num_dof == B - 1 && sk.max_depth >= 1 && sk.max_depth <= PBHC_MAX_DEPTH);
   memset(t, 0, sizeof(*t));
   int last[PBHC_ART_MAX_BODIES], count[PBHC_ART_MAX_BODIES];
   for (int b = 0; b < PBHC_ART_MAX_BODIES; ++b) { t->first_child[b] = t->next_sibling[b] = last[b] = -1; count[b] = 0; }
-  ART_CHECK(sk.parent[0] < 0 && sk.depth[0] == 0);
+  CL_CHECK(sk.parent[0] < 0 && sk.depth[0] == 0);
   int maxd = 0;
   for (int b = 1; b < B; ++b) {
     const int pa = sk.parent[b];
-    ART_CHECK(pa >= 0 && pa < b && sk.depth[b] == sk.depth[pa] + 1 && sk.depth[b] <= PBHC_MAX_DEPTH);
+    CL_CHECK(pa >= 0 && pa < b && sk.depth[b] == sk.depth[pa] + 1 && sk.depth[b] <= PBHC_MAX_DEPTH);
     if (last[pa] < 0) t->first_child[pa] = b; else t->next_sibling[last[pa]] = b;
     last[pa] = b;
     count[pa] += 1;
@@ -438,31 +338,24 @@ static int art_tree(const PbhcSkeleton& sk, ArtTree* t) {
 }
 
 static int art_check_params(const PbhcArticulatedParams* p, int B) {
-  for (int b = 0; b < B; ++b) ART_CHECK(p->mass[b] >= 0.0f);
-  for (int d = 0; d < B - 1; ++d) ART_CHECK(p->armature[d] >= 0.0f && p->damping[d] >= 0.0f);
+  for (int b = 0; b < B; ++b) CL_CHECK(p->mass[b] >= 0.0f);
+  for (int d = 0; d < B - 1; ++d) CL_CHECK(p->armature[d] >= 0.0f && p->damping[d] >= 0.0f);
   return PBHC_OK;
 }
 
 extern "C" int pbhc_articulated_sim_step(PbhcEnv* e, const PbhcStepIO* io, const PbhcArticulatedParams* p, void* stream) {
-  ART_CHECK(e && io && p);
+  CL_CHECK(p);
   const PbhcEnvConfig *hc = nullptr, *dcfg = nullptr;
   const PbhcMotionTable* tbl = nullptr;
   double* glob = nullptr;
-  int rc = pbhc_env_parts(e, &hc, &dcfg, &tbl, &glob);
+  int rc = cl_check_step(e, io, p->decimation, &hc, &dcfg, &tbl, &glob);
   if (rc != PBHC_OK) return rc;
-  ART_CHECK(io->actions_in && io->frame_root && io->frame_dof_pos && io->frame_dof_vel && io->frame_contact && io->num_frames == 1);
-  ART_CHECK(io->dof_state && io->action_queue && io->action_delay_idx && io->kp_scale && io->kd_scale && io->rfi_lim_scale && io->rao_scale);
-  ART_CHECK(io->episode_length_buf && io->motion_start_times && io->motion_ids && io->env_origins);
-  ART_CHECK(p->decimation >= 1 && p->decimation <= ART_MAX_DECIMATION);
-  ART_CHECK(hc->control_type == 0 || hc->control_type == 2);          // "V" needs last_dof_vel per sub-step: refused
   const int D = hc->skel.num_dof, B = hc->skel.num_bodies, N = hc->num_envs;
-  ART_CHECK(N >= 1 && D >= 1 && B <= PBHC_ART_MAX_BODIES && D == B - 1 && hc->num_feet >= 0 && hc->num_feet <= PBHC_MAX_FEET);
-  for (int f = 0; f < hc->num_feet; ++f) ART_CHECK(hc->feet[f] >= 0 && hc->feet[f] < B);
+  CL_CHECK(B <= PBHC_ART_MAX_BODIES && D == B - 1);
   if ((rc = art_check_params(p, B)) != PBHC_OK) return rc;
-  ART_CHECK((uint64_t)N * (uint64_t)(3 * B > 2 * D ? 3 * B : 2 * D) < (1ull << 30));          // 32-bit row offsets in the kernel
   ArtTree tree;
   if ((rc = art_tree(hc->skel, &tree)) != PBHC_OK) return rc;
-  hipLaunchKernelGGL(k_articulated_sim, dim3((N + ART_EPB - 1) / ART_EPB), dim3(PBHC_G * ART_EPB), 0, (hipStream_t)stream, dcfg, *tbl, *io, *p, tree,
+  hipLaunchKernelGGL(k_articulated_sim, dim3((N + CL_EPB - 1) / CL_EPB), dim3(PBHC_G * CL_EPB), 0, (hipStream_t)stream, dcfg, *tbl, *io, *p, tree,
                      (const double*)glob, N);
   if (hipGetLastError() != hipSuccess) {
     snprintf(g_pbhc_err, sizeof(g_pbhc_err), "pbhc_articulated_sim_step: launch failed");
@@ -474,14 +367,14 @@ extern "C" int pbhc_articulated_sim_step(PbhcEnv* e, const PbhcStepIO* io, const
 extern "C" int pbhc_debug_articulated_substeps(const PbhcSkeleton* skel, const PbhcArticulatedParams* p, const float* base, const float* q, const float* v,
                                                const float* tau, int n, int steps, float h, int enforce_limits, const float* limits, float* out_q,
                                                float* out_v, float* out_qdd0, void* stream) {
-  ART_CHECK(skel && p && base && q && v && tau && out_q && out_v && out_qdd0);
-  ART_CHECK(n >= 1 && steps >= 1 && steps <= ART_MAX_DEBUG_STEPS && h > 0.0f && (!enforce_limits || limits));
+  CL_CHECK(skel && p && base && q && v && tau && out_q && out_v && out_qdd0);
+  CL_CHECK(n >= 1 && steps >= 1 && steps <= ART_MAX_DEBUG_STEPS && h > 0.0f && (!enforce_limits || limits));
   ArtTree tree;
   int rc = art_tree(*skel, &tree);
   if (rc != PBHC_OK) return rc;
   const int B = skel->num_bodies;
   if ((rc = art_check_params(p, B)) != PBHC_OK) return rc;
-  ART_CHECK((uint64_t)n * (uint64_t)B < (1ull << 28));
+  CL_CHECK((uint64_t)n * (uint64_t)B < (1ull << 28));
   ArtSkel sk;
   memset(&sk, 0, sizeof(sk));
   sk.num_bodies = B;
@@ -496,7 +389,7 @@ extern "C" int pbhc_debug_articulated_substeps(const PbhcSkeleton* skel, const P
       if (enforce_limits) { sk.limits[b][0] = limits[2 * (b - 1)]; sk.limits[b][1] = limits[2 * (b - 1) + 1]; }
     }
   }
-  hipLaunchKernelGGL(k_art_debug, dim3((n + ART_EPB - 1) / ART_EPB), dim3(PBHC_G * ART_EPB), 0, (hipStream_t)stream, sk, *p, tree, base, q, v, tau, n,
+  hipLaunchKernelGGL(k_art_debug, dim3((n + CL_EPB - 1) / CL_EPB), dim3(PBHC_G * CL_EPB), 0, (hipStream_t)stream, sk, *p, tree, base, q, v, tau, n,
                      steps, h, enforce_limits, out_q, out_v, out_qdd0);
   if (hipGetLastError() != hipSuccess) {
     snprintf(g_pbhc_err, sizeof(g_pbhc_err), "pbhc_debug_articulated_substeps: launch failed");

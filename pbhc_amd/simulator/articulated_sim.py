@@ -28,13 +28,12 @@ It needs the link masses and inertia tensors, which only the robot's MJCF holds:
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+import torch
 
 from .. import _lib
 from ..skeleton import Skeleton
-from .joint_sim import JointSpaceSim, _per_dof
+from .closed_loop import ClosedLoopSim, _per_dof
 
 KEY = "simulator.config.articulated_sim"
 KEYS = ("armature", "damping", "gravity", "base_acceleration", "contact_force", "foot_height_threshold", "enforce_limits")
@@ -99,20 +98,17 @@ def pd_stability_margins(h, kp_gain, kd_gain, Mt):
     return h * h * lam(kp_gain), h * lam(kd_gain)
 
 
-class ArticulatedSim(JointSpaceSim):
+class ArticulatedSim(ClosedLoopSim):
+    KEY = KEY
+    STEP = "pbhc_articulated_sim_step"
+
     def __init__(self, config, device):
         cfg = config.simulator.config.get("articulated_sim", None) or {}
         for k in cfg.keys():
             if k not in KEYS:
                 raise _lib.PbhcError(f"{KEY}.{k}: unknown key (known: {', '.join(KEYS)})")
-        D = len(config.robot.dof_names)
-        if config.robot.control.control_type == "V":
-            raise _lib.PbhcError(f'{KEY}: robot.control.control_type "V" is not supported (its damping term differences the velocity over '
-                                 'control steps, which has no meaning inside a sub-step); use "P" or "T"')
-        self._armature = _per_dof(cfg.get("armature", 0.0), D, "armature", KEY)
-        self._damping = _per_dof(cfg.get("damping", 0.0), D, "damping", KEY)
-        if (self._armature < 0).any() or (self._damping < 0).any():
-            raise _lib.PbhcError(f"{KEY}: armature and damping must not be negative")
+        self._refuse_velocity_control(config)
+        self._parse_passive(cfg, len(config.robot.dof_names))
         try:
             self.gravity = np.asarray([float(x) for x in cfg.get("gravity", [0.0, 0.0, -9.81])], np.float64)
         except (TypeError, ValueError):
@@ -120,14 +116,9 @@ class ArticulatedSim(JointSpaceSim):
         if self.gravity.shape != (3,):
             raise _lib.PbhcError(f"{KEY}.gravity: expected a list of 3 numbers, got {cfg.get('gravity')!r}")
         self.base_acceleration = bool(cfg.get("base_acceleration", True))
-        self.contact_force = float(cfg.get("contact_force", 300.0))
-        self.foot_height_threshold = float(cfg.get("foot_height_threshold", 0.06))
-        self.enforce_limits = bool(cfg.get("enforce_limits", True))
+        self._parse_options(cfg)
         self.check_model(config, Skeleton.from_motion_config(config.robot.motion), self._armature)
-        self.inertia = None                                  # (JointSpaceSim's per-joint inertia: not this class's)
-        super(JointSpaceSim, self).__init__(config, device)
-        self._params = None
-        self.tau0 = None
+        super().__init__(config, device)
         self.base_acc = None
 
     # ---- construction-time checks (no GPU) -----------------------------------------------------------------------------------------
@@ -161,21 +152,13 @@ class ArticulatedSim(JointSpaceSim):
                                      "gains or raise simulator.config.sim.fps)")
         return Mt
 
-    def load_assets(self):
-        return super(JointSpaceSim, self).load_assets()
-
-    def set_replay(self, *a, **k):
-        raise _lib.PbhcError("ArticulatedSim.set_replay: the simulator writes its own one-frame window every control step; a replay window "
-                             "belongs to ReplaySimStub")
-
     def bind(self, env):
         """called by the env at the end of its construction: the one-frame window, the inertial table, the kernel's parameters"""
         self._bind_window()
         self._params = self.params(self.skeleton, self._armature, self._damping, self.gravity)
         p = self._params
         p.base_acceleration = int(self.base_acceleration)
-        p.contact_force, p.foot_height_threshold = self.contact_force, self.foot_height_threshold
-        p.enforce_limits, p.decimation = int(self.enforce_limits), int(self.decimation)
+        self._fill_common(p)
 
     @staticmethod
     def params(skeleton, armature, damping, gravity=(0.0, 0.0, -9.81)):
@@ -202,12 +185,5 @@ class ArticulatedSim(JointSpaceSim):
 
     def set_debug_base(self, on=True):
         """keep the base's linear and angular acceleration of every control step in `self.base_acc [N, 6]`"""
-        import torch
-
         self.base_acc = torch.zeros(self.num_envs, 6, device=self.device) if on else None
         self._params.base_acc = self.base_acc.data_ptr() if on else None
-
-    def advance(self, env):
-        """the frame of the control step about to be launched, on the current (stepping) stream"""
-        _lib.check(_lib.lib().pbhc_articulated_sim_step(env._env, C.byref(env._io), C.byref(self._params), _lib.current_stream()),
-                   "pbhc_articulated_sim_step")

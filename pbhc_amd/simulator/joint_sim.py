@@ -28,22 +28,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .replay_stub import ReplaySimStub
+from .closed_loop import ClosedLoopSim, _per_dof  # noqa: F401  (_per_dof: re-exported)
 
 KEY = "simulator.config.joint_sim"
-
-
-def _per_dof(value, D, name, key=KEY):
-    """scalar or list of D -> float64 [D]; a list of another length is refused by name"""
-    if isinstance(value, (int, float)) and not isinstance(value, bool):
-        return np.full(D, float(value), np.float64)
-    try:
-        v = [float(x) for x in value]
-    except (TypeError, ValueError):
-        raise _lib.PbhcError(f"{key}.{name}: expected a number or a list of {D} numbers, got {value!r}") from None
-    if len(v) != D:
-        raise _lib.PbhcError(f"{key}.{name}: a list must have one entry per dof ({D}), got {len(v)}")
-    return np.asarray(v, np.float64)
 
 
 def _quat_rotate_xyzw(q, v):
@@ -71,7 +58,7 @@ def subtree_inertia(skeleton, body_pos, body_rot_xyzw, armature=0.0):
     rot = rot / np.linalg.norm(rot, axis=-1, keepdims=True)
     mass = np.asarray(skeleton.body_mass, np.float64)
     parents = np.asarray(skeleton.parents[:B])
-    arm = _per_dof(armature, D, "armature")
+    arm = _per_dof(armature, D, "armature", KEY)
     out = np.zeros(D, np.float64)
     for d in range(D):
         b = d + 1                                            # dof d drives body d + 1
@@ -107,34 +94,28 @@ def check_pd_stability(h, kp_gain, kd_gain, inertia, names=None):
                                  "or raise simulator.config.sim.fps)")
 
 
-class JointSpaceSim(ReplaySimStub):
+class JointSpaceSim(ClosedLoopSim):
+    KEY = KEY
+    STEP = "pbhc_joint_sim_step"
+
     def __init__(self, config, device):
         js = config.simulator.config.get("joint_sim", None) or {}
         D = len(config.robot.dof_names)
-        if config.robot.control.control_type == "V":
-            raise _lib.PbhcError(f'{KEY}: robot.control.control_type "V" is not supported (its damping term differences the velocity over '
-                                 'control steps, which has no meaning inside a sub-step); use "P" or "T"')
+        self._refuse_velocity_control(config)
         self._inertia_spec = js.get("inertia", "subtree")
         if isinstance(self._inertia_spec, str):
             if self._inertia_spec != "subtree":
                 raise _lib.PbhcError(f'{KEY}.inertia: expected a number, a list of {D} numbers or "subtree", got {self._inertia_spec!r}')
         else:
-            self._inertia_spec = _per_dof(self._inertia_spec, D, "inertia")
-        self._armature = _per_dof(js.get("armature", 0.0), D, "armature")
-        self._damping = _per_dof(js.get("damping", 0.0), D, "damping")
-        if (self._armature < 0).any() or (self._damping < 0).any():
-            raise _lib.PbhcError(f"{KEY}: armature and damping must not be negative")
-        self.contact_force = float(js.get("contact_force", 300.0))
-        self.foot_height_threshold = float(js.get("foot_height_threshold", 0.06))
-        self.enforce_limits = bool(js.get("enforce_limits", True))
+            self._inertia_spec = _per_dof(self._inertia_spec, D, "inertia", KEY)
+        self._parse_passive(js, D)
+        self._parse_options(js)
         if not isinstance(self._inertia_spec, str):
             self.inertia = self._checked_inertia(self._inertia_spec + self._armature, list(config.robot.dof_names))
             self._check_stability(config, self.inertia)
         else:
             self.inertia = None                              # needs the rigid-body state of the default pose: bind()
         super().__init__(config, device)
-        self._params = None
-        self.tau0 = None
 
     # ---- construction-time checks (no GPU) -----------------------------------------------------------------------------------------
     @staticmethod
@@ -143,26 +124,6 @@ class JointSpaceSim(ReplaySimStub):
             if not (np.isfinite(v) and v > 0.0):
                 raise _lib.PbhcError(f"{KEY}.inertia: the inertia of {names[d]} (armature included) is {v:g}; it must be > 0")
         return np.asarray(inertia, np.float64)
-
-    @staticmethod
-    def _top_gains(config):
-        """per dof: kp Kp and kd Kd at the top of the DR gain ranges (robot.control gains by name, as env_config matches them)"""
-        rc, dr = config.robot, config.domain_rand
-        ctrl = rc.control
-        K, Kd = [], []
-        for name in rc.dof_names:
-            k = kd = 0.0
-            for joint in ctrl.stiffness.keys():
-                if joint in name:
-                    k, kd = float(ctrl.stiffness[joint]), float(ctrl.damping[joint])
-            K.append(k); Kd.append(kd)
-        K, Kd = np.asarray(K, np.float64), np.asarray(Kd, np.float64)
-        if dr.get("randomize_pd_gain", False):
-            K, Kd = K * float(dr.kp_range[1]), Kd * float(dr.kd_range[1])
-        pspd = dr.get("parallel_serial_pd", None)
-        if pspd is not None and pspd.get("enable", False):
-            K, Kd = K * max(1.0, float(pspd.ratio[1])), Kd * max(1.0, float(pspd.ratio[1]))
-        return K, Kd
 
     @classmethod
     def _check_stability(cls, config, inertia):
@@ -176,11 +137,6 @@ class JointSpaceSim(ReplaySimStub):
         if self.inertia is None and self.skeleton.body_mass is None:
             subtree_inertia(self.skeleton, None, None)       # refuses by name: no link masses
         return out
-
-    # ---- the window is the simulator's own -------------------------------------------------------------------------------------------
-    def set_replay(self, *a, **k):
-        raise _lib.PbhcError("JointSpaceSim.set_replay: the simulator writes its own one-frame window every control step; a replay window "
-                             "belongs to ReplaySimStub")
 
     def bind(self, env):
         """called by the env at the end of its construction: the one-frame window, the inertias, the kernel's parameters"""
@@ -199,27 +155,5 @@ class JointSpaceSim(ReplaySimStub):
         p = _lib.PbhcJointSimParams()
         for d in range(D):
             p.inertia[d], p.damping[d] = float(self.inertia[d]), float(self._damping[d])
-        p.contact_force, p.foot_height_threshold = self.contact_force, self.foot_height_threshold
-        p.enforce_limits, p.decimation = int(self.enforce_limits), int(self.decimation)
-        p.tau0 = None
+        self._fill_common(p)
         self._params = p
-
-    def _bind_window(self):
-        """the one-frame window the simulator's kernel writes and the step reads"""
-        N, B, dev = self.num_envs, self.num_bodies, self.device
-        # contact is zeroed ONCE, here: the kernel writes z of the foot bodies and nothing else
-        self.replay = dict(root=self.robot_root_states.clone()[None].contiguous(), dof_pos=self.dof_pos.clone()[None].contiguous(),
-                           dof_vel=self.dof_vel.clone()[None].contiguous(), contact=torch.zeros(1, N, B, 3, device=dev))
-        self.replay_len = 1
-        self.frame_cursor.zero_()
-        self._host_frame = 0
-        self.replay_version += 1
-
-    def set_debug_torques(self, on=True):
-        """keep the first sub-step's torque of every control step in `self.tau0 [N, D]` (what the step reports as `torques`)"""
-        self.tau0 = torch.zeros(self.num_envs, self.num_dof, device=self.device) if on else None
-        self._params.tau0 = self.tau0.data_ptr() if on else None
-
-    def advance(self, env):
-        """the frame of the control step about to be launched, on the current (stepping) stream"""
-        _lib.check(_lib.lib().pbhc_joint_sim_step(env._env, C.byref(env._io), C.byref(self._params), _lib.current_stream()), "pbhc_joint_sim_step")

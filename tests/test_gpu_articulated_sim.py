@@ -412,6 +412,56 @@ def test_first_substep_torque_is_the_steps_torque(cfgname, N, general, inject):
     assert bool(env._c.randomize_torque_rfi) and float(env._c.rfi_lim) > 0
 
 
+def _front_inputs(env):
+    """the live tensors the simulators' kernels read in front of the joint law, and the step's queue shift"""
+    s = env.simulator
+    return dict(dof_state=s.dof_state, queue=env.action_queue, delay=env.action_delay_idx, kp=env._kp_scale, kd=env._kd_scale, rfi=env._rfi_lim_scale,
+                rao=env._rao_scale, ep=env._episode_length_buf, start=env.motion_start_times, ids=env.motion_ids, origins=env.env_origins,
+                globals=env.globals)
+
+
+@pytest.mark.parametrize("inject", [True, False])
+def test_the_front_of_the_step_is_the_joint_simulators_bit_for_bit(inject):
+    """Everything in front of the joint law — the loads, the draws, the delayed action, the first sub-step's torque, the root row, the contact
+    rule — is one piece of device code (csrc/pbhc_closed_loop.h) under two lane mappings: from the same state, queue and scales and the same
+    action, ONE step of ArticulatedSim and of JointSpaceSim (same skeleton, any inertias) gives the same tau0, root frame, contact frame and
+    action queue, bit for bit.  N = 33: four full groups of 8 envs and a tail workgroup of one.
+    reset_all() ends with one zero-action step (base_task.py:83-93), which already runs each simulator's OWN joint law: after it the two
+    (q, v) differ, as they must.  So the articulated env's pre-step inputs are copied into the joint-space env, and asserted equal, before
+    the step that is compared."""
+    N = 33
+    sc = scenario(N, 23, 100.0)
+    envs = []
+    for target in (SIM, "pbhc_amd.simulator.joint_sim.JointSpaceSim"):
+        spec = {"inertia": [float(x) for x in sc["inertia"](23)], "damping": DAMP}
+        cfg, env = _build(WALK, N, False, extra={"simulator._target_": target, "simulator.config.joint_sim": spec})
+        assert type(env.simulator).__name__ == target.rsplit(".", 1)[1] and env.num_dof == 23
+        assert float(env._c.action_clip_value) == 100.0
+        _prepare(env, sc)
+        env.simulator.set_debug_torques(True)
+        env.set_injected_draws(u_rfi=torch.from_numpy(sc["u_rfi"][0]).to(env.device) if inject else None)
+        envs.append(env)
+    art, jnt = (_front_inputs(e) for e in envs)
+    print("differ after reset_all:", [k for k in art if not torch.equal(art[k], jnt[k])])
+    for k in art:
+        jnt[k].copy_(art[k])
+    torch.cuda.synchronize()
+    pre = [{k: v.clone() for k, v in _front_inputs(e).items()} for e in envs]
+    for k in pre[0]:
+        assert torch.equal(pre[0][k], pre[1][k]), ("the two simulators do not start from the same state", k)
+    assert int(pre[0]["delay"].max()) > 0, "no env has a delayed action"
+    out = []
+    for env in envs:
+        env.step({"actions": torch.from_numpy(sc["actions"][0]).to(env.device)})
+        torch.cuda.synchronize()
+        s = env.simulator
+        out.append(dict(tau0=s.tau0.clone(), root=s.replay["root"][0].clone(), contact=s.replay["contact"][0].clone(), queue=env.action_queue.clone()))
+    a, j = out
+    for k in a:
+        assert torch.equal(a[k], j[k]), (k, float((a[k] - j[k]).abs().max()))
+    assert float(a["tau0"].abs().max()) > 0 and float(a["contact"].abs().max()) > 0 and float(a["queue"].abs().max()) > 0
+
+
 @pytest.mark.parametrize("cfgname,N,general", CASES)
 def test_root_contact_and_base_acceleration_of_the_frame(cfgname, N, general):
     """the root the step consumed = the library's root body at (episode_length + 2) dt + start (pre-step values) + env origin; the contact frame
