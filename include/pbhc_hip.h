@@ -969,7 +969,9 @@ int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, f
                           int act, void* stream);
 /* pbhc_linear_dgrad_act for TWO layers in one launch on 32 x 128 tiles (the larger problem takes the leading workgroups; each problem has its
  * own scratch and row-block count = ceil(M / 32)): bit for bit the results of two pbhc_linear_dgrad_act calls that run on 32 x 128 tiles.
- * Refused for a problem that entry would not run so: needs 4 <= K <= 128 and N % 4 == 0.  The two M need not be equal. */
+ * Refused for a problem that entry would not run so: needs 4 <= K <= 128 and N % 4 == 0.  The two M need not be equal.  When both K are exactly
+ * 128 the pair runs the weight-stationary kernel (one persistent workgroup per CU holds a 128 x 128 slice of W in LDS), as the single entry
+ * does for such a problem on 32 x 128 tiles; the results are the same bits either way. */
 /* 1 if pbhc_linear_dgrad_act itself runs (M, N, K) on those tiles (its own tile choice; no test / measurement setting active), else 0:
  * ask this for BOTH problems before forming a pair, so that pairing never changes the tile height a layer runs on. */
 int pbhc_linear_dgrad_act_pairable(int M, int N, int K);
@@ -983,7 +985,10 @@ int pbhc_linear_wgrad_parts(int M, int N, int K);
 int pbhc_linear_wgrad(const float* dy, const float* x, float* dw, float* scratch, int M, int N, int K, void* stream);
 /* test / measurement aid for the Linear entries above.  shape < 0: everything automatic.  Otherwise bits 0-7: tile shape (0: 128x128, 1: 96x128,
  * 2: 64x128, 3: 64x64 forward only, 0xff: automatic); bits 8-15: K-loop ablation flags (tools/gemm_ablation.py; results are wrong with parts
- * off); bits 16-23: staging version (0: automatic, 1: register-staged version 1, 2: LDS-DMA with BK 16 x 3 stages). */
+ * off); bits 16-23: staging version (0: automatic, 1: register-staged version 1, 2: LDS-DMA with BK 16 x 3 stages, 4: automatic except that
+ * the K = 128 input gradients on 32 x 128 tiles stay on the ring kernel instead of the weight-stationary one — the pair entries and the
+ * pairable queries read 4 as 0); bits 24-30: workgroups of a weight-stationary launch (0: one per CU; raised to one per 128-column slice
+ * and capped at the number of tiles — no result depends on it). */
 void pbhc_gemm_debug_force_shape(int shape);
 
 /* The minibatch shuffle of one update (RolloutStorage.mini_batch_generator, agents/modules/data_utils.py:134-152: `tensor.flatten(0, 1)[indices]`

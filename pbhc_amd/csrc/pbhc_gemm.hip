@@ -723,11 +723,189 @@ __global__ __launch_bounds__(GEMM_T, 2) void k_gemm2(const float* __restrict__ A
 // rounds of tiles with a 4-16-stage K loop — prologue-, epilogue- and ramp-bound): workgroups [0, n0) run problem 0, the rest problem 1.
 // The choice is one scalar compare; the tile code, and with it every result, is k_gemm2's.  Launched with dbg = 0 in both argument sets: the
 // diagnosis branches of the tile code read blockIdx / gridDim of the whole grid and are for k_gemm2 alone.
+// MODE 1 pairs whose reductions are both exactly 128 (the shipped stacks' input gradient of the 128-wide layer) no longer run here but on
+// k_dgrad_ws below — the same tiles and arithmetic with W stationary in LDS; this kernel keeps the shorter reductions and stays reachable
+// for K = 128 as staging variant 4 of pbhc_gemm_debug_force_shape (tests/test_gpu_dgrad_stationary.py compares the two bit for bit).
 template <int MODE, int WM, int WN, int TM, int TN, int BK, int NS>
 __global__ __launch_bounds__(GEMM_T, 2) void k_gemm2_pair(Gemm2Args g0, Gemm2Args g1, int n0) {
   const bool first = (int)blockIdx.x < n0;
   const Gemm2Args g = first ? g0 : g1;
   gemm2_tile<MODE, WM, WN, TM, TN, BK, NS>(g, first ? blockIdx.x : blockIdx.x - n0, first ? n0 : gridDim.x - n0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Weight-stationary input gradient for a reduction of exactly 128 (the 128-wide last hidden layers: dx[M, N] = dy[M, 128] . W[128, N]) on the
+// 32 x 128 tiles of k_gemm2<1, 1, 4, 1, 1, 32, 2>.  There a tile is four K stages in a ring of two — every stage's wait, barrier and DMA landing
+// exposed once per 16 MFMAs of a wave — and pulls its own 64 KB slice of W through LDS-DMA.  Here a workgroup owns one (problem, 128-column
+// tile) slice and a contiguous run of that slice's row tiles: W's slice is fetched ONCE, in the ring kernel's MODE-1 layout ([k][128], chunks
+// rotated by 8 for k rows with bit 2 set), and only the 16 KB dy tiles stream past it, each in one burst of 16 pieces laid out as the ring's
+// four [row][32] swizzled stages.  A tile's arithmetic is the ring kernel's to the bit: 64 MFMAs per wave in the order stage, k8, s from zero
+// accumulators, the [32][132] image, gemm_mul_grad4 over rows p = 0..3 with csum in that order, the eight row groups summed 0..7.
+//
+// Eight waves as two teams of four, each with the ring kernel's 256-thread (row, column) mapping, its own dy buffer, image and column-sum
+// rows.  The teams take alternate tiles of the run and alternate ROLES in lock step, two workgroup barriers per half step:
+//   half step h:   team h & 1        | wait dy(h) . barrier A . request saved(h), MFMA blocks 0-7   . barrier B . MFMA blocks 8-15
+//                  team (h - 1) & 1  | wait saved(h-1), acc -> image . barrier A . request dy(h+1), row pass, stores, csum . barrier B . part
+// so a SIMD always holds one wave that issues MFMAs and one that runs the previous tile's epilogue; dy and the saved activations are
+// requested a whole half step (64 MFMAs, ~1.7 us) before they are waited for.  All vector-memory waits are vmcnt(0) at the head of a half
+// step: the loads are issued from asm (the compiler's own bookkeeping would otherwise order every LDS read behind a pending LDS-DMA).
+// Rows / columns beyond M / N: addresses clamped, nothing stored or summed, as in the ring kernel.  Which workgroup computes a tile changes
+// no result, so the workgroup count is free (one per CU by default).
+#define WS_T 512
+constexpr int WS_W_FLOATS = 128 * 128, WS_DY_FLOATS = 32 * 128, WS_CS = 132, WS_IMG_FLOATS = 32 * WS_CS, WS_RED_FLOATS = 8 * 128;
+constexpr int WS_TEAM_FLOATS = WS_DY_FLOATS + WS_IMG_FLOATS + WS_RED_FLOATS;
+constexpr int WS_LDS_BYTES = (WS_W_FLOATS + 2 * WS_TEAM_FLOATS) * 4;      // 64 KB + 2 x (16 KB + 16.5 KB + 4 KB) = 140 288 B of the CU's 160 KB
+
+__device__ __forceinline__ f32x4 gload16_sv(const void* sbase, unsigned voff) {      // 16 bytes at SGPR base + 32-bit VGPR byte offset; retired by an explicit wait
+  f32x4 v;
+  asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(v) : "v"(voff), "s"(sbase) : "memory");
+  return v;
+}
+
+__global__ __launch_bounds__(WS_T) void k_dgrad_ws(Gemm2Args g0, Gemm2Args g1, int n0) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  // ---- this workgroup's problem, slice and run of row tiles: the problem's G workgroups go to its tiles_n slices as evenly as they divide
+  // (the first G % tiles_n slices have one more), a slice's row tiles to its workgroups likewise ----
+  const bool first = (int)blockIdx.x < n0;
+  const Gemm2Args g = first ? g0 : g1;
+  const float* __restrict__ A = g.A;
+  const float* __restrict__ B = g.B;
+  const float* __restrict__ S = g.S;
+  float* __restrict__ Cout = g.Cout;
+  float* __restrict__ part = g.part;
+  const int M = g.M, N = g.N, act = g.act, tn = g.tiles_n;
+  int b = first ? (int)blockIdx.x : (int)blockIdx.x - n0;
+  const int G = first ? n0 : (int)gridDim.x - n0;           // >= tn (the launcher sees to it)
+  const int q = G / tn, rem = G - q * tn;
+  int slice, wi, gs;
+  if (b < rem * (q + 1)) { slice = b / (q + 1); wi = b - slice * (q + 1); gs = q + 1; }
+  else { b -= rem * (q + 1); slice = rem + b / q; wi = b - (slice - rem) * q; gs = q; }
+  const int tiles_m = (M + 31) >> 5;
+  const int per = tiles_m / gs, extra = tiles_m - per * gs;
+  const int t0 = wi * per + min(wi, extra), cnt = per + (wi < extra ? 1 : 0);
+  if (cnt == 0) return;                                    // (more workgroups than row tiles: the whole workgroup leaves before any barrier)
+  const int col0 = slice * 128;
+
+  const int tid = threadIdx.x, lane = tid & 63, ltid = tid & 255;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int team = wave >> 2, wn = wave & 3;
+  const int r = lane & 31, kk = lane >> 5;
+  float* Wl = lds;
+  float* dyb = lds + WS_W_FLOATS + team * WS_TEAM_FLOATS;
+  float* img = dyb + WS_DY_FLOATS;
+  float* red = img + WS_IMG_FLOATS;
+
+  // ---- W[0:128, col0 : col0 + 128] -> Wl: 64 pieces of two k rows, eight per wave ----
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int bp = wave + 8 * i;
+    const int kr = 2 * bp + kk;
+    const int c = ((lane & 31) - 8 * ((kr >> 2) & 1)) & 31;
+    glds16_sv(B, ((unsigned)kr * (unsigned)N + (unsigned)min(col0 + 4 * c, N - 4)) * 4u, Wl + bp * 256);
+  }
+  // a team's dy tile: stage i of the four is piece wn of that stage's four 8-row pieces for this wave
+  const int dy_row = wn * 8 + (lane >> 3);
+  const int dy_c = (lane & 7) ^ ((dy_row >> 1) & 7);
+  auto issue_dy = [&](int tile) {
+    const int row0 = tile * 32;
+    const char* sb = reinterpret_cast<const char*>(A + (size_t)row0 * 128);
+    const unsigned vo = ((unsigned)min(dy_row, M - 1 - row0) * 128u + 4u * dy_c) * 4u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16_sv(sb, vo + 128u * i, dyb + (4 * i + wn) * 256);
+  };
+  if (team < cnt) issue_dy(t0 + team);
+
+  // constant per-lane fragment indices (floats), as in gemm2_tile
+  const int sw_r = (r >> 1) & 7;
+  int fa[4];
+#pragma unroll
+  for (int k8 = 0; k8 < 4; ++k8) fa[k8] = r * 32 + 4 * ((2 * k8 + kk) ^ sw_r);
+  const int fb = 4 * kk * 128 + ((wn * 32 + r + 32 * kk) & 127);
+  // the epilogue's thread -> (row, 4 columns) mapping inside the team
+  const int c4 = (ltid & 31) * 4, rr = ltid >> 5;
+  const bool cok = col0 + c4 < N;
+
+  f32x16 acc;
+  f32x4 sv[4], fra[2], frb[2];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) sv[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+  fra[0] = fra[1] = frb[0] = frb[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto read_frags = [&](int kb, f32x4& af, f32x4& bf) {    // k block kb of 16: stage kb / 4, k8 = kb % 4
+    af = *reinterpret_cast<const f32x4*>(&dyb[(kb >> 2) * 1024 + fa[kb & 3]]);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) bf[s] = Wl[(kb * 8 + s) * 128 + fb];
+  };
+  auto mfma_blocks = [&](auto half_c) {                    // eight k blocks; the next block's fragments are read while this block's MFMAs run
+    constexpr int K0 = decltype(half_c)::value * 8;
+#pragma unroll
+    for (int kb = K0; kb < K0 + 8; ++kb) {
+      if (kb + 1 < 16) read_frags(kb + 1, fra[(kb + 1) & 1], frb[(kb + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fra[kb & 1][s], frb[kb & 1][s], acc, 0, 0, 0);
+    }
+  };
+
+  for (int h = 0; h <= cnt; ++h) {
+    const bool mf = h < cnt && (h & 1) == team;            // this team's MFMAs of tile t0 + h
+    const bool ep = h >= 1 && ((h - 1) & 1) == team;       // this team's epilogue of tile t0 + h - 1
+    float csum[4] = {0.f, 0.f, 0.f, 0.f};
+    wait_vmcnt<0>();                                       // dy(h) / saved(h - 1) (and W, the first time) have landed for this wave
+    asm volatile("" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]));      // (the saved activations are read only behind the wait)
+    if (ep) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) img[(8 * (e >> 2) + 4 * kk + (e & 3)) * WS_CS + wn * 32 + r] = acc[e];
+    }
+    lds_barrier_raw();                                     // A: dy(h) is in LDS for its team; the other team's image is complete; every wave is done with its MFMAs of h - 1
+    if (mf) {
+      const int row0 = (t0 + h) * 32;
+      if (act) {                                           // the lower layer's saved activations of this tile: in flight under its MFMAs
+        const char* sb = reinterpret_cast<const char*>(S + (size_t)row0 * N + col0);
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+          sv[p] = gload16_sv(sb, ((unsigned)min(p * 8 + rr, M - 1 - row0) * (unsigned)N + (unsigned)min(c4, N - 4 - col0)) * 4u);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+      read_frags(0, fra[0], frb[0]);
+      mfma_blocks(IC<0>{});
+    }
+    if (ep) {
+      if (h + 1 < cnt) issue_dy(t0 + h + 1);               // the team's next tile (its MFMAs of h - 1 are behind barrier A)
+      const int row0 = (t0 + h - 1) * 32;
+      const int col = col0 + c4;
+      auto row_pass = [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int row = row0 + p * 8 + rr;
+          f32x4 v = *reinterpret_cast<const f32x4*>(&img[(p * 8 + rr) * WS_CS + c4]);
+          if (ACT) v = gemm_mul_grad4<ACT>(v, sv[p]);
+          if (row < M && cok) {
+            reinterpret_cast<F4U*>(Cout + (size_t)row * N + col)->v = v;
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) csum[qq] += v[qq];      // rows in the fixed order p = 0, 1, ...
+          }
+        }
+      };
+      if (act == 1) row_pass(IC<1>{}); else if (act == 2) row_pass(IC<2>{}); else if (act == 3) row_pass(IC<3>{}); else row_pass(IC<0>{});
+      if (part) {
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) red[rr * 128 + c4 + qq] = csum[qq];
+      }
+    }
+    lds_barrier_raw();                                     // B: the team's eight rows of column sums are complete
+    if (mf) mfma_blocks(IC<1>{});
+    if (ep && part && ltid < 128) {                        // the eight row groups in the fixed order 0..7
+      float t = 0.0f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) t += red[w * 128 + ltid];
+      if (col0 + ltid < N) part[(size_t)(t0 + h - 1) * N + col0 + ltid] = t;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -941,7 +1119,8 @@ static hipError_t gemm2_launch(const float* A, const float* B, const float* bias
 #ifndef PBHC_GEMM_BK
 #define PBHC_GEMM_BK 32
 #endif
-static int g_variant = 0;                                  // diagnosis: 0 automatic (version 2 where it applies); 1 force version 1 (register staging); 2 version 2 with BK 16 x 3 stages
+static int g_variant = 0;                                  // diagnosis: 0 automatic (version 2 where it applies); 1 force version 1 (register staging); 2 version 2 with BK 16 x 3 stages;
+                                                           // 4 automatic, but the K = 128 input gradients stay on the ring kernel (see dgrad_ws_applies)
 template <int MODE, int WM, int WN, int TM, int TN>
 static hipError_t gemm_variant(const float* A, const float* B, const float* bias, const float* S, float* C, float* pre, float* part, int M, int N, int K, int act,
                                hipStream_t st) {
@@ -973,7 +1152,9 @@ static int pick_shape(int M, int N, int K, int forced, bool forward) {
   // (K 256 / 512) and the input gradients of layers with <= 128 outputs (K = out_features): more workgroups in flight hide a tile's prologue and
   // epilogue, which is most of such a launch.  Chosen from the update's own trace (profiles/round2_update_step_timeline.txt: forward 128x256
   // 28.5 -> 20.0 us, 128x512 36.3 -> 31.9; input gradient 21 -> 128 17.2 -> 10.5, 23 -> 128 15.7 -> 9.2, 128 -> 512 42.3 -> 39.8); the wider layers
-  // lose 2-10 % on it there although a back-to-back probe (tools/gemm_probe.py --shape 2,4, operands warm in L2) shows them 3-8 % faster
+  // lose 2-10 % on it there although a back-to-back probe (tools/gemm_probe.py --shape 2,4, operands warm in L2) shows them 3-8 % faster.
+  // An input gradient that lands here with K == 128 exactly runs these 32 x 128 tiles on the weight-stationary k_dgrad_ws (four ring stages per
+  // tile made the ring kernel's hand-overs most of such a tile; profiles/dgrad_stationary.txt); K < 128 stays on the ring kernel
   if (M <= 32 * PBHC_ACT_MAX_BLOCKS && M >= 8192 && (forward ? N <= 128 : K <= 128)) return 4;
   if (N <= 128 && M % 96 == 0 && (M / 96) % 256 == 0) return 1;
   // few rows (the rollout's 4 096-row policy / critic forward): 64 x 64 tiles keep every CU busy where 64 x 128 tiles would leave fewer than two
@@ -983,13 +1164,54 @@ static int pick_shape(int M, int N, int K, int forced, bool forward) {
 }
 static int g_force_shape = -1;
 
+// ---- the weight-stationary input gradient (k_dgrad_ws): one or two problems with K == 128 on 32 x 128 tiles ----
+// g_variant 4 (diagnosis) keeps these shapes on the ring kernel and changes nothing else: everywhere but here it reads as 0.
+static bool variant_plain() { return g_variant == 0 || g_variant == 4; }
+static int g_ws_wgs = 0;                                   // diagnosis: workgroups of a k_dgrad_ws launch (0: one per CU)
+static int g_ws_cus = 0;
+// The kernel's 137 KB of dynamic LDS has to be granted once, and not inside a stream capture: pbhc_linear_dgrad_act_pairable — asked when an
+// update is planned, before any capture — does it; a launch that comes first does it itself.
+static hipError_t dgrad_ws_init() {
+  if (g_ws_cus > 0) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dgrad_ws), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
+  if (e != hipSuccess) return e;
+  int dev = 0, cus = 0;
+  if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+  if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+  g_ws_cus = cus > 0 ? cus : 256;
+  return hipSuccess;
+}
+static bool dgrad_ws_applies(int M, int N, int K) {        // (M, N, K) already known to run on 32 x 128 tiles of the LDS-DMA kernel
+  return K == 128 && g_variant == 0 && g_dbg == 0;
+}
+// p1 == nullptr: one problem.  Workgroups go to the problems in proportion to their tiles, at least one per 128-column slice; inside a problem
+// the kernel splits them over the slices and a slice's row tiles over its workgroups, remainders of at most one.
+static hipError_t dgrad_ws_launch(const Gemm2Args& p0, const Gemm2Args* p1, hipStream_t st) {
+  hipError_t e = dgrad_ws_init();
+  if (e != hipSuccess) return e;
+  const long long w0 = (long long)((p0.M + 31) / 32) * p0.tiles_n, w1 = p1 ? (long long)((p1->M + 31) / 32) * p1->tiles_n : 0;
+  const int slices = p0.tiles_n + (p1 ? p1->tiles_n : 0);
+  long long G = g_ws_wgs > 0 ? g_ws_wgs : g_ws_cus;
+  if (G > w0 + w1) G = w0 + w1;
+  if (G < slices) G = slices;
+  long long G0 = G;
+  if (p1) {
+    G0 = (G * w0 + (w0 + w1) / 2) / (w0 + w1);
+    if (G0 < p0.tiles_n) G0 = p0.tiles_n;
+    if (G0 > G - p1->tiles_n) G0 = G - p1->tiles_n;
+  }
+  hipLaunchKernelGGL(k_dgrad_ws, dim3((unsigned)G), dim3(WS_T), WS_LDS_BYTES, st, p0, p1 ? *p1 : p0, (int)G0);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 void pbhc_gemm_debug_force_shape(int shape) {
-  if (shape < 0) { g_force_shape = -1; g_dbg = 0; g_variant = 0; return; }
+  if (shape < 0) { g_force_shape = -1; g_dbg = 0; g_variant = 0; g_ws_wgs = 0; return; }
   g_force_shape = (shape & 0xff) == 0xff ? -1 : shape & 0xff;
   g_dbg = (shape >> 8) & 0xff;
   g_variant = (shape >> 16) & 0xff;
+  g_ws_wgs = (shape >> 24) & 0x7f;
 }
 
 int pbhc_linear_act_fwd(const float* x, const float* w, const float* bias, float* y, float* pre, int M, int N, int K, int act, void* stream) {
@@ -1022,9 +1244,11 @@ static int dgrad_shape(int M, int N, int K) {             // the tile shape pbhc
 
 int pbhc_linear_dgrad_act_pairable(int M, int N, int K) {
   // what k_gemm2_pair<1, ...> is built for: the LDS-DMA kernel (gemm_variant's v2ok) on 32 x 128 tiles, chosen by the entry itself
-  if (M < 1 || N < 1 || K < 1 || g_variant != 0 || g_dbg != 0) return 0;
+  if (M < 1 || N < 1 || K < 1 || !variant_plain() || g_dbg != 0) return 0;
   const bool v2ok = K >= 4 && (N & 3) == 0 && (size_t)M * K < (1u << 30) && (size_t)K * N < (1u << 30);
-  return v2ok && dgrad_shape(M, N, K) == 4;
+  if (!(v2ok && dgrad_shape(M, N, K) == 4)) return 0;
+  if (dgrad_ws_applies(M, N, K)) (void)dgrad_ws_init();     // (outside any capture; an error here comes back from the launch)
+  return 1;
 }
 
 int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, float* dx, float* scratch, int* num_row_blocks, int M, int N, int K,
@@ -1036,6 +1260,12 @@ int pbhc_linear_dgrad_act(const float* dy, const float* w, const float* saved, f
   GEMM_ARG(!scratch || nb <= PBHC_ACT_MAX_BLOCKS);
   if (num_row_blocks) *num_row_blocks = nb;
   // A = dy [M, K] (K = out_features of the layer, the reduction), B = W [K, N] (N = in_features, contiguous)
+  const bool v2ok = K >= 4 && (N & 3) == 0 && (size_t)M * K < (1u << 30) && (size_t)K * N < (1u << 30);      // (gemm_variant's, MODE 1)
+  if (shape == 4 && v2ok && dgrad_ws_applies(M, N, K)) {
+    const Gemm2Args p{dy, w, nullptr, saved, dx, nullptr, scratch, M, N, K, act, (N + 127) / 128, 0, K, N, GemmOutLayer{nullptr, nullptr, nullptr, 0}};
+    GEMM_HIP(dgrad_ws_launch(p, nullptr, (hipStream_t)stream));
+    return PBHC_OK;
+  }
   GEMM_HIP(gemm_dispatch<1>(shape, dy, w, nullptr, saved, dx, nullptr, scratch, M, N, K, act, (hipStream_t)stream));
   return PBHC_OK;
 }
@@ -1081,7 +1311,7 @@ int pbhc_linear_act_fwd_out_pair(const float* x0, const float* w0, const float* 
   int rc = fwd_out_check(x0, w0, y0, M0, N0, K0, act0, w_out0, NO0, out0);
   if (rc == PBHC_OK) rc = fwd_out_check(x1, w1, y1, M1, N1, K1, act1, w_out1, NO1, out1);
   if (rc != PBHC_OK) return rc;
-  if (g_variant != 0 || g_dbg != 0) {                      // a diagnosis setting of the single entry (staging variant, ablation flags): two single launches
+  if (!variant_plain() || g_dbg != 0) {                    // a diagnosis setting of the single entry (staging variant, ablation flags): two single launches
     rc = pbhc_linear_act_fwd_out(x0, w0, bias0, y0, pre0, M0, N0, K0, act0, w_out0, b_out0, NO0, out0, stream);
     return rc != PBHC_OK ? rc : pbhc_linear_act_fwd_out(x1, w1, bias1, y1, pre1, M1, N1, K1, act1, w_out1, b_out1, NO1, out1, stream);
   }
@@ -1097,13 +1327,15 @@ int pbhc_linear_dgrad_act_pair(const float* dy0, const float* w0, const float* s
   int rc = dgrad_pair_check(dy0, w0, saved0, dx0, scratch0, num_row_blocks0, M0, N0, K0, act0);
   if (rc == PBHC_OK) rc = dgrad_pair_check(dy1, w1, saved1, dx1, scratch1, num_row_blocks1, M1, N1, K1, act1);
   if (rc != PBHC_OK) return rc;
-  GEMM_ARG(g_variant == 0 && g_dbg == 0);                  // (diagnosis settings change what the single entry runs: see pbhc_linear_dgrad_act_pairable)
+  GEMM_ARG(variant_plain() && g_dbg == 0);                 // (diagnosis settings change what the single entry runs: see pbhc_linear_dgrad_act_pairable)
   if (num_row_blocks0) *num_row_blocks0 = (M0 + 31) / 32;
   if (num_row_blocks1) *num_row_blocks1 = (M1 + 31) / 32;
   const GemmOutLayer none{nullptr, nullptr, nullptr, 0};
   const Gemm2Args p0{dy0, w0, nullptr, saved0, dx0, nullptr, scratch0, M0, N0, K0, act0, (N0 + 127) / 128, 0, K0, N0, none};
   const Gemm2Args p1{dy1, w1, nullptr, saved1, dx1, nullptr, scratch1, M1, N1, K1, act1, (N1 + 127) / 128, 0, K1, N1, none};
-  GEMM_HIP((gemm2_pair_launch<1, 1>(p0, p1, (size_t)N1 * K1 > (size_t)N0 * K0, (hipStream_t)stream)));
+  const bool swap = (size_t)N1 * K1 > (size_t)N0 * K0;
+  if (dgrad_ws_applies(M0, N0, K0) && dgrad_ws_applies(M1, N1, K1)) GEMM_HIP(dgrad_ws_launch(swap ? p1 : p0, swap ? &p0 : &p1, (hipStream_t)stream));
+  else GEMM_HIP((gemm2_pair_launch<1, 1>(p0, p1, swap, (hipStream_t)stream)));
   return PBHC_OK;
 }
 
@@ -1111,7 +1343,7 @@ int pbhc_linear_dgrad_act_pair(const float* dy0, const float* w0, const float* s
 int pbhc_linear_act_fwd_pairable(int M, int N, int K) {
   // 1 exactly when pbhc_linear_act_fwd itself launches k_gemm2<0, 1, 4, 2, 1, 32, 2>: pick_shape() says 2 (a forced shape counts: it is what
   // the single entry runs), gemm_variant's v2ok holds and no diagnosis setting is active
-  if (M < 1 || N < 1 || K < 1 || g_variant != 0 || g_dbg != 0) return 0;
+  if (M < 1 || N < 1 || K < 1 || !variant_plain() || g_dbg != 0) return 0;
   const bool v2ok = K >= 4 && (size_t)M * K < (1u << 30) && (size_t)N * K < (1u << 30);
   return v2ok && pick_shape(M, N, K, g_force_shape, true) == 2;
 }
