@@ -14,6 +14,7 @@
 #ifndef PBHC_HIP_H
 #define PBHC_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

@@ -1,9 +1,10 @@
 """ctypes binding of libpbhc_hip.so (include/pbhc_hip.h).
 
-The ctypes Structures are generated from the header text itself, so the Python view of the ABI
-cannot drift from the C one; sizes are cross-checked against `pbhc_sizeof_*()` at load.
-There is no fallback: if the library is missing or was built for another ABI, using the
-product raises.
+Everything the binding knows about the ABI comes from one parse of the header text: the constants, the ctypes Structures, the
+prototype (restype, argtypes) of every declared function, the list of exports and the `pbhc_sizeof_*()` / struct pairs that are
+compared at load.  A declaration the parser does not understand raises at import; nothing is skipped.  tests/test_abi.py holds the
+derived prototypes and struct layouts against a C++ compiler's view of the same header.
+There is no fallback: if the library is missing or was built for another ABI, using the product raises.
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ LIB_PATH = os.environ.get("PBHC_LIB", os.path.join(_HERE, "libpbhc_hip.so"))   #
 _CTYPES = {
     "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
     "float": C.c_float, "double": C.c_double, "uint8_t": C.c_uint8, "int": C.c_int,
+    "size_t": C.c_size_t, "long long": C.c_longlong,
 }
 
 
@@ -27,8 +29,34 @@ def _strip_comments(t):
     return re.sub(r"//[^\n]*", "", t)
 
 
-def _parse_header(path):
-    text = _strip_comments(open(path).read())
+def _ctype(decl, structs, opaque, fn):
+    """The mapping rule: one return type or parameter of the declaration of `fn` -> its ctypes type (None for void).
+    Scalars and structs by value map to themselves, `const char*` to c_char_p, one level of pointer to a struct with a body to
+    POINTER(that class) (so the wrong struct raises on the host), every other pointer to a known type to c_void_p (callers pass
+    tensor.data_ptr() integers, byref, arrays or None).  Anything else raises."""
+    m = re.fullmatch(r"(const\s+)?(long long|\w+)((?:\s*\*(?:\s*const\b)?)*)\s*(\w+)?", " ".join(decl.split()))
+    if m:
+        const, base, stars = m.group(1), m.group(2), m.group(3).count("*")
+        if stars == 0:
+            if base == "void" and not m.group(4):
+                return None
+            if base in _CTYPES:
+                return _CTYPES[base]
+            if base in structs:
+                return structs[base]
+        elif base in structs:
+            if stars == 1:
+                return C.POINTER(structs[base])
+        elif base == "char" and const and stars == 1:
+            return C.c_char_p
+        elif base in _CTYPES or base in opaque or base in ("void", "char"):
+            return C.c_void_p
+    raise ValueError(f"{fn}: no ctypes mapping for '{decl.strip()}' in include/pbhc_hip.h")
+
+
+def _parse_header(text):
+    """header text -> (constants, Structures by name, {function: (restype, [argtypes])}, {pbhc_sizeof_* function: its Structure})"""
+    text = _strip_comments(text)
     consts = {}
     for m in re.finditer(r"#define\s+(PBHC_\w+)\s+\(?(-?\d+)\)?", text):
         consts[m.group(1)] = int(m.group(2))
@@ -73,51 +101,31 @@ def _parse_header(path):
                     ct = ct * d
                 fields.append((vname, ct))
         structs[name] = type(name, (C.Structure,), {"_fields_": fields})
-    return consts, structs
+    opaque = set(re.findall(r"typedef\s+struct\s+(\w+)\s+\1\s*;", text))
+    protos = {}
+    for m in re.finditer(r"^[ \t]*([\w \t*]+?)\s*\b(pbhc_\w+)\s*\(([^;{}]*)\)\s*;", text, flags=re.M):
+        ret, fn, params = m.groups()
+        args = [] if params.strip() in ("", "void") else [_ctype(p, structs, opaque, fn) for p in params.split(",")]
+        if None in args:
+            raise ValueError(f"{fn}: a parameter of type void in include/pbhc_hip.h")
+        protos[fn] = (_ctype(ret, structs, opaque, fn), args)
+    missing = set(re.findall(r"\b(pbhc_\w+)\s*\(", text)) - set(protos)
+    if missing:
+        raise ValueError(f"include/pbhc_hip.h names functions whose declarations were not parsed: {sorted(missing)}")
+    squash = {s.replace("_", "").lower(): cls for s, cls in structs.items()}
+    sizeofs = {}
+    for fn in protos:
+        if fn.startswith("pbhc_sizeof_"):
+            key = "pbhc" + fn[len("pbhc_sizeof_"):].replace("_", "")
+            if key not in squash:
+                raise ValueError(f"{fn}: include/pbhc_hip.h defines no struct of that name")
+            sizeofs[fn] = squash[key]
+    return consts, structs, protos, sizeofs
 
 
-K, _S = _parse_header(HEADER)
-PbhcSkeleton = _S["PbhcSkeleton"]
-PbhcOutMap = _S["PbhcOutMap"]
-PbhcEnvConfig = _S["PbhcEnvConfig"]
-PbhcMotionTable = _S["PbhcMotionTable"]
-PbhcStepIO = _S["PbhcStepIO"]
-PbhcRecordIO = _S["PbhcRecordIO"]
-PbhcMlpSample = _S["PbhcMlpSample"]
-PbhcMlpInput = _S["PbhcMlpInput"]
-PbhcRider = _S["PbhcRider"]
-PbhcConvEncoder = _S["PbhcConvEncoder"]
-PbhcPpoReduce = _S["PbhcPpoReduce"]
-PbhcSqnorm = _S["PbhcSqnorm"]
-PbhcMotionExtend = _S["PbhcMotionExtend"]
-PbhcMotionAugment = _S["PbhcMotionAugment"]
-PbhcMotionScreen = _S["PbhcMotionScreen"]
-PbhcMirrorJob = _S["PbhcMirrorJob"]
-PbhcJointSimParams = _S["PbhcJointSimParams"]
-PbhcArticulatedParams = _S["PbhcArticulatedParams"]
-PbhcRetargetParams = _S["PbhcRetargetParams"]
-PbhcRetargetState = _S["PbhcRetargetState"]
-
-EXPORTS = ["pbhc_abi_version", "pbhc_last_error", "pbhc_sizeof_env_config", "pbhc_sizeof_step_io", "pbhc_motion_build",
-           "pbhc_motion_state", "pbhc_sim_fk", "pbhc_env_create", "pbhc_env_destroy", "pbhc_env_step", "pbhc_gae",
-           "pbhc_env_profile", "pbhc_env_profile_read", "pbhc_env_profile_overhead", "pbhc_ppo_loss", "pbhc_ppo_loss_scratch_floats", "pbhc_adam_clip",
-           "pbhc_policy_sample", "pbhc_rollout_post", "pbhc_act_bwd_bias", "pbhc_env_finalize", "pbhc_act_bwd_partials", "pbhc_colsum_final", "pbhc_adam_clip2", "pbhc_debug_rotations", "pbhc_motion_build_batch",
-           "pbhc_linear_act_fwd", "pbhc_env_config_lds_bytes", "pbhc_linear_act_fwd_out", "pbhc_debug_out_bwd_variant", "pbhc_gather_rows", "pbhc_linear_dgrad_act", "pbhc_gemm_debug_force_shape", "pbhc_linear_wgrad", "pbhc_linear_wgrad_parts", "pbhc_linear_act_fwd_strided",
-           "pbhc_env_step_launch", "pbhc_env_step_finish", "pbhc_mlp_fwd", "pbhc_mlp_fwd_lds_bytes", "pbhc_mlp_pack", "pbhc_mlp_packed_floats", "pbhc_rollout_post2", "pbhc_mlp_fwd_sample", "pbhc_linear_out_bwd",
-           "pbhc_env_get_config", "pbhc_env_attach_specialised", "pbhc_env_is_specialised", "pbhc_env_config_finalize", "pbhc_kl_lr_rule", "pbhc_debug_fk", "pbhc_mlp_fwd_cat", "pbhc_conv_encoder_fwd", "pbhc_conv_encoder_lds_bytes",
-           "pbhc_record_motion", "pbhc_sizeof_record_io", "pbhc_debug_rotvec_host",
-           "pbhc_clip_stats", "pbhc_clip_sampling_update", "pbhc_clip_sample_slots", "pbhc_clip_track",
-           "pbhc_start_stats", "pbhc_start_sampling_update", "pbhc_start_draw",
-           "pbhc_ppo_loss_partials", "pbhc_colsum_final_ppo_reduce",
-           "pbhc_colsum_final_ppo_reduce_sqnorm", "pbhc_colsum_final_ppo_reduce_sqnorm_slots", "pbhc_adam_clip2_parts",
-           "pbhc_motion_extend_batch", "pbhc_motion_augment_batch", "pbhc_motion_screen_frames", "pbhc_motion_screen_clips",
-           "pbhc_env_finalize_rider", "pbhc_mlp_fwd_sample_riders", "pbhc_mlp_fwd_cat_riders", "pbhc_debug_env_finalize",
-           "pbhc_linear_act_fwd_out_pair", "pbhc_linear_dgrad_act_pair", "pbhc_linear_dgrad_act_pairable",
-           "pbhc_linear_act_fwd_pairable", "pbhc_linear_act_fwd_pair",
-           "pbhc_mirror_rows", "pbhc_symmetry_loss",
-           "pbhc_sizeof_joint_sim_params", "pbhc_joint_sim_step",
-           "pbhc_sizeof_articulated_params", "pbhc_articulated_sim_step", "pbhc_debug_articulated_substeps",
-           "pbhc_sizeof_retarget_params", "pbhc_sizeof_retarget_state", "pbhc_retarget_loss_grad", "pbhc_retarget_fit", "pbhc_retarget_finish"]
+K, _S, _PROTOS, _SIZEOFS = _parse_header(open(HEADER).read())
+globals().update(_S)   # every struct of the header by its name: PbhcSkeleton, PbhcEnvConfig, PbhcStepIO, ...
+EXPORTS = list(_PROTOS)
 
 
 class PbhcError(RuntimeError):
@@ -131,108 +139,14 @@ def _load():
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C pbhc_amd/csrc`."
         )
     lib = C.CDLL(LIB_PATH)
-    lib.pbhc_last_error.restype = C.c_char_p
     if lib.pbhc_abi_version() != K["PBHC_ABI_VERSION"]:
         raise PbhcError("libpbhc_hip.so ABI version does not match include/pbhc_hip.h")
-    if (lib.pbhc_sizeof_env_config() != C.sizeof(PbhcEnvConfig) or lib.pbhc_sizeof_step_io() != C.sizeof(PbhcStepIO)
-            or lib.pbhc_sizeof_record_io() != C.sizeof(PbhcRecordIO) or lib.pbhc_sizeof_joint_sim_params() != C.sizeof(PbhcJointSimParams)
-            or lib.pbhc_sizeof_articulated_params() != C.sizeof(PbhcArticulatedParams)
-            or lib.pbhc_sizeof_retarget_params() != C.sizeof(PbhcRetargetParams) or lib.pbhc_sizeof_retarget_state() != C.sizeof(PbhcRetargetState)):
-        raise PbhcError("struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h — rebuild")
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
-    lib.pbhc_motion_build.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, f, vp, vp, vp]
-    lib.pbhc_motion_build_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
-    lib.pbhc_motion_extend_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, i, PbhcMotionExtend, vp, vp, vp, vp]
-    lib.pbhc_motion_augment_batch.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp, i, PbhcMotionAugment, vp, vp, vp, vp, vp]
-    lib.pbhc_motion_screen_frames.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, i, i, vp, PbhcMotionScreen, vp, vp, vp, vp, vp, vp]
-    lib.pbhc_motion_screen_clips.argtypes = [vp, vp, i, i, vp, vp, PbhcMotionScreen, vp, vp, vp]
-    lib.pbhc_motion_state.argtypes = [C.POINTER(PbhcMotionTable), i, i, vp, vp, vp, i, vp, vp]
-    lib.pbhc_sim_fk.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp]
-    lib.pbhc_debug_fk.argtypes = [C.POINTER(PbhcSkeleton), vp, vp, vp, i, i, vp, vp]
-    lib.pbhc_env_create.argtypes = [C.POINTER(PbhcEnvConfig), C.POINTER(PbhcMotionTable), vp, C.POINTER(vp)]
-    lib.pbhc_env_destroy.argtypes = [vp]
-    lib.pbhc_env_destroy.restype = None
-    lib.pbhc_env_get_config.argtypes = [vp, C.POINTER(PbhcEnvConfig)]
-    lib.pbhc_env_attach_specialised.argtypes = [vp, C.c_char_p]
-    lib.pbhc_env_is_specialised.argtypes = [vp]
-    lib.pbhc_env_config_finalize.argtypes = [C.POINTER(PbhcEnvConfig), C.POINTER(PbhcEnvConfig)]
-    lib.pbhc_env_config_lds_bytes.argtypes = [C.POINTER(PbhcEnvConfig)]
-    lib.pbhc_env_step.argtypes = [vp, C.POINTER(PbhcStepIO), vp]
-    lib.pbhc_env_step_launch.argtypes = [vp, C.POINTER(PbhcStepIO), vp]
-    lib.pbhc_env_step_finish.argtypes = [vp, C.POINTER(PbhcStepIO), vp]
-    lib.pbhc_env_finalize.argtypes = [vp, vp, C.c_double, vp]
-    lib.pbhc_record_motion.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcRecordIO), vp]
-    lib.pbhc_debug_rotvec_host.argtypes = [vp, i, vp, vp]
-    lib.pbhc_clip_stats.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
-    lib.pbhc_clip_sampling_update.argtypes = [vp, vp, vp, vp, vp, vp, i, C.c_double, C.c_double, C.c_double, vp]
-    lib.pbhc_clip_sample_slots.argtypes = [vp, i, C.c_uint64, C.c_uint32, vp, i, vp]
-    lib.pbhc_clip_track.argtypes = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcMotionTable)] + [vp] * 8 + [i, i, vp, vp]
-    lib.pbhc_start_stats.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, i, i, i, vp, vp]
-    lib.pbhc_start_sampling_update.argtypes = [vp, vp, vp, vp, vp, i, i, C.c_double, C.c_double, C.c_double, i, C.c_double, vp]
-    lib.pbhc_start_draw.argtypes = [vp, vp, vp, vp, vp, i, i, i, C.c_uint64, vp, C.c_uint32, vp, vp]
-    lib.pbhc_env_profile.argtypes = [vp, i]
-    lib.pbhc_env_profile_read.argtypes = [vp, C.POINTER(C.c_float), i, C.POINTER(C.c_int)]
-    lib.pbhc_env_profile_overhead.argtypes = [vp, vp, C.POINTER(C.c_float)]
-    lib.pbhc_ppo_loss.argtypes = [vp] * 10 + [i, i, i, f, f, f, i, f, i] + [vp] * 7 + [vp]
-    lib.pbhc_ppo_loss_scratch_floats.argtypes = [i]
-    lib.pbhc_kl_lr_rule.argtypes = [vp, i, vp, f, vp]
-    lib.pbhc_act_bwd_bias.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
-    lib.pbhc_act_bwd_partials.argtypes = [vp, vp, i, i, i, vp, vp, C.POINTER(C.c_int), vp]
-    lib.pbhc_colsum_final.argtypes = [vp, i, vp]
-    lib.pbhc_linear_out_bwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
-    lib.pbhc_ppo_loss_partials.argtypes = [vp] * 10 + [i, i, i, f, f, i, i, vp, vp, vp, C.POINTER(C.c_int), vp]
-    lib.pbhc_colsum_final_ppo_reduce.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), vp]
-    lib.pbhc_colsum_final_ppo_reduce_sqnorm.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), C.POINTER(PbhcSqnorm), vp]
-    lib.pbhc_colsum_final_ppo_reduce_sqnorm_slots.argtypes = [vp, i, C.POINTER(PbhcPpoReduce), C.POINTER(PbhcSqnorm), C.POINTER(C.c_int32)]
-    lib.pbhc_linear_act_fwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
-    lib.pbhc_linear_act_fwd_out.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp, vp]
-    lib.pbhc_linear_dgrad_act.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i, vp]
-    lib.pbhc_linear_act_fwd_out_pair.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, i, vp] * 2 + [vp]
-    lib.pbhc_linear_dgrad_act_pairable.argtypes = [i, i, i]
-    lib.pbhc_linear_dgrad_act_pair.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int), i, i, i, i] * 2 + [vp]
-    lib.pbhc_linear_act_fwd_pairable.argtypes = [i, i, i]
-    lib.pbhc_linear_act_fwd_pair.argtypes = [vp, vp, vp, vp, vp, i, i, i, i] * 2 + [vp]
-    lib.pbhc_gemm_debug_force_shape.argtypes = [i]
-    lib.pbhc_debug_out_bwd_variant.argtypes = [i]
-    lib.pbhc_gather_rows.argtypes = [vp, i, vp, i, vp]
-    lib.pbhc_mirror_rows.argtypes = [C.POINTER(PbhcMirrorJob), i, i, vp]
-    lib.pbhc_joint_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcJointSimParams), vp]
-    lib.pbhc_articulated_sim_step.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcArticulatedParams), vp]
-    lib.pbhc_debug_articulated_substeps.argtypes = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcArticulatedParams), vp, vp, vp, vp, i, i, f, i, vp, vp, vp, vp, vp]
-    _rt = [C.POINTER(PbhcSkeleton), C.POINTER(PbhcRetargetParams)]
-    lib.pbhc_retarget_loss_grad.argtypes = _rt + [vp] * 5 + [i, i, vp, vp] + [vp] * 6 + [vp]
-    lib.pbhc_retarget_fit.argtypes = _rt + [vp, vp, i, i, vp, vp, C.POINTER(PbhcRetargetState), i, vp, vp]
-    lib.pbhc_retarget_finish.argtypes = _rt + [vp, i, i, vp, vp, C.POINTER(PbhcRetargetState), vp, vp, vp, vp]
-    lib.pbhc_symmetry_loss.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp]
-    lib.pbhc_debug_out_bwd_variant.restype = None
-    lib.pbhc_linear_wgrad_parts.argtypes = [i, i, i]
-    lib.pbhc_linear_act_fwd_strided.argtypes = [vp, i, C.c_longlong, vp, vp, vp, vp, i, C.c_longlong, i, i, i, i, i, vp]
-    lib.pbhc_linear_wgrad.argtypes = [vp, vp, vp, vp, i, i, i, vp]
-    lib.pbhc_mlp_fwd.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, vp, i, i, vp]
-    lib.pbhc_mlp_fwd_sample.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, i, C.POINTER(PbhcMlpSample), vp]
-    lib.pbhc_conv_encoder_lds_bytes.argtypes = [C.POINTER(PbhcConvEncoder)]
-    lib.pbhc_conv_encoder_lds_bytes.restype = C.c_size_t
-    lib.pbhc_conv_encoder_fwd.argtypes = [vp, i, C.POINTER(PbhcConvEncoder), vp, i, i, vp]
-    lib.pbhc_mlp_fwd_cat.argtypes = [C.POINTER(PbhcMlpInput), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, vp, i, i, C.POINTER(PbhcMlpSample), vp]
-    lib.pbhc_env_finalize_rider.argtypes = [vp, C.POINTER(PbhcStepIO), C.POINTER(PbhcRider)]
-    lib.pbhc_debug_env_finalize.argtypes = [C.POINTER(PbhcRider), vp]
-    lib.pbhc_mlp_fwd_sample_riders.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, i, C.POINTER(PbhcMlpSample), C.POINTER(PbhcRider), vp]
-    lib.pbhc_mlp_fwd_cat_riders.argtypes = [C.POINTER(PbhcMlpInput), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, i, vp, i, i, C.POINTER(PbhcMlpSample),
-                                            C.POINTER(PbhcRider), vp]
-    lib.pbhc_mlp_fwd_lds_bytes.argtypes = [C.POINTER(i), i]
-    lib.pbhc_mlp_fwd_lds_bytes.restype = C.c_size_t
-    lib.pbhc_mlp_pack.argtypes = [vp, i, i, vp, vp]
-    lib.pbhc_mlp_packed_floats.argtypes = [i, i]
-    lib.pbhc_mlp_packed_floats.restype = C.c_size_t
-    lib.pbhc_gemm_debug_force_shape.restype = None
-    lib.pbhc_adam_clip.argtypes = [vp, vp, vp, vp, i, vp, vp, f, f, f, f, f, vp, vp, vp]
-    lib.pbhc_adam_clip2.argtypes = [vp, vp, vp, vp, i, i, vp, vp, f, f, f, f, f, i, vp, vp, vp]
-    lib.pbhc_adam_clip2_parts.argtypes = [vp, vp, vp, vp, i, i, vp, vp, f, f, f, f, f, i, vp, i, vp, i, vp, vp]
-    lib.pbhc_policy_sample.argtypes = [vp, vp, vp, i, i, i, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
-    lib.pbhc_rollout_post.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp, vp]
-    lib.pbhc_rollout_post2.argtypes = [vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp, vp, vp]
-    lib.pbhc_gae.argtypes = [vp, vp, vp, vp, i, i, i, f, f, vp, vp, vp, vp]
-    lib.pbhc_debug_rotations.argtypes = [i, vp, vp, vp, i, vp, vp]
+    for name, (restype, argtypes) in _PROTOS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    for name, struct in _SIZEOFS.items():
+        if getattr(lib, name)() != C.sizeof(struct):
+            raise PbhcError(f"struct layout mismatch between libpbhc_hip.so and include/pbhc_hip.h ({struct.__name__}) — rebuild")
     return lib
 
 

@@ -140,7 +140,7 @@ def _launch_jobs(job_list, st, reduce=None):
     lib = _lib.lib()
     for k in range(0, max(len(job_list), 1), MAXJ):
         chunk = job_list[k:k + MAXJ]
-        jobs = (_lib._S["PbhcColsumJob"] * MAXJ)()
+        jobs = (_lib.PbhcColsumJob * MAXJ)()
         for j, (part, out, nrb, n) in zip(jobs, chunk):
             j.part, j.out, j.num_row_blocks, j.n = part, out, nrb, n
         if reduce is not None and k + MAXJ >= len(job_list):
@@ -211,7 +211,7 @@ class StepSqnorm:
             base += 4 * n
         P = StepSqnorm.Plan()
         P.num_jobs = len(job_list)
-        P.jobs = (_lib._S["PbhcColsumJob"] * max(P.num_jobs, 1))()
+        P.jobs = (_lib.PbhcColsumJob * max(P.num_jobs, 1))()
         for j, (part, out, nrb, n) in zip(P.jobs, job_list):
             j.part, j.out, j.num_row_blocks, j.n = part, out, nrb, n
         slots = (C.c_int32 * 2)()

@@ -221,7 +221,7 @@ class RolloutStorage(nn.Module):
         MAXJ = _lib.K["PBHC_MAX_GATHER_JOBS"]
         for a in range(0, len(jobs), MAXJ):
             chunk = jobs[a:a + MAXJ]
-            arr = (_lib._S["PbhcGatherJob"] * len(chunk))()
+            arr = (_lib.PbhcGatherJob * len(chunk))()
             for j, (src, dst, w, pitch) in zip(arr, chunk):
                 j.src, j.dst, j.width, j.src_pitch = src, dst, w, pitch
             _lib.check(_lib.lib().pbhc_gather_rows(arr, len(chunk), indices.data_ptr(), indices.numel(), _lib.current_stream()), "pbhc_gather_rows")

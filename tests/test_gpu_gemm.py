@@ -352,7 +352,7 @@ def test_linear_out_bwd_matches_fp64(shape, act, mfma):
     finally:
         lib.pbhc_debug_out_bwd_variant(1)
     assert 1 <= nb.value <= MAXB
-    jobs = (_lib._S["PbhcColsumJob"] * 3)()
+    jobs = (_lib.PbhcColsumJob * 3)()
     dw, db, cs = torch.empty(A, K, device="cuda"), torch.empty(A, device="cuda"), torch.empty(K, device="cuda")
     for j, (part, out, n) in enumerate([(pdw, dw, A * K), (pdb, db, A), (pcs, cs, K)]):
         jobs[j].part, jobs[j].out, jobs[j].num_row_blocks, jobs[j].n = part.data_ptr(), out.data_ptr(), nb.value, n
@@ -418,7 +418,7 @@ def test_colsum_final_job_shapes():
     lib = _lib.lib()
     g = torch.Generator(device="cuda").manual_seed(5)
     specs = [(512, 128, 0), (1024, 23 * 128, 0), (2, 768 * 630, 0), (32, 256 * 512, 0), (4, 512 * 380, 1), (16, 4096 + 4, 0), (64, 4096, 3), (8, 8192, 2), (65, 8192, 0), (7, 5, 0)]
-    jobs = (_lib._S["PbhcColsumJob"] * _lib.K["PBHC_MAX_COLSUM_JOBS"])()
+    jobs = (_lib.PbhcColsumJob * _lib.K["PBHC_MAX_COLSUM_JOBS"])()
     parts, outs = [], []
     for j, (P, n, shift) in enumerate(specs):
         part = torch.randn(P * n + 1, device="cuda", generator=g)[(1 if j == 7 else 0):][:P * n].view(P, n)      # (job 7: an unaligned partial buffer)

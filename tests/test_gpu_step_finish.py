@@ -214,7 +214,7 @@ def test_straddling_job_is_refused_and_launches_nothing():
         base += 4 * f.n[s]
     sq.step = step.data_ptr()
     jl = f._job_list(new)
-    jobs = (L._S["PbhcColsumJob"] * 1)()
+    jobs = (L.PbhcColsumJob * 1)()
     jobs[0].part, jobs[0].out, jobs[0].num_row_blocks, jobs[0].n = jl[0]
     red = f._reduce(new)
     assert lib.pbhc_colsum_final_ppo_reduce_sqnorm(jobs, 1, C.byref(red), C.byref(sq), L.current_stream()) == L.K["PBHC_EINVAL"]

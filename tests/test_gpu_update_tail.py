@@ -35,7 +35,7 @@ def _run_tail(shape, clipped, kl_form, adapt, desired_kl=0.01, lr=(1e-3, 5e-4), 
                                        out["grad_value"].data_ptr(), scratch.data_ptr(), C.byref(npart), L.current_stream()), "pbhc_ppo_loss_partials")
     assert npart.value == min((B + 7) // 8, 512)
     g = torch.Generator().manual_seed(B + 17)
-    jobs = (L._S["PbhcColsumJob"] * L.K["PBHC_MAX_COLSUM_JOBS"])()
+    jobs = (L.PbhcColsumJob * L.K["PBHC_MAX_COLSUM_JOBS"])()
     parts, sums = [], []
     for j, n in zip(jobs, jobs_n):
         part = torch.randn(37, n, generator=g).to(DEV)
@@ -55,7 +55,7 @@ def _run_tail(shape, clipped, kl_form, adapt, desired_kl=0.01, lr=(1e-3, 5e-4), 
     for part, o, n in zip(parts, sums, jobs_n):
         assert _tail_ok(o, n)
         want = _guarded(n)
-        one = (L._S["PbhcColsumJob"] * L.K["PBHC_MAX_COLSUM_JOBS"])()
+        one = (L.PbhcColsumJob * L.K["PBHC_MAX_COLSUM_JOBS"])()
         one[0].part, one[0].out, one[0].num_row_blocks, one[0].n = part.data_ptr(), want.data_ptr(), 37, n
         L.check(lib.pbhc_colsum_final(one, 1, L.current_stream()), "pbhc_colsum_final")
         torch.cuda.synchronize()
