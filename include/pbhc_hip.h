@@ -1151,6 +1151,60 @@ int pbhc_debug_articulated_substeps(const PbhcSkeleton* skel, const PbhcArticula
                                     const float* tau, int n, int steps, float h, int enforce_limits, const float* limits, float* out_q, float* out_v,
                                     float* out_qdd0, void* stream);
 
+/* The floating-base simulator (pbhc_amd/simulator/floating_sim.py FloatingBaseSim; k_floating_sim in csrc/pbhc_floating_sim.hip): the same place in the
+ * step, the same one-frame window, delayed-action peek, torque law, draws, tau0 and limits clamp as pbhc_articulated_sim_step, the same tree, link
+ * inertias and kinematics — but the root is FREE (six more degrees of freedom of the tree; the root link's own mass, centre of mass and inertia count)
+ * and the ground pushes back at contact points fixed to the links.  The clip's root, its contact mask and a contact_force are not read.
+ * State: io->root_states [N,13] (position, quaternion xyzw, WORLD linear velocity v_0 of the root's origin, world angular velocity w_0) and io->dof_state,
+ * both what the previous step left, resets included.  Every sub-step, h = sim_dt:
+ *   1. tau from the current (q, v) by the step's torque law.
+ *   2. contact, explicitly from the state at the start of the sub-step: point k is r_k in the frame of body b_k; z_k its world height,
+ *      xd_k = v_0 + (velocity of b_k's origin relative to the root's) + w_b x R_b r_k its world velocity; delta = ground_height - z_k.
+ *      delta > 0:  f_n = max(0, stiffness delta - normal_damping xd_z),  f_t = -friction f_n xd_t / max(|xd_t|, slip_velocity)  (Coulomb, linear below
+ *      the slip velocity; xd_t the horizontal part);  else f = 0.
+ *   3. H(q) [a_0; alpha_0; q''] = [0; 0; tau - b v] - C(q, v, w_0) + sum_k J_k^T f_k + H [g; 0; 0],  diag(armature + h b) added to the joint block of
+ *      the (6 + D) x (6 + D) inertia matrix H of the free-floating tree; a_0 = d v_0 / dt, alpha_0 = d w_0 / dt.
+ *   4. v_0 += h a_0;  w_0 += h alpha_0;  v += h q'';  p_0 += h v_0;  R_0 <- exp(h w_0) R_0 (world-frame exponential map, renormalised);  q += h v;
+ *      with enforce_limits the clamp of pbhc_joint_sim_step.
+ * Frame: frame_root the integrated root state, frame_dof_pos / frame_dof_vel the integrated joints, frame_contact — for every body that owns contact
+ * points — all three components of the sum of its points' forces at the LAST sub-step (no other element is written: the caller zeroes it once).
+ * points: DEVICE [PBHC_ART_MAX_BODIES][PBHC_FLOAT_MAX_POINTS][3] (body frame, m; the whole table is read), of which body b uses the first
+ * num_points[b].  tau0 (may be NULL): device [N,D], the
+ * first sub-step's torque.  root_acc (may be NULL): device [N,6], the LAST sub-step's a_0 and alpha_0.
+ * NULL pointers (io->root_states, points included), io->num_frames != 1, B > PBHC_ART_MAX_BODIES, decimation outside [1, 64], a negative mass,
+ * armature, damping, stiffness, normal_damping or friction, slip_velocity <= 0, a root mass <= 0, num_points outside [0, PBHC_FLOAT_MAX_POINTS] or
+ * not 0 for a body >= B, control type "V" return PBHC_EINVAL without a launch. */
+#define PBHC_FLOAT_MAX_POINTS 4
+typedef struct PbhcFloatingParams {
+  float mass[PBHC_ART_MAX_BODIES];          /* m_b  kg, the root's included */
+  float com[PBHC_ART_MAX_BODIES][3];        /* c_b  m, body frame */
+  float inertia[PBHC_ART_MAX_BODIES][6];    /* I_b  kg m^2 about the centre of mass, body frame: xx yy zz xy xz yz */
+  float armature[PBHC_MAX_DOF];             /* kg m^2, added to the diagonal of the joint block */
+  float damping[PBHC_MAX_DOF];              /* b_d  N m s / rad, passive, taken implicitly */
+  float gravity[3];                         /* m / s^2, world */
+  float stiffness;                          /* N / m */
+  float normal_damping;                     /* N s / m */
+  float friction;
+  float slip_velocity;                      /* m / s */
+  float ground_height;                      /* m, world z of the plane */
+  int32_t enforce_limits;
+  int32_t decimation;
+  int32_t num_points[PBHC_ART_MAX_BODIES];
+  const float* points;
+  float* tau0;
+  float* root_acc;
+} PbhcFloatingParams;
+int pbhc_sizeof_floating_params(void);
+int pbhc_floating_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcFloatingParams* params, void* stream);
+/* Test-only: `steps` sub-steps of h seconds of the SAME device function as k_floating_sim under a constant torque, n independent robots.
+ * root [n,13] as io->root_states; q, v, tau [n,D]; limits: HOST [D,2], read only with enforce_limits.  out_root [n,13], out_q, out_v [n,D] the final
+ * state; out_acc0 [n,6+D] the FIRST sub-step's [a_0, alpha_0, q'']; out_force [n,B,PBHC_FLOAT_MAX_POINTS,3] the first sub-step's force on every point
+ * (0 for a point a body does not have).  steps outside [1, 4096], h <= 0, NULL pointers and what pbhc_floating_sim_step refuses of the params
+ * return PBHC_EINVAL without a launch. */
+int pbhc_debug_floating_substeps(const PbhcSkeleton* skel, const PbhcFloatingParams* params, const float* root, const float* q, const float* v,
+                                 const float* tau, int n, int steps, float h, int enforce_limits, const float* limits, float* out_root, float* out_q,
+                                 float* out_v, float* out_acc0, float* out_force, void* stream);
+
 /* Retargeting at ingestion (pbhc_amd/motion_retarget.py; csrc/pbhc_retarget.hip; definition: DESIGN §8 "Retargeting"; reference:
  * smpl_retarget/phc_retarget/fit_smpl_motion.py:137-179).  M clips concatenated: `starts` is the HOST array int32 [M + 1] (checked before any
  * launch), `d_starts` its device copy; every other array is a device pointer.  keypoints [total, P, 3] world-frame targets of the bodies

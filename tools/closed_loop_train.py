@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Train MHPPO in the closed loop of JointSpaceSim (pbhc_amd/simulator/joint_sim.py) or ArticulatedSim (pbhc_amd/simulator/articulated_sim.py)
-and print whether the tracking error moves.
+"""Train MHPPO in the closed loop of JointSpaceSim (pbhc_amd/simulator/joint_sim.py), ArticulatedSim (pbhc_amd/simulator/articulated_sim.py)
+or FloatingBaseSim (pbhc_amd/simulator/floating_sim.py) and print whether the tracking error moves.
 
     python tools/closed_loop_train.py --config tests/golden/configs/v1_g1_23dof_walk.yaml --envs 1024 --iters 300 --sim joint
 
@@ -16,6 +16,13 @@ The joint simulator is no physics engine (no gravity, no coupling between joints
 error here shows that the loop action -> torque -> joint state -> observation -> reward is closed and that PPO can use it, nothing more.
 `--sim articulated` runs the robot's tree with the MJCF's masses and inertia tensors under gravity and the gantry's accelerations (armature and
 damping from the same flags; --inertia is not used): still no free root, no contact dynamics, no balance.
+`--sim floating` frees the root and lets the ground push back at the four corners of each sole of the G1 (the corners of the footprint of the
+foot's collision capsules, friction 0.8): the robot can fall, and the loop prints per iteration, after the columns above,
+    ended_by     the share of the episodes that ended in the rollout's last step by gravity / motion-far / time-out / motion-end (the step
+                 kernel's batch means of its termination flags, normalised to their sum; "-" when no episode ended in that step)
+The contact defaults (stiffness 10000 N/m and normal damping 100 N s/m per point, slip velocity 0.4 m/s) pass the stability screen at the
+config's 200 Hz with a static sink of 0.39 cm; `--sim-fps F` raises sim.fps to F and the decimation with it (F must be a multiple
+of the config's fps), which a stiffer ground or a smaller slip velocity needs, and says so.
 """
 import argparse
 import os
@@ -45,6 +52,23 @@ def build(args):
         ov["simulator.config.articulated_sim"] = {"armature": args.armature, "damping": args.damping}
         if args.mjcf:                                         # the masses and inertia tensors: the skeleton from the MJCF
             ov["robot.motion.asset.assetFileName"] = args.mjcf
+    elif args.sim == "floating":
+        ov["simulator._target_"] = "pbhc_amd.simulator.floating_sim.FloatingBaseSim"
+        ov["simulator.config.floating_sim"] = {"armature": args.armature, "damping": args.damping, "stiffness": args.stiffness,
+                                               "normal_damping": args.normal_damping, "friction": args.friction, "slip_velocity": args.slip_velocity,
+                                               "contact_points": {"left_ankle_roll_link": G1_SOLE, "right_ankle_roll_link": G1_SOLE}}
+        ov["domain_rand.push_robots"] = False                 # (it would do nothing: the simulator has no push)
+        if args.mjcf:
+            ov["robot.motion.asset.assetFileName"] = args.mjcf
+        if args.sim_fps:
+            base = load_config(args.config, {}, now="closed_loop").simulator.config.sim
+            if args.sim_fps % int(base.fps) != 0:
+                raise SystemExit(f"--sim-fps {args.sim_fps}: not a multiple of the config's sim.fps {base.fps}")
+            ratio = args.sim_fps // int(base.fps)
+            ov["simulator.config.sim.fps"] = args.sim_fps
+            ov["simulator.config.sim.control_decimation"] = int(base.control_decimation) * ratio
+            print(f"# sim.fps {base.fps} -> {args.sim_fps}, control_decimation {base.control_decimation} -> {int(base.control_decimation) * ratio} "
+                  "(the control step stays what it was)")
     else:
         ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
     cfg = load_config(args.config, ov, now="closed_loop")
@@ -55,6 +79,17 @@ def build(args):
     return cfg, env, algo
 
 
+# the corners of the footprint of the G1's foot collision capsules (x from -0.054 to 0.132, y +-0.026, 0.025 + the 0.01 radius below the
+# ankle-roll link's origin), in that link's frame
+G1_SOLE = [[0.132, 0.026, -0.035], [0.132, -0.026, -0.035], [-0.054, 0.026, -0.035], [-0.054, -0.026, -0.035]]
+
+
+def ended_by(log):
+    parts = [float(log[k]) for k in ("terminate_by_gravity", "terminate_by_motion_far", "terminate_by_time_out", "terminate_by_motion_end")]
+    total = sum(parts)
+    return "-" if total <= 0 else "/".join(f"{p / total:.2f}" for p in parts)
+
+
 def tracking_figures(env):
     log = env.read_log()
     keep = env.reset_buf == 0
@@ -62,7 +97,7 @@ def tracking_figures(env):
     err = ((qref - env.simulator.dof_pos) ** 2).mean(dim=1)
     r = torch.exp(-err / float(log["adp_sigma_teleop_joint_pos"]))
     r = float(r[keep].mean()) if bool(keep.any()) else float("nan")
-    return float(log["joint_pos_diff_norm"]), r, float(log["average_episode_length"])
+    return float(log["joint_pos_diff_norm"]), r, float(log["average_episode_length"]), ended_by(log)
 
 
 def main():
@@ -70,11 +105,16 @@ def main():
     ap.add_argument("--config", default=os.path.join(ROOT, "tests", "golden", "configs", "v1_g1_23dof_walk.yaml"))
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=300)
-    ap.add_argument("--sim", choices=("joint", "articulated", "replay"), default="joint")
+    ap.add_argument("--sim", choices=("joint", "articulated", "floating", "replay"), default="joint")
     ap.add_argument("--inertia", default="subtree", help='"subtree" or one number (kg m^2) for every joint')
     ap.add_argument("--armature", type=float, default=0.02)
     ap.add_argument("--damping", type=float, default=0.05)
     ap.add_argument("--mjcf", default="mjcf/g1_23dof_lock_wrist_fitmotionONLY.xml", help="robot.motion.asset.assetFileName for --sim joint ('' keeps the config's)")
+    ap.add_argument("--stiffness", type=float, default=10000.0, help="--sim floating: N/m per contact point")
+    ap.add_argument("--normal-damping", type=float, default=100.0, help="--sim floating: N s/m per contact point")
+    ap.add_argument("--friction", type=float, default=0.8)
+    ap.add_argument("--slip-velocity", type=float, default=0.4, help="--sim floating: m/s below which the friction is linear")
+    ap.add_argument("--sim-fps", type=int, default=0, help="--sim floating: raise sim.fps to this multiple of the config's, and the decimation with it")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--print-every", type=int, default=1)
@@ -90,7 +130,7 @@ def main():
     elif args.sim == "joint":
         print("# inertia (kg m^2): " + " ".join(f"{v:.4f}" for v in env.simulator.inertia))
     print(f"# sim {args.sim}, {args.envs} envs, {algo.num_steps_per_env} steps per rollout, {args.iters} iterations")
-    print("# iter joint_diff r_joint_pos avg_ep_len rollout_ms graph")
+    print("# iter joint_diff r_joint_pos avg_ep_len rollout_ms graph" + (" ended_by(gravity/motion_far/time_out/motion_end)" if args.sim == "floating" else ""))
     times, first, last = [], None, None
     for it in range(args.iters):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -101,13 +141,14 @@ def main():
         algo._training_step()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)
-        jd, rj, epl = tracking_figures(env)
+        jd, rj, epl, ended = tracking_figures(env)
         if it >= 2:
             times.append(ms)
         first = (jd, rj) if first is None else first
         last = (jd, rj)
         if it % args.print_every == 0 or it == args.iters - 1:
-            print(f"{it:5d} {jd:.5f} {rj:.5f} {epl:8.2f} {ms:8.3f} {int(bool(getattr(algo, '_rollout_used_graph', False)))}", flush=True)
+            print(f"{it:5d} {jd:.5f} {rj:.5f} {epl:8.2f} {ms:8.3f} {int(bool(getattr(algo, '_rollout_used_graph', False)))}"
+                  + (f" {ended}" if args.sim == "floating" else ""), flush=True)
     if times:
         print(f"# rollout_ms median {statistics.median(times):.3f} min {min(times):.3f} max {max(times):.3f} over {len(times)} iterations")
     print(f"# joint_diff {first[0]:.5f} -> {last[0]:.5f}   r_joint_pos {first[1]:.5f} -> {last[1]:.5f}")
