@@ -377,6 +377,26 @@ typedef struct PbhcMotionTable {
 } PbhcMotionTable;
 
 /* ---- per-step tensors of the fused env step ------------------------------------------------ */
+/* Extent, alignment and pitch of the caller-owned buffers (N = PbhcEnvConfig.num_envs, D dofs, B bodies, Bx bodies with the extended ones,
+ * Q = queue_len, F = num_feet, T = num_frames), from the loads and stores the kernels issue (k_env_step generic and specialised,
+ * k_dof_far_any, k_env_finalize; held by tests/test_gpu_step_memory.py, table in DESIGN.md "Memory contract of the per-step entries"):
+ *   extent     exactly the shape given at the field, dense (row pitch = row length) except `obs[g]` and `hist`.  Nothing is read or written
+ *              outside it: the last workgroup of a batch that is no multiple of the 4 envs of a workgroup clamps its loads onto env N - 1
+ *              and stores nothing for the missing envs; a frame is read at index `frame_index` (or *frame_cursor) of [0, T) only.
+ *   alignment  float, int32 and uint8 buffers: the element's own (4, 4, 1 bytes) — a base 4, 8 or 12 bytes behind a 16-byte boundary is
+ *              fine.  int64 buffers (episode_length_buf, last_episode_length_buf, reset_buf, action_delay_idx, motion_ids, ovr_delay):
+ *              8 bytes, else PBHC_EINVAL.  `hist` under a specialised kernel that reads history rows 16 bytes per lane: 16 bytes, else
+ *              PBHC_EINVAL.  totals_out (and the `totals` of pbhc_env_finalize), doubles: 8 bytes, else PBHC_EINVAL.
+ *   pitch      obs[g]: obs_pitch[g] floats between rows, 0 = dense, at least PbhcEnvConfig.groups[g].pitch (= the group's dimension),
+ *              N x pitch < 2^30; columns [0, dim) of a row are written.  The generic kernel stores elements in PAIRS when the pitch is even
+ *              and the base 8-byte aligned: with an odd dim and pitch > dim the float in column `dim` is written too (the only padding
+ *              float any entry touches; callers that pad rows own their padding).  Any other pitch / base: element by element.
+ *              hist (and obs[num_groups - 1], its write-back): hist_pitch floats, 0 = dense, >= hist_dim; under such a specialised
+ *              kernel a multiple of 4 and >= hist_dim rounded up to 4 — the last 16-byte read of a row may take in up to 3 floats of its
+ *              padding, whose values reach no result.
+ *   NULL       where the field says "may be NULL"; the ovr_* draws and u_rfi: NULL -> in-kernel Philox.
+ * Index-typed inputs are trusted, not clamped: motion_ids in [0, num_motions), action_delay_idx / ovr_delay in [0, Q), *frame_cursor and
+ * frame_index < T. */
 typedef struct PbhcStepIO {
   /* inputs */
   const float* actions_in;        /* [N,D]   policy actions                                    */
@@ -453,6 +473,10 @@ typedef struct PbhcStepIO {
 /* The evaluation recorder (env.config.save_motion, motion_tracking.py:140-170,861-938): device-resident [N,T,...] buffers, T = total_steps =
  * save_total_steps, one frame per env and control step, each env's frames contiguous.  Not part of PbhcEnvConfig: the step kernel and its
  * specialised builds do not know the recorder exists. */
+/* Contract: every buffer dense with exactly the extent given at the field, float / int32 buffers 4-byte aligned, `terminate` (int64) and the
+ * PbhcStepIO int64 buffers it reads 8-byte aligned (else PBHC_EINVAL); actor_obs is read through PbhcStepIO.obs_pitch[obs_group] and
+ * written dense.  A launch whose counter word 0 is < 3 or >= T + 3 stores nothing into the [N,T,...] buffers; of the counter only word 0
+ * and the ticket words named below are ever written, and the ticket words are 0 again when the launch ends. */
 #define PBHC_REC_SHARDS 128
 #define PBHC_REC_COUNTER_WORDS 4160   /* 32 * (2 + PBHC_REC_SHARDS) */
 typedef struct PbhcRecordIO {
@@ -576,12 +600,19 @@ int pbhc_motion_screen_clips(const float* foot_pos, const float* dist, int total
 
 /* Phase lookup + lerp/slerp.  Replaces MotionLibBase.get_motion_state (motion_lib_base.py:123-259).
  * ids [N] int64, times [N], offset [N,3] or NULL -> out [N,row] packed like a frame row
- * (positions include the offset). */
+ * (positions include the offset).
+ * Contract: all dense; float buffers 4-byte aligned, ids 8-byte aligned (else PBHC_EINVAL); ids in [0, tbl->num_motions) (trusted).  Of the
+ * table only rows length_starts[id] .. length_starts[id] + num_frames[id] - 1 are read: a time at or beyond the clip's length reads its LAST
+ * row twice, never the row behind it (the next clip's first row, or the end of `frames`); a negative time reads rows 0 and 1 with
+ * blend 0. */
 int pbhc_motion_state(const PbhcMotionTable* tbl, int num_bodies_ext, int num_dof, const int64_t* ids, const float* times,
                       const float* offset, int n, float* out, void* stream);
 
 /* Rigid-body pose + twist from (root state, q, q-dot): what Isaac Gym's rigid-body state tensor
- * supplied in the reference (isaacgym.py:574-605).  out [N,B,13]. */
+ * supplied in the reference (isaacgym.py:574-605).  out [N,B,13].
+ * Contract: root_states [N,13] and out [N,B,13] dense; dof_pos / dof_vel: element (env, d) at float index (env * D + d) * dof_stride, i.e.
+ * [N,D] dense with dof_stride 1, or the two columns of one [N,D,2] dof_state (dof_vel = dof_pos + 1) with dof_stride 2 — the last float
+ * read is index (N * D - 1) * dof_stride.  4-byte alignment throughout. */
 int pbhc_sim_fk(const PbhcSkeleton* skel, const float* root_states, const float* dof_pos, const float* dof_vel,
                 int dof_stride, int n, float* out_body_state, void* stream);
 /* Test-only: the same chain for every body INCLUDING the extended ones (motion_tracking.py:619-643), out [N,Bx,13], by method 0 — the walk
@@ -1111,6 +1142,15 @@ typedef struct PbhcJointSimParams {
   float* tau0;
 } PbhcJointSimParams;
 int pbhc_sizeof_joint_sim_params(void);
+/* Memory contract of the three simulator step entries (pbhc_joint_sim_step, pbhc_articulated_sim_step, pbhc_floating_sim_step; 8 envs per
+ * workgroup, loads of a ragged last workgroup clamped onto env N - 1, nothing stored for the missing envs).  Read, with the extents and
+ * alignments of PbhcStepIO: actions_in, dof_state, action_queue, action_delay_idx, kp_scale, kd_scale, rfi_lim_scale, rao_scale,
+ * episode_length_buf, motion_start_times, motion_ids, env_origins, u_rfi / ovr_ps_tau / default_dof_pos when non-NULL (the floating
+ * simulator also root_states), and the motion table's rows of the env's clip.  Written: the ONE frame of the window — frame_root [1,N,13],
+ * frame_dof_pos / frame_dof_vel [1,N,D] whole, of frame_contact [1,N,B,3] only z of the foot bodies (floating: all three components of the
+ * bodies that own contact points) — and, when non-NULL, tau0 [N,D] and base_acc / root_acc [N,6].  PbhcFloatingParams.points:
+ * [PBHC_ART_MAX_BODIES, PBHC_FLOAT_MAX_POINTS, 3] floats, read only.  Everything dense, float buffers 4-byte aligned, the int64 buffers
+ * 8-byte aligned (else PBHC_EINVAL). */
 int pbhc_joint_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcJointSimParams* params, void* stream);
 
 /* The articulated rigid-body simulator (pbhc_amd/simulator/articulated_sim.py ArticulatedSim; k_articulated_sim in csrc/pbhc_articulated_sim.hip): the

@@ -167,6 +167,7 @@ static int cl_check_step(PbhcEnv* e, const PbhcStepIO* io, int decimation, const
   CL_CHECK(io->actions_in && io->frame_root && io->frame_dof_pos && io->frame_dof_vel && io->frame_contact && io->num_frames == 1);
   CL_CHECK(io->dof_state && io->action_queue && io->action_delay_idx && io->kp_scale && io->kd_scale && io->rfi_lim_scale && io->rao_scale);
   CL_CHECK(io->episode_length_buf && io->motion_start_times && io->motion_ids && io->env_origins);
+  CL_CHECK(((((uintptr_t)io->episode_length_buf | (uintptr_t)io->motion_ids | (uintptr_t)io->action_delay_idx) & 7) == 0));     // int64 elements
   CL_CHECK(decimation >= 1 && decimation <= CL_MAX_DECIMATION);
   CL_CHECK((*hc)->control_type == 0 || (*hc)->control_type == 2);      // "V" needs last_dof_vel per sub-step: refused
   const int D = (*hc)->skel.num_dof, B = (*hc)->skel.num_bodies, N = (*hc)->num_envs, NF = (*hc)->num_feet;

@@ -573,6 +573,7 @@ int pbhc_motion_build_batch(const PbhcSkeleton* skel, const float* pose_aa, cons
 int pbhc_motion_state(const PbhcMotionTable* tbl, int Bx, int D, const int64_t* ids, const float* times, const float* offset, int n,
                       float* out, void* stream) {
   ARG_CHECK(tbl && tbl->frames && ids && times && out && n >= 0);
+  ARG_CHECK(((uintptr_t)ids & 7) == 0);                                   // int64 elements; every float buffer: 4-byte alignment
   ARG_CHECK(Bx >= 1 && Bx <= PBHC_MAX_BODIES && D >= 1 && D <= PBHC_MAX_DOF && tbl->row == 2 * D + 2 + 13 * Bx);
   if (n == 0) return PBHC_OK;
   hipLaunchKernelGGL(k_motion_state, dim3((n + PBHC_EPB - 1) / PBHC_EPB), dim3(PBHC_G * PBHC_EPB), 0, (hipStream_t)stream, *tbl, Bx, D, ids, times, offset, n, out);
@@ -909,6 +910,15 @@ static int env_step_check(PbhcEnv* e, const PbhcStepIO* io) {
   }
   ARG_CHECK(io->hist_pitch == 0 || io->hist_pitch >= e->cfg.hist_dim);
   ARG_CHECK(!e->cfg.noise_process || io->ou_state);
+  // the 64-bit counters and indices are read and written as one 8-byte element (every other buffer of the step needs 4-byte alignment only;
+  // the history rows of a specialised kernel: pbhc_env_step_launch)
+  if ((((uintptr_t)io->episode_length_buf | (uintptr_t)io->last_episode_length_buf | (uintptr_t)io->reset_buf | (uintptr_t)io->action_delay_idx |
+        (uintptr_t)io->motion_ids | (uintptr_t)io->ovr_delay) & 7) != 0) {
+    snprintf(g_err, sizeof(g_err), "pbhc_env_step: the int64 buffers (episode_length_buf, last_episode_length_buf, reset_buf, action_delay_idx, motion_ids, "
+                                   "ovr_delay) must be 8-byte aligned");
+    return PBHC_EINVAL;
+  }
+  ARG_CHECK(((uintptr_t)io->totals_out & 7) == 0);                        // doubles (written by the step's second half)
   return PBHC_OK;
 }
 
@@ -961,6 +971,7 @@ int pbhc_env_step_launch(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
 // after the fused launch and before the next one (the rollout runs it next to the policy forward, off the step -> policy -> step chain).
 int pbhc_env_step_finish(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
   ARG_CHECK(e && io && io->frame_cursor && io->num_frames >= 1);
+  ARG_CHECK(((uintptr_t)io->totals_out & 7) == 0);                        // doubles
   hipLaunchKernelGGL(k_env_finalize, dim3(1), dim3(64 * PBHC_FIN_CHUNKS), 0, (hipStream_t)stream, e->d_cfg, e->d_glob, e->d_partials, 2 * e->nblocks, io->frame_cursor,
                      io->num_frames, (const double*)nullptr, io->totals_out, 0.0);
   HIP_CHECK(hipGetLastError());
@@ -996,6 +1007,7 @@ int pbhc_record_motion(PbhcEnv* e, const PbhcStepIO* io, const PbhcRecordIO* rec
   ARG_CHECK(rec->pose_aa && rec->action && rec->actor_obs && rec->terminate && rec->motion_times);
   ARG_CHECK(io->root_states && io->dof_state && io->actions && io->contacts_filt && io->env_origins && io->motion_start_times);
   ARG_CHECK(io->episode_length_buf && io->reset_buf && io->obs[rec->obs_group]);
+  ARG_CHECK(((((uintptr_t)rec->terminate | (uintptr_t)io->episode_length_buf | (uintptr_t)io->reset_buf) & 7) == 0));    // int64 elements
   const int g = rec->obs_group, N = e->cfg.num_envs;
   RecSrc s;
   s.root = io->root_states; s.dof_state = io->dof_state; s.actions = io->actions; s.contacts_filt = io->contacts_filt;
@@ -1019,6 +1031,7 @@ int pbhc_env_step(PbhcEnv* e, const PbhcStepIO* io, void* stream) {
 
 int pbhc_env_finalize(PbhcEnv* e, const double* totals, double num_envs_total, void* stream) {
   ARG_CHECK(e && totals && num_envs_total >= 1.0);
+  ARG_CHECK(((uintptr_t)totals & 7) == 0);                                // doubles
   hipLaunchKernelGGL(k_env_finalize, dim3(1), dim3(64 * PBHC_FIN_CHUNKS), 0, (hipStream_t)stream, e->d_cfg, e->d_glob, (const float*)nullptr, 0, (int32_t*)nullptr, 1,
                      totals, (double*)nullptr, num_envs_total);
   HIP_CHECK(hipGetLastError());

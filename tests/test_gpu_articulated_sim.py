@@ -85,12 +85,14 @@ def _np(t):
 
 
 # ---- the test-only export ------------------------------------------------------------------------------------------------------------------
-def _debug(sk, p, base13, q, v, tau, steps, h=H, limits=None):
-    """pbhc_debug_articulated_substeps on float32 copies of the inputs -> (q, v, qdd0) float64 numpy"""
-    t = lambda a: torch.as_tensor(np.asarray(a, np.float32)).to(DEV).contiguous()
-    tb, tq, tv, tt = t(base13), t(q), t(v), t(tau)
+def _debug(sk, p, base13, q, v, tau, steps, h=H, limits=None, place=None):
+    """pbhc_debug_articulated_substeps on float32 copies of the inputs -> (q, v, qdd0) float64 numpy.  place(name, tensor) -> tensor: where
+    every device operand goes (tests/test_gpu_step_memory.py: into arenas)"""
+    place = place or (lambda name, x: x)
+    t = lambda name, a: place(name, torch.as_tensor(np.asarray(a, np.float32)).to(DEV).contiguous())
+    tb, tq, tv, tt = t("base", base13), t("q", q), t("v", v), t("tau", tau)
     n = tq.shape[0]
-    oq, ov, oa = torch.zeros_like(tq), torch.zeros_like(tq), torch.zeros_like(tq)
+    oq, ov, oa = (place(name, torch.zeros_like(tq)) for name in ("out_q", "out_v", "out_qdd0"))
     lim = None if limits is None else np.ascontiguousarray(limits, np.float32)
     csk = sk.to_c()
     _lib.check(_lib.lib().pbhc_debug_articulated_substeps(C.byref(csk), C.byref(p), tb.data_ptr(), tq.data_ptr(), tv.data_ptr(), tt.data_ptr(), n, steps, h,

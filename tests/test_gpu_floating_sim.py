@@ -58,14 +58,16 @@ def _setup(mjcf, arm=ARM, damp=DAMP, law=LAW, gravity=(0.0, 0.0, -9.81), points=
     return sk, m, p, table                                   # `table`: the device point table p.points names — the caller keeps it alive
 
 
-def _debug(sk, p, root, q, v, tau, steps, h=H, limits=None):
-    """pbhc_debug_floating_substeps on float32 copies of the inputs -> dict of float64 numpy arrays"""
-    t = lambda a: torch.as_tensor(np.asarray(a, np.float32)).to(DEV).contiguous()
-    tr, tq, tv, tt = t(root), t(q), t(v), t(tau)
+def _debug(sk, p, root, q, v, tau, steps, h=H, limits=None, place=None):
+    """pbhc_debug_floating_substeps on float32 copies of the inputs -> dict of float64 numpy arrays.  place(name, tensor) -> tensor: where
+    every device operand goes (tests/test_gpu_step_memory.py: into arenas)"""
+    place = place or (lambda name, x: x)
+    t = lambda name, a: place(name, torch.as_tensor(np.asarray(a, np.float32)).to(DEV).contiguous())
+    tr, tq, tv, tt = t("root", root), t("q", q), t("v", v), t("tau", tau)
     n, D = tq.shape
     B = sk.num_bodies
-    o_root, o_q, o_v = torch.zeros_like(tr), torch.zeros_like(tq), torch.zeros_like(tq)
-    o_acc, o_f = torch.zeros(n, 6 + D, device=DEV), torch.zeros(n, B, 4, 3, device=DEV)
+    o_root, o_q, o_v = place("out_root", torch.zeros_like(tr)), place("out_q", torch.zeros_like(tq)), place("out_v", torch.zeros_like(tq))
+    o_acc, o_f = place("out_acc0", torch.zeros(n, 6 + D, device=DEV)), place("out_force", torch.zeros(n, B, 4, 3, device=DEV))
     lim = None if limits is None else np.ascontiguousarray(limits, np.float32)
     csk = sk.to_c()
     _lib.check(_lib.lib().pbhc_debug_floating_substeps(C.byref(csk), C.byref(p), tr.data_ptr(), tq.data_ptr(), tv.data_ptr(), tt.data_ptr(), n, steps, h,
@@ -295,13 +297,16 @@ def _model_step(m, root, q, v, a_del, P):
     return fm.carried_bound(m, fm.state(root, q, v), torque, P["h"], P["decimation"], GAMMA, EPS, lo=P["lo"], hi=P["hi"], tau_abs_fn=tabs, tile_fn=tile_fn)
 
 
-def _run_case(cfgname, N, general, steps=None, zero_actions=False):
+def _run_case(cfgname, N, general, steps=None, zero_actions=False, prepare=None, after_step=None):
+    """prepare(env) / after_step(env, k): the hooks of tests/test_gpu_parity.py's _env_step_vs_oracle"""
     cfg, env = _build(cfgname, N, general)
     D = env.num_dof
     sc = scenario(N, D, float(env._c.action_clip_value))
     _prepare(env, sc)
     s = env.simulator
     s.set_debug_torques(True)
+    if prepare is not None:
+        prepare(env)
     m = _env_model(env)
     out = []
     for k in range(sc["steps"] if steps is None else steps):
@@ -313,6 +318,8 @@ def _run_case(cfgname, N, general, steps=None, zero_actions=False):
         a_del = jm.delayed_action(actions, float(env._c.action_clip_value), pre["queue"], pre["delay"], bool(env._c.randomize_ctrl_delay))
         env.step({"actions": torch.from_numpy(actions).to(env.device)})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         out.append(dict(P=P, pre=pre, a_del=a_del, reset=env.reset_buf.bool().cpu().numpy(), frame_q=_np(s.replay["dof_pos"][0]),
                         frame_v=_np(s.replay["dof_vel"][0]), frame_root=_np(s.replay["root"][0]), frame_contact=s.replay["contact"][0].clone(),
                         root=_np(s.robot_root_states), dof_pos=_np(s.dof_pos), tau0=s.tau0.clone(), torques=env.torques.clone()))

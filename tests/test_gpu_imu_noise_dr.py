@@ -48,7 +48,8 @@ def _slices(cfg, group):
     return out
 
 
-def _trace(tag, cfgname, overrides, general):
+def _trace(tag, cfgname, overrides, general, prepare=None, after_step=None):
+    """prepare(env) / after_step(env, k): the hooks of tests/test_gpu_parity.py's _env_step_vs_oracle"""
     g = dict(np.load(f"{GOLDEN}/{tag}.npz"))
     T, N, D = g["actions_in"].shape
     cfg, env = build_hip_env(cfgname, N, general=general, overrides=dict({"domain_rand.push_robots": False}, **overrides))
@@ -57,6 +58,8 @@ def _trace(tag, cfgname, overrides, general):
     tg = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(env.device)
     env.noise_process_state.copy_(tg(g["state0__ou_state"]))
     env.simulator.set_replay(tg(g["replay_root"]), tg(g["replay_dof_pos"]), tg(g["replay_dof_vel"]), tg(g["replay_contact"]))
+    if prepare is not None:
+        prepare(env)
     c = env._c
     for k in range(T):
         st = lambda name, dt=torch.float32: tg(g["step__state__" + name][k]).to(dt)
@@ -67,6 +70,8 @@ def _trace(tag, cfgname, overrides, general):
                                ps_rao=dr("ps_rao") if c.ps_tau else None, ps_tau=dr("ps_tau") if c.ps_tau else None)
         obs, rew, reset, extras = env.step({"actions": tg(g["actions_in"][k])})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         w = f"{tag} step {k}: "
         assert torch.equal(reset.cpu(), torch.from_numpy(g["step__reset_buf_out"][k])), w + "reset_buf"
         close(rew, g["step__rew_buf"][k], 3e-5, w + "rew_buf", rtol=2e-4)

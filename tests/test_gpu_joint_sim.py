@@ -96,8 +96,9 @@ def _prepare(env, sc):
     torch.cuda.synchronize()
 
 
-def _run_case(cfgname, N, general, inject):
-    """six steps; per step the kernel's frame, tau0 and the step's torques, next to the model's prediction from the kernel's OWN pre-step state"""
+def _run_case(cfgname, N, general, inject, prepare=None, after_step=None):
+    """prepare(env) / after_step(env, k): the hooks of tests/test_gpu_parity.py's _env_step_vs_oracle.
+    six steps; per step the kernel's frame, tau0 and the step's torques, next to the model's prediction from the kernel's OWN pre-step state"""
     cfg, env = _build(cfgname, N, general)
     D = env.num_dof
     sc = scenario(N, D, float(env._c.action_clip_value))
@@ -105,6 +106,8 @@ def _run_case(cfgname, N, general, inject):
     _prepare(env, sc)
     s = env.simulator
     s.set_debug_torques(True)
+    if prepare is not None:
+        prepare(env)
     out = []
     for k in range(sc["steps"]):
         u = torch.from_numpy(sc["u_rfi"][k]).to(env.device) if inject else None
@@ -117,6 +120,8 @@ def _run_case(cfgname, N, general, inject):
         terms = model.torque_terms(pre["q"], pre["v"], a_del, P)
         env.step({"actions": torch.from_numpy(sc["actions"][k]).to(env.device)})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         out.append(dict(P=P, pre=pre, model=m, terms=terms, a_del=a_del, reset=env.reset_buf.bool().cpu().numpy(), time_outs=int(env.time_out_buf.sum()),
                         frame_q=_np(s.replay["dof_pos"][0]), frame_v=_np(s.replay["dof_vel"][0]), frame_root=s.replay["root"][0].clone(),
                         frame_contact=s.replay["contact"][0].clone(), dof_pos=_np(s.dof_pos), dof_vel=_np(s.dof_vel), root=s.robot_root_states.clone(),

@@ -101,17 +101,23 @@ def _probe(line):
             f.write(line + "\n")
 
 
-def close(a, b, tol, what, rtol=None, hard=None, frac=0.0, tol_override=None):
+def close_limit(b, tol, what="", rtol=None, tol_override=None):
+    """-> (tol, the elementwise limit |a - b| is held to by `close`): tol + rtol |b|, rtol = tol for a scalar tol and 0 for an elementwise one
+    unless given"""
     tol = tol if tol_override is None else tol_override
-    a = torch.as_tensor(a).detach().float().cpu()
-    b = torch.as_tensor(b).detach().float().cpu()
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    err = (a - b).abs()
     if torch.is_tensor(tol):                                  # elementwise absolute bound (conditioned tolerances)
         tol = tol.detach().float().cpu()
         assert tol.shape == b.shape, (what, tol.shape, b.shape)
         rtol = 0.0 if rtol is None else rtol
-    lim = tol + (tol if rtol is None else rtol) * b.abs()
+    return tol, tol + (tol if rtol is None else rtol) * b.abs()
+
+
+def close(a, b, tol, what, rtol=None, hard=None, frac=0.0, tol_override=None):
+    a = torch.as_tensor(a).detach().float().cpu()
+    b = torch.as_tensor(b).detach().float().cpu()
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    err = (a - b).abs()
+    tol, lim = close_limit(b, tol, what, rtol, tol_override)
     bad = err > lim
     if hard is not None:
         assert float(err.max()) <= hard, (what, "hard bound", float(err.max()))
@@ -370,8 +376,9 @@ def test_env_step_matches_oracle_4096_walk_config():
 
 
 def test_env_step_matches_oracle_ragged_tail():
-    """13 envs: the last workgroup is only partly filled (loads of its missing envs are clamped onto env N-1, nothing is stored for them),
-    and the env-count-dependent reductions (log means, curricula) divide by 13."""
+    """13 envs: the last workgroup is only partly filled (loads of its missing envs are clamped onto env N-1, nothing is stored for them:
+    asserted in tests/test_gpu_step_memory.py, where every operand has poison behind its last env), and the env-count-dependent reductions
+    (log means, curricula) divide by 13."""
     _env_step_vs_oracle(13, 4)
 
 
@@ -505,7 +512,9 @@ def sigma_and_ema_match_oracle(env, orc, w):
 
 
 def _env_step_vs_oracle(N, T, tag="horse", cfgname="v1_g1_23dof_horse_stance.yaml", overrides=None, contact_hits=False, noise_curriculum=False, default_bias=False, gates=None,
-                        redraw_steps=(), soft_limits=False):
+                        redraw_steps=(), soft_limits=False, prepare=None, after_step=None):
+    """prepare(env): called once the env is built, loaded and holds its replay window; after_step(env, k): called after step k has
+    run, ahead of its comparisons (tests/test_gpu_step_memory.py re-homes the env into arenas and checks them there)"""
     from oracle.env_v1 import MotionTrackingOracle
     from oracle.fk import sim_fk
     from oracle.motion_lib import MotionLib as OML
@@ -549,6 +558,8 @@ def _env_step_vs_oracle(N, T, tag="horse", cfgname="v1_g1_23dof_horse_stance.yam
     load_state_into_hip_env(env, flat)
     tg = lambda a: a.contiguous().to(DEV)
     env.simulator.set_replay(tg(root[1:]), tg(qp[1:]), tg(qv[1:]), tg(cf[1:]))
+    if prepare is not None:
+        prepare(env)
     kept = []
     for k in range(T):
         act = 0.5 * torch.randn(N, 23, generator=gen)
@@ -571,6 +582,8 @@ def _env_step_vs_oracle(N, T, tag="horse", cfgname="v1_g1_23dof_horse_stance.yam
                                gate_u=torch.tensor(gates[k], dtype=torch.float32, device=DEV) if gates else None)
         obs, rew, reset, extras = env.step({"actions": tg(act)})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         w = f"step {k}: "
         assert torch.equal(reset.cpu(), o_reset), w + f"reset mismatch {int((reset.cpu() != o_reset).sum())}"
         assert int(o_reset.sum()) > 0 or k > 0

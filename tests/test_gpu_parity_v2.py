@@ -336,7 +336,8 @@ def _attribute_obs_errors(path, step, cfg, env, obs, o_obs, orc, tols=None):
                             f"{float(orc.env_origins[i].norm()):.1f} m)  >1e-4: {int((e > 1e-4).sum())}  >1e-5: {int((e > 1e-5).sum())} of {e.numel()}{ratio}\n")
 
 
-def _multi_clip_vs_oracle(N, T, M, library_seed=3):
+def _multi_clip_vs_oracle(N, T, M, library_seed=3, prepare=None, after_step=None):
+    """prepare(env) / after_step(env, k): the hooks of tests/test_gpu_parity.py's _env_step_vs_oracle"""
     import bench
     from oracle.env_v2 import GeneralTrackingOracle
     from oracle.fk import sim_fk
@@ -388,6 +389,8 @@ def _multi_clip_vs_oracle(N, T, M, library_seed=3):
     load_state_into_hip_env(env, flat)
     tg = lambda a: a.contiguous().to(DEV)
     env.simulator.set_replay(tg(root[1:]), tg(qp[1:]), tg(qv[1:]), tg(cf[1:]))
+    if prepare is not None:
+        prepare(env)
     nreset = 0
     for k in range(T):
         act = 0.5 * torch.randn(N, D, generator=gen)
@@ -402,6 +405,8 @@ def _multi_clip_vs_oracle(N, T, M, library_seed=3):
                                rfi_lim=tg(samp["rfi_lim_scale"]), rao=tg(samp["rao_scale"]), delay=tg(samp["action_delay_idx"]))
         obs, rew, reset, extras = env.step({"actions": tg(act)})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         w = f"step {k}: "
         assert torch.equal(reset.cpu(), o_reset), w + f"reset mismatch {int((reset.cpu() != o_reset).sum())}"
         nreset += int(o_reset.sum())
@@ -415,7 +420,7 @@ def _multi_clip_vs_oracle(N, T, M, library_seed=3):
         for name, view in env.history.items():
             close(view, orc.hist[name], 3e-5, w + "hist " + name)
         sigma_and_ema_match_oracle(env, orc, w)
-    assert nreset >= 48
+    assert nreset >= min(48, N)                          # (the envs set onto their clips' ends: all of them below 48 envs)
 
 
 def test_general_tracking_config5_shard_with_noise_and_dr_matches_oracle():

@@ -23,7 +23,8 @@ def _K():
     return _lib.K
 
 
-def _trace(tag, cfgname, overrides, general):
+def _trace(tag, cfgname, overrides, general, prepare=None, after_step=None):
+    """prepare(env) / after_step(env, k): the hooks of tests/test_gpu_parity.py's _env_step_vs_oracle"""
     g = dict(np.load(f"{GOLDEN}/{tag}.npz"))
     T, N, D = g["actions_in"].shape
     cfg, env = build_hip_env(cfgname, N, general=general, overrides=dict({"domain_rand.push_robots": False}, **overrides))
@@ -33,6 +34,8 @@ def _trace(tag, cfgname, overrides, general):
         env.globals[_K()["PBHC_G_DOF_FAR_THR"]] = float(g["step__log__terminate_when_dof_far_threshold"][0])
     tg = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(env.device)
     env.simulator.set_replay(tg(g["replay_root"]), tg(g["replay_dof_pos"]), tg(g["replay_dof_vel"]), tg(g["replay_contact"]))
+    if prepare is not None:
+        prepare(env)
     from oracle.motion_lib import MotionLib as OML
     from tests.helpers import clip_from_env_golden, skel_from_golden
 
@@ -45,6 +48,8 @@ def _trace(tag, cfgname, overrides, general):
                                reset_root=tg(g["step__reset_root"][k]), reset_dof_pos=tg(g["step__reset_dof_pos"][k]), reset_dof_vel=tg(g["step__reset_dof_vel"][k]))
         obs, rew, reset, extras = env.step({"actions": tg(g["actions_in"][k])})
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(env, k)
         w = f"{tag} step {k}: "
         rs = torch.from_numpy(g["step__reset_buf_out"][k]).bool()
         noisy_resets += int((rs & (torch.from_numpy(g["step__reset_root"][k]).abs().sum(1) > 0)).sum())
