@@ -21,7 +21,11 @@
 extern "C" {
 #endif
 
-#define PBHC_ABI_VERSION 15
+#define PBHC_ABI_VERSION 16
+/* The layout of PbhcEnvConfig and PbhcStepIO, the value of PbhcEnvConfig.abi_version.  It moves only when one of those two structs changes:
+ * the config-specialised step kernel is compiled from the text of a filled PbhcEnvConfig, and saved training states carry its fingerprint,
+ * so a change elsewhere in the ABI (version 16: PbhcFloatingParams) leaves both as they are. */
+#define PBHC_ENV_CONFIG_VERSION 15
 
 #define PBHC_OK 0
 #define PBHC_EINVAL (-22)   /* bad argument / size over a compile-time maximum */
@@ -220,7 +224,7 @@ typedef struct PbhcOutMap {
  * Filled by the host from the reference's YAML config tree (same keys); copied to the device by
  * pbhc_env_create. */
 typedef struct PbhcEnvConfig {
-  int32_t abi_version;
+  int32_t abi_version;                      /* PBHC_ENV_CONFIG_VERSION */
   int32_t num_envs;
   PbhcSkeleton skel;
   /* extended bodies: skel entries B..Bx-1 (parent, offset, local_rot) */
@@ -1149,8 +1153,11 @@ int pbhc_sizeof_joint_sim_params(void);
  * simulator also root_states), and the motion table's rows of the env's clip.  Written: the ONE frame of the window — frame_root [1,N,13],
  * frame_dof_pos / frame_dof_vel [1,N,D] whole, of frame_contact [1,N,B,3] only z of the foot bodies (floating: all three components of the
  * bodies that own contact points) — and, when non-NULL, tau0 [N,D] and base_acc / root_acc [N,6].  PbhcFloatingParams.points:
- * [PBHC_ART_MAX_BODIES, PBHC_FLOAT_MAX_POINTS, 3] floats, read only.  Everything dense, float buffers 4-byte aligned, the int64 buffers
- * 8-byte aligned (else PBHC_EINVAL). */
+ * [PBHC_ART_MAX_BODIES, PBHC_FLOAT_MAX_POINTS, 3] floats, read only.  The floating simulator's optional per-env operands, each NULL or whole:
+ * read only env_inertial [N, PBHC_ART_MAX_BODIES, 4] floats (16-byte aligned, else PBHC_EINVAL; one 16-byte load per lane), env_friction [N]
+ * floats and u_push [N,3] floats; read AND written push_counter [N] int32 and push_interval [N] int32 (every env, every step), push_vel [N,2]
+ * floats (written for the envs whose push fires, never read), stored by lane 0 of the env alone.  Everything dense, float and int32
+ * buffers 4-byte aligned, the int64 buffers 8-byte aligned (else PBHC_EINVAL). */
 int pbhc_joint_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcJointSimParams* params, void* stream);
 
 /* The articulated rigid-body simulator (pbhc_amd/simulator/articulated_sim.py ArticulatedSim; k_articulated_sim in csrc/pbhc_articulated_sim.hip): the
@@ -1211,6 +1218,21 @@ int pbhc_debug_articulated_substeps(const PbhcSkeleton* skel, const PbhcArticula
  * points: DEVICE [PBHC_ART_MAX_BODIES][PBHC_FLOAT_MAX_POINTS][3] (body frame, m; the whole table is read), of which body b uses the first
  * num_points[b].  tau0 (may be NULL): device [N,D], the
  * first sub-step's torque.  root_acc (may be NULL): device [N,6], the LAST sub-step's a_0 and alpha_0.
+ * Per-env domain randomisation (every pointer may be NULL: the feature is off and the kernel runs the path it ran without it):
+ *   env_inertial  DEVICE [N][PBHC_ART_MAX_BODIES][4], 16-byte aligned: row (n, b) = (mass, com_x, com_y, com_z) of body b in env n, which
+ *                 replaces mass[b] and com[b] there (the inertia tensor about the centre of mass stays `inertia`); rows b >= B are 0.  The
+ *                 values are the caller's statement (masses >= 0, the root's > 0): a device table is not read by the entry.
+ *   env_friction  DEVICE [N], replaces `friction` in env n.
+ *   push_counter  DEVICE int32 [N], push_interval DEVICE int32 [N] (whole seconds), push_vel DEVICE [N,2]: push_robots.  NULL together or
+ *                 set together.  In front of the sub-steps of a control step, per env, dt the env's control step:
+ *                   fire = push_counter == (int)((float)push_interval / dt);
+ *                   fire: push_counter = 0;  push_interval = min(push_lo + (int)floor(u0 (push_hi - push_lo)), push_hi - 1);
+ *                         push_vel = ((2 u1 - 1) max_push_vel_xy, (2 u2 - 1) max_push_vel_xy);  unless the previous step reset the env
+ *                         (episode_length_buf == 0): v_0.xy += push_vel with push_fixed, v_0.xy = push_vel without;
+ *                   push_counter += 1.
+ *                 (u0, u1, u2): u_push [N,3] when non-NULL, else Philox stream 22 keyed (seed, env, step counter, 22, 0), words 0..2.
+ *                 push_lo < push_hi, both >= 0, and max_push_vel_xy >= 0, else PBHC_EINVAL.  pbhc_debug_floating_substeps has no control
+ *                 step: it honours env_inertial and env_friction for its n robots and refuses a non-NULL push_counter.
  * NULL pointers (io->root_states, points included), io->num_frames != 1, B > PBHC_ART_MAX_BODIES, decimation outside [1, 64], a negative mass,
  * armature, damping, stiffness, normal_damping or friction, slip_velocity <= 0, a root mass <= 0, num_points outside [0, PBHC_FLOAT_MAX_POINTS] or
  * not 0 for a body >= B, control type "V" return PBHC_EINVAL without a launch. */
@@ -1233,6 +1255,16 @@ typedef struct PbhcFloatingParams {
   const float* points;
   float* tau0;
   float* root_acc;
+  const float* env_inertial;
+  const float* env_friction;
+  int32_t* push_counter;
+  int32_t* push_interval;
+  float* push_vel;
+  const float* u_push;
+  int32_t push_lo;                          /* push_interval is drawn from {push_lo, ..., push_hi - 1}  s */
+  int32_t push_hi;
+  float max_push_vel_xy;                    /* m / s */
+  int32_t push_fixed;                       /* != 0: the push is added to v_0.xy; 0: it replaces it */
 } PbhcFloatingParams;
 int pbhc_sizeof_floating_params(void);
 int pbhc_floating_sim_step(PbhcEnv* env, const PbhcStepIO* io, const PbhcFloatingParams* params, void* stream);

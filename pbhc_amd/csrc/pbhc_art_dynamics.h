@@ -288,10 +288,18 @@ __device__ __forceinline__ void art_integrate_root(ArtBase& base, ArtFloat& X, f
   base.R0 = quat_unit_fast(fk_mul(mk4(hw.x * sc, hw.y * sc, hw.z * sc, c), base.R0));
 }
 
+// `env_row` (FREE, per-env randomisation; else NULL): the lane's 16-byte aligned (mass, com_x, com_y, com_z) of this env, one 16-byte load,
+// in place of p.mass[lane] and p.com[lane]; the inertia about the centre of mass stays the params'
 template <typename P>
-__device__ __forceinline__ void art_lane_inertial(ArtLane& L, const P& p, int lane, int dcl, float h) {
-  L.mass = p.mass[lane];
-  L.com = mk3(p.com[lane][0], p.com[lane][1], p.com[lane][2]);
+__device__ __forceinline__ void art_lane_inertial(ArtLane& L, const P& p, int lane, int dcl, float h, const float* __restrict__ env_row = nullptr) {
+  if (env_row) {
+    const float4 r = *reinterpret_cast<const float4*>(env_row);
+    L.mass = r.x;
+    L.com = mk3(r.y, r.z, r.w);
+  } else {
+    L.mass = p.mass[lane];
+    L.com = mk3(p.com[lane][0], p.com[lane][1], p.com[lane][2]);
+  }
   L.inertia.xx = p.inertia[lane][0]; L.inertia.yy = p.inertia[lane][1]; L.inertia.zz = p.inertia[lane][2];
   L.inertia.xy = p.inertia[lane][3]; L.inertia.xz = p.inertia[lane][4]; L.inertia.yz = p.inertia[lane][5];
   L.damping = p.damping[dcl];

@@ -27,16 +27,63 @@ using namespace pbhc;
 static_assert(PBHC_FLOAT_MAX_POINTS == ART_MAX_POINTS, "the point table's width");
 
 // the lane's contact points and the contact law
-__device__ __forceinline__ void float_lane_contact(ArtFloat& X, const PbhcFloatingParams& p, int lane) {
+// (`env_friction` [N], or NULL: in place of the params' one coefficient; `envc`: the env, clamped)
+__device__ __forceinline__ void float_lane_contact(ArtFloat& X, const PbhcFloatingParams& p, int lane, const float* __restrict__ env_friction, int envc) {
   X.npts = p.num_points[lane];
   const float* r = p.points + lane * (ART_MAX_POINTS * 3);  // the table has PBHC_ART_MAX_BODIES rows: every lane's loads are in bounds
   X.r0 = mk3(r[0], r[1], r[2]); X.r1 = mk3(r[3], r[4], r[5]); X.r2 = mk3(r[6], r[7], r[8]); X.r3 = mk3(r[9], r[10], r[11]);
   const f3 zero = mk3(0.0f, 0.0f, 0.0f);
   X.f0 = zero; X.f1 = zero; X.f2 = zero; X.f3_ = zero;
-  X.stiffness = p.stiffness; X.normal_damping = p.normal_damping; X.friction = p.friction; X.slip_velocity = p.slip_velocity;
+  X.stiffness = p.stiffness; X.normal_damping = p.normal_damping; X.friction = env_friction ? env_friction[envc] : p.friction; X.slip_velocity = p.slip_velocity;
   X.ground_height = p.ground_height;
   X.g = mk3(p.gravity[0], p.gravity[1], p.gravity[2]);
   X.a0 = zero; X.alpha0 = zero;
+}
+
+// the lane's row of env_inertial ([N, PBHC_ART_MAX_BODIES, 4]; NULL without the table)
+__device__ __forceinline__ const float* float_env_row(const PbhcFloatingParams& p, int envc, int lane) {
+  return p.env_inertial ? p.env_inertial + ((size_t)envc * PBHC_ART_MAX_BODIES + (size_t)lane) * 4 : nullptr;
+}
+
+// push_robots (include/pbhc_hip.h, PbhcFloatingParams.push_counter): the env's words, loaded in front of the sub-steps with the other per-env
+// loads (the same addresses on every lane of the env: the root's state lives on every lane, so every lane evaluates the same test) ...
+struct FloatPush { int counter, interval; float u0, u1, u2; };
+__device__ __forceinline__ void float_push_load(FloatPush& P, const PbhcFloatingParams& p, int envc) {
+  typedef unsigned int u32;
+  P.counter = 0; P.interval = 0; P.u0 = P.u1 = P.u2 = 0.0f;
+  if (!p.push_counter) return;
+  // (a ragged last workgroup's missing envs load env N - 1's words from other waves while that env's lane 0 stores them: whatever they
+  // read, their results are discarded and they never store)
+  P.counter = p.push_counter[envc]; P.interval = p.push_interval[envc];
+  if (p.u_push) { P.u0 = at(p.u_push, (u32)envc * 3u); P.u1 = at(p.u_push, (u32)envc * 3u + 1u); P.u2 = at(p.u_push, (u32)envc * 3u + 2u); }
+}
+// ... and the push itself, on the root's linear velocity in registers before the first sub-step.  `just_reset`: the previous step reset the
+// env (its counter and interval are renewed and the draws consumed, the velocity is the reset's).  Lane 0 alone stores, plain vector stores.
+__device__ __forceinline__ void float_push(ArtFloat& X, FloatPush P, const PbhcFloatingParams& p, uint64_t seed, unsigned int env, int envc,
+                                           unsigned int step_ctr, float dt, bool just_reset, bool store) {
+  typedef unsigned int u32;
+  if (!p.push_counter) return;
+  const bool fire = P.counter == (int)((float)P.interval / dt);
+  float pvx = 0.0f, pvy = 0.0f;
+  if (fire) {
+    if (!p.u_push) {
+      float u[4];
+      rng_uniform4(seed, env, step_ctr, PBHC_RNG_STREAM_PUSH, 0u, u);
+      P.u0 = u[0]; P.u1 = u[1]; P.u2 = u[2];
+    }
+    P.counter = 0;
+    P.interval = min(p.push_lo + (int)floorf(P.u0 * (float)(p.push_hi - p.push_lo)), p.push_hi - 1);
+    pvx = (2.0f * P.u1 - 1.0f) * p.max_push_vel_xy;
+    pvy = (2.0f * P.u2 - 1.0f) * p.max_push_vel_xy;
+    if (!just_reset) {
+      X.v0.x = p.push_fixed ? X.v0.x + pvx : pvx;
+      X.v0.y = p.push_fixed ? X.v0.y + pvy : pvy;
+    }
+  }
+  if (!store) return;
+  p.push_counter[envc] = P.counter + 1;
+  p.push_interval[envc] = P.interval;
+  if (fire) { at(p.push_vel, (u32)envc * 2u) = pvx; at(p.push_vel, (u32)envc * 2u + 1u) = pvy; }
 }
 
 // the root's 13 words (one per lane 0..12, `rs`) onto every lane
@@ -66,6 +113,9 @@ __device__ __forceinline__ float float_acc_word(f3 a0, f3 alpha0, int lane) {
   return w;
 }
 
+// DR: a per-env operand of the params is non-NULL (env_inertial, env_friction, push_counter).  DR = false is the kernel without them: the
+// entry launches it when every one is NULL, so a simulator with the randomisation off runs the instructions it ran before there was any.
+template <bool DR>
 __global__ __launch_bounds__(PBHC_G* CL_EPB) void k_floating_sim(const PbhcEnvConfig* __restrict__ cfgp, PbhcStepIO io, PbhcFloatingParams p, ArtTree tree,
                                                                  const double* __restrict__ glob, int N) {
   ClCfg& c = *(ClCfg*)cfgp;
@@ -89,13 +139,16 @@ __global__ __launch_bounds__(PBHC_G* CL_EPB) void k_floating_sim(const PbhcEnvCo
     const f3 ax = mk3(c.skel.dof_axis[dc][0], c.skel.dof_axis[dc][1], c.skel.dof_axis[dc][2]);     // normalised as the FK's (skel_word)
     L.axis = mul3(ax, 1.0f / fmaxf(norm3(ax), 1e-9f));
   }
-  art_lane_inertial(L, p, lane, dc, h);
+  art_lane_inertial(L, p, lane, dc, h, DR ? float_env_row(p, F.envc, lane) : nullptr);
   ArtFloat X;
-  float_lane_contact(X, p, lane);
+  float_lane_contact(X, p, lane, DR ? p.env_friction : nullptr, F.envc);
+  FloatPush push;
+  if (DR) float_push_load(push, p, F.envc);
   __builtin_amdgcn_sched_barrier(0);
   cl_control(F, c, io);
   ArtBase base;
   float_root_state(base, X, rs);
+  if (DR) float_push(X, push, p, c.seed, (u32)F.env, F.envc, F.step_ctr, c.dt, F.ep1 == 1, F.valid && lane == 0);
 
   // ---- the sub-steps: torque from the current (q, v), contact from the current state, the free tree's forward dynamics, the step
   float q = F.q, v = F.v;
@@ -146,9 +199,9 @@ __global__ __launch_bounds__(PBHC_G* CL_EPB) void k_float_debug(ArtSkel sk, Pbhc
   L.off = mk3(sk.offset[lane][0], sk.offset[lane][1], sk.offset[lane][2]);
   L.lq = mk4(sk.lq_xyzw[lane][0], sk.lq_xyzw[lane][1], sk.lq_xyzw[lane][2], sk.lq_xyzw[lane][3]);
   L.axis = mk3(sk.axis[lane][0], sk.axis[lane][1], sk.axis[lane][2]);
-  art_lane_inertial(L, p, lane, dc, h);
+  art_lane_inertial(L, p, lane, dc, h, float_env_row(p, envc, lane));
   ArtFloat X;
-  float_lane_contact(X, p, lane);
+  float_lane_contact(X, p, lane, p.env_friction, envc);
   ArtBase base;
   float_root_state(base, X, at(rootp, (u32)envc * 13u + (u32)min(lane, 12)));
   float q = at(qp, eDc + dc), v = at(vp, eDc + dc);
@@ -193,6 +246,20 @@ static int float_check_params(const PbhcFloatingParams* p, int B) {
   for (int d = 0; d < B - 1; ++d) CL_CHECK(p->armature[d] >= 0.0f && p->damping[d] >= 0.0f);
   CL_CHECK(p->stiffness >= 0.0f && p->normal_damping >= 0.0f && p->friction >= 0.0f && p->slip_velocity > 0.0f);
   for (int b = 0; b < PBHC_ART_MAX_BODIES; ++b) CL_CHECK(p->num_points[b] >= 0 && p->num_points[b] <= (b < B ? PBHC_FLOAT_MAX_POINTS : 0));
+  CL_CHECK(((uintptr_t)p->env_inertial & 15) == 0);        // one 16-byte load per lane
+  CL_CHECK(((uintptr_t)p->env_friction & 3) == 0);
+  return PBHC_OK;
+}
+
+// push_robots: the three state pointers together or not at all, the draws' buffer only with them
+static int float_check_push(const PbhcFloatingParams* p) {
+  if (!p->push_counter) {
+    CL_CHECK(!p->push_interval && !p->push_vel && !p->u_push);
+    return PBHC_OK;
+  }
+  CL_CHECK(p->push_interval && p->push_vel);
+  CL_CHECK(((((uintptr_t)p->push_counter | (uintptr_t)p->push_interval | (uintptr_t)p->push_vel | (uintptr_t)p->u_push) & 3) == 0));
+  CL_CHECK(p->push_lo >= 0 && p->push_hi > p->push_lo && p->max_push_vel_xy >= 0.0f);
   return PBHC_OK;
 }
 
@@ -207,10 +274,14 @@ extern "C" int pbhc_floating_sim_step(PbhcEnv* e, const PbhcStepIO* io, const Pb
   const int D = hc->skel.num_dof, B = hc->skel.num_bodies, N = hc->num_envs;
   CL_CHECK(B <= PBHC_ART_MAX_BODIES && D == B - 1);
   if ((rc = float_check_params(p, B)) != PBHC_OK) return rc;
+  if ((rc = float_check_push(p)) != PBHC_OK) return rc;
   ArtTree tree;
   if ((rc = art_tree(hc->skel, &tree)) != PBHC_OK) return rc;
-  hipLaunchKernelGGL(k_floating_sim, dim3((N + CL_EPB - 1) / CL_EPB), dim3(PBHC_G * CL_EPB), 0, (hipStream_t)stream, dcfg, *io, *p, tree,
-                     (const double*)glob, N);
+  const dim3 grid((N + CL_EPB - 1) / CL_EPB), block(PBHC_G * CL_EPB);
+  if (p->env_inertial || p->env_friction || p->push_counter)
+    hipLaunchKernelGGL(k_floating_sim<true>, grid, block, 0, (hipStream_t)stream, dcfg, *io, *p, tree, (const double*)glob, N);
+  else
+    hipLaunchKernelGGL(k_floating_sim<false>, grid, block, 0, (hipStream_t)stream, dcfg, *io, *p, tree, (const double*)glob, N);
   if (hipGetLastError() != hipSuccess) {
     snprintf(g_pbhc_err, sizeof(g_pbhc_err), "pbhc_floating_sim_step: launch failed");
     return PBHC_EHIP;
@@ -228,6 +299,7 @@ extern "C" int pbhc_debug_floating_substeps(const PbhcSkeleton* skel, const Pbhc
   if (rc != PBHC_OK) return rc;
   const int B = skel->num_bodies;
   if ((rc = float_check_params(p, B)) != PBHC_OK) return rc;
+  CL_CHECK(!p->push_counter && !p->push_interval && !p->push_vel && !p->u_push);      // no control step here: no push
   CL_CHECK((uint64_t)n * (uint64_t)B * (uint64_t)(PBHC_FLOAT_MAX_POINTS * 3) < (1ull << 30));
   ArtSkel sk;
   art_skel(*skel, enforce_limits ? limits : nullptr, &sk);

@@ -646,7 +646,7 @@ extern "C" int pbhc_debug_fk(const PbhcSkeleton* skel, const float* root_states,
 // arithmetic only, so that a specialised kernel can be generated for a config without a device at hand (pbhc_env_config_finalize).
 static int finalize_config(const PbhcEnvConfig* cfg, PbhcEnvConfig* fin, int* lds_stride, size_t* lds_bytes) {
   ARG_CHECK(cfg && fin && lds_stride && lds_bytes);
-  ARG_CHECK(cfg->abi_version == PBHC_ABI_VERSION);
+  ARG_CHECK(cfg->abi_version == PBHC_ENV_CONFIG_VERSION);
   int rc = pbhc_check_skel(&cfg->skel);
   if (rc) return rc;
   const int Bx = cfg->skel.num_bodies_ext;

@@ -307,6 +307,8 @@ __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0
 // 21 the start-time draw of start_sampling (k_start_draw; counter words (env, step counter, 21, salt): salt 0 for the per-step launch,
 // the count of redraw-all calls otherwise).
 #define PBHC_RNG_STREAM_START_SAMPLING 21u
+// 22 push_robots of the floating-base simulator (k_floating_sim; counter words (env, step counter, 22, 0): interval, x, y).
+#define PBHC_RNG_STREAM_PUSH 22u
 // four uniforms of one Philox call, keyed (env, step, stream, idx): for draws that are consumed together
 __device__ __forceinline__ void rng_uniform4(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, uint32_t idx, float u[4]) {
   uint32_t o[4];

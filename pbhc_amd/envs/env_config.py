@@ -165,7 +165,7 @@ def build(cfg, skel, motion_lib, num_envs, device, sim_link_mass_dim, seed=0, mo
         raise _lib.PbhcError("config dof_names do not match the skeleton")
     c = _lib.PbhcEnvConfig()
     L = EnvLayout()
-    c.abi_version = K["PBHC_ABI_VERSION"]
+    c.abi_version = K["PBHC_ENV_CONFIG_VERSION"]       # the layout of this struct: not every ABI bump moves it
     c.tracking_mode = mode
     c.num_envs = num_envs
     c.skel = skel.to_c()

@@ -23,6 +23,10 @@ foot's collision capsules, friction 0.8): the robot can fall, and the loop print
 The contact defaults (stiffness 10000 N/m and normal damping 100 N s/m per point, slip velocity 0.4 m/s) pass the stability screen at the
 config's 200 Hz with a static sink of 0.39 cm; `--sim-fps F` raises sim.fps to F and the decimation with it (F must be a multiple
 of the config's fps), which a stiffer ground or a smaller slip velocity needs, and says so.
+`--randomize` (with --sim floating) turns on simulator.config.floating_sim.domain_rand.{link_mass, base_com, friction}: every env integrates
+its own link masses, torso centre of mass and friction coefficient, the ones the critic observes; the stability screen is then taken at
+friction_range[1] = 1.2, which the default slip velocity does not pass at 200 Hz, so the default becomes 0.6 m/s (and is printed).
+`--push` turns on domain_rand.push and leaves the config's push_robots as it is; without it push_robots is switched off.
 """
 import argparse
 import os
@@ -54,10 +58,16 @@ def build(args):
             ov["robot.motion.asset.assetFileName"] = args.mjcf
     elif args.sim == "floating":
         ov["simulator._target_"] = "pbhc_amd.simulator.floating_sim.FloatingBaseSim"
+        slip = args.slip_velocity if args.slip_velocity is not None else (0.6 if args.randomize else 0.4)
+        flags = dict.fromkeys(("link_mass", "base_com", "friction"), bool(args.randomize))
+        flags["push"] = bool(args.push)
         ov["simulator.config.floating_sim"] = {"armature": args.armature, "damping": args.damping, "stiffness": args.stiffness,
-                                               "normal_damping": args.normal_damping, "friction": args.friction, "slip_velocity": args.slip_velocity,
-                                               "contact_points": {"left_ankle_roll_link": G1_SOLE, "right_ankle_roll_link": G1_SOLE}}
-        ov["domain_rand.push_robots"] = False                 # (it would do nothing: the simulator has no push)
+                                               "normal_damping": args.normal_damping, "friction": args.friction, "slip_velocity": slip,
+                                               "contact_points": {"left_ankle_roll_link": G1_SOLE, "right_ankle_roll_link": G1_SOLE},
+                                               "domain_rand": flags}
+        if not args.push:
+            ov["domain_rand.push_robots"] = False             # (without --push the simulator does not push)
+        print(f"# floating_sim: slip_velocity {slip} m/s, domain_rand " + " ".join(f"{k}={int(v)}" for k, v in flags.items()))
         if args.mjcf:
             ov["robot.motion.asset.assetFileName"] = args.mjcf
         if args.sim_fps:
@@ -113,13 +123,17 @@ def main():
     ap.add_argument("--stiffness", type=float, default=10000.0, help="--sim floating: N/m per contact point")
     ap.add_argument("--normal-damping", type=float, default=100.0, help="--sim floating: N s/m per contact point")
     ap.add_argument("--friction", type=float, default=0.8)
-    ap.add_argument("--slip-velocity", type=float, default=0.4, help="--sim floating: m/s below which the friction is linear")
+    ap.add_argument("--slip-velocity", type=float, default=None, help="--sim floating: m/s below which the friction is linear (default 0.4; 0.6 with --randomize)")
+    ap.add_argument("--randomize", action="store_true", help="--sim floating: per-env link masses, torso centre of mass and friction (floating_sim.domain_rand)")
+    ap.add_argument("--push", action="store_true", help="--sim floating: push_robots as the config has it (floating_sim.domain_rand.push)")
     ap.add_argument("--sim-fps", type=int, default=0, help="--sim floating: raise sim.fps to this multiple of the config's, and the decimation with it")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--print-every", type=int, default=1)
     args = ap.parse_args()
 
+    if (args.randomize or args.push) and args.sim != "floating":
+        raise SystemExit("--randomize and --push belong to --sim floating")
     cfg, env, algo = build(args)
     algo._train_mode()
     obs = env.reset_all()

@@ -1,9 +1,11 @@
-"""k_joint_sim / k_articulated_sim under the profiler, next to the two kernels of the same mapping (k_dof_far_any, k_clip_stats).
+"""k_joint_sim / k_articulated_sim / k_floating_sim under the profiler, next to the two kernels of the same mapping (k_dof_far_any, k_clip_stats).
 
-  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/joint_sim_probe.py steps ENVS [joint|articulated|both|replay]
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/joint_sim_probe.py steps ENVS [joint|articulated|both|replay|floating|floating-dr]
         reset_all + 20 control steps of the v1 walk config on one stream with terminate_when_dof_far and clip_statistics on: per step one
         k_joint_sim (joint) or k_articulated_sim (articulated: the G1 MJCF, armature 0.02, damping 0.05), one k_dof_far_any, one k_env_step,
-        one k_env_finalize and one k_clip_stats dispatch; `both` runs the two simulators one after the other in ONE trace
+        one k_env_finalize and one k_clip_stats dispatch; `both` runs the two simulators one after the other in ONE trace;
+        floating: FloatingBaseSim (the G1 MJCF, armature 0.02, damping 0.05, eight sole points, slip velocity 0.6 m/s), floating-dr: the same
+        with all four floating_sim.domain_rand flags on and push_robots as the config has it (floating: push_robots off)
   python3 tools/joint_sim_probe.py summary DIR [DIR ...]
         per directory: dispatches, median and minimum (microseconds) of those kernels
 """
@@ -15,7 +17,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-KERNELS = ("k_joint_sim", "k_articulated_sim", "k_dof_far_any", "k_clip_stats", "k_env_step", "k_env_finalize")
+SOLE = [[0.132, 0.026, -0.035], [0.132, -0.026, -0.035], [-0.054, 0.026, -0.035], [-0.054, -0.026, -0.035]]
+KERNELS = ("k_joint_sim", "k_articulated_sim", "k_floating_sim", "k_dof_far_any", "k_clip_stats", "k_env_step", "k_env_finalize")
 
 
 def steps(num_envs, sim):
@@ -33,6 +36,14 @@ def steps(num_envs, sim):
     elif sim == "articulated":
         ov.update({"simulator._target_": "pbhc_amd.simulator.articulated_sim.ArticulatedSim",
                    "simulator.config.articulated_sim": {"armature": 0.02, "damping": 0.05},
+                   "robot.motion.asset.assetFileName": "mjcf/g1_23dof_lock_wrist_fitmotionONLY.xml"})
+    elif sim in ("floating", "floating-dr"):
+        spec = {"armature": 0.02, "damping": 0.05, "slip_velocity": 0.6, "contact_points": {"left_ankle_roll_link": SOLE, "right_ankle_roll_link": SOLE}}
+        if sim == "floating-dr":
+            spec["domain_rand"] = dict.fromkeys(("link_mass", "base_com", "friction", "push"), True)
+        else:
+            ov["domain_rand.push_robots"] = False
+        ov.update({"simulator._target_": "pbhc_amd.simulator.floating_sim.FloatingBaseSim", "simulator.config.floating_sim": spec,
                    "robot.motion.asset.assetFileName": "mjcf/g1_23dof_lock_wrist_fitmotionONLY.xml"})
     else:
         ov["simulator._target_"] = "pbhc_amd.simulator.replay_stub.ReplaySimStub"
